@@ -6,11 +6,17 @@ power-law graph S100k (N=100,000, m=10, E=999,900; BASELINE.json configs[2]): a 
 every edge, arg-min, candidate/improvement tensor, host softmax draw, add, stale arg-max, conditional remove.
 The graph is resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 SDRF is inherently sequential (each iteration depends on the previous graph), so with N > 1 every rank runs an
 independent replica (its own numpy seed) — "replicas only", no data-path collective; value = N*K / max-rank time.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else to that line, each from runs of its own: the pass time and roofline of the timed steps (HIP
+events around every pass), the incremental / host-draw / tau = inf modes, configs[2] as 500 iterations, the Cora-sized run,
+the pass at S1M, the GCN legs, the profile-keyed per-kernel figures, the reference's timing and the CPU baselines.
+--dump-outputs DIR writes what the last timed step left (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -434,6 +440,36 @@ def spawn_ranks(n):
     return rc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, run):
+    """What the timed path hands its caller after the last timed step, as DIR/<name>.npy (float32 / float64 only):
+        edge_index  [2, 2E]  the rewired graph, as rewire() returns it (node ids; float32 while they are exact in it)
+        curvature   [3, E]   u, v and the Balanced Forman curvature of every edge, from the pass the last step ran behind its edit
+        last_step   [3]      the arg-min edge (x, y) of the last step and the number of candidates it drew from
+    Above 64 MB in all, the columns of edge_index and curvature are cut to the same fixed, seeded sample (numpy's
+    default_rng(0): never the legacy global stream the SDRF draw uses), so that two builds compare position for position."""
+    G = run.G
+    ei = G.to_edge_index()
+    eu, ev, cv = G.curvature_read()
+    id_t = np.float32 if G.number_of_nodes() < (1 << 24) else np.float64
+    arrays = {'edge_index': ei.astype(id_t),
+              'curvature': np.stack([eu.astype(np.float64), ev.astype(np.float64), cv]),
+              'last_step': np.array([np.nan if v is None else v for v in run.last], dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES * 0.95 / total
+        rng = np.random.default_rng(0)
+        for name in ('edge_index', 'curvature'):
+            a = arrays[name]
+            keep = np.sort(rng.choice(a.shape[1], size=max(1, int(a.shape[1] * frac)), replace=False))
+            arrays[name] = np.ascontiguousarray(a[:, keep])
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -452,7 +488,14 @@ def main():
     ap.add_argument('--gcn-epochs', type=int, default=20)
     ap.add_argument('--gcn-warmup', type=int, default=3)
     ap.add_argument('--gcn-timeout', type=float, default=300.0)
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figure (side legs, GCN, rooflines, CPU baselines); the --no-* '
+                         'switches act on this mode')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start one fresh process per rank (nothing in this parent has
@@ -500,9 +543,11 @@ def main():
 
     for _ in range(args.warmup):
         run.step()
-    bytes0, bytes0_2s = G.bfc_algorithmic_bytes(one_sided=True), G.bfc_algorithmic_bytes()
     pass_engine = G.pass_engine() if hasattr(G, 'pass_engine') else 'node-centric'
-    G.profile_reset()
+    if args.full:
+        # the pass's own figures: byte counts on the device and HIP events around every pass of the timed steps
+        bytes0, bytes0_2s = G.bfc_algorithmic_bytes(one_sided=True), G.bfc_algorithmic_bytes()
+        G.profile_reset()
     barrier()
     t0 = time.perf_counter()
     steps_done = 0
@@ -515,8 +560,6 @@ def main():
             break
     barrier()
     elapsed = time.perf_counter() - t0
-    pass_ms_total, pass_count = G.profile_read()
-    bytes1, bytes1_2s = G.bfc_algorithmic_bytes(one_sided=True), G.bfc_algorithmic_bytes()
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
@@ -527,6 +570,33 @@ def main():
         total_steps = int(s.item())
     else:
         total_steps = steps_done
+    if total_steps < world * args.steps:   # (every rank sees the sum: all of them leave)
+        raise SystemExit(f'bench.py: the SDRF loop ended (no candidate, nothing to remove) after {steps_done} of the '
+                         f'{args.steps} timed steps: no figure for --steps {args.steps}')
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, run)
+    draws = {'device': int(getattr(run, 'device_draws', 0)), 'host': int(getattr(run, 'host_draws', 0))}
+    headline = {
+        'metric': 'SDRF iterations/sec', 'value': total_steps / elapsed, 'unit': 'iterations/sec',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': elapsed / max(steps_done, 1) * 1e3,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
+        'data': 'synthetic',
+        'config': {'workload': f'S100k: preferential-attachment graph N={n} m={args.m} E={E} (PCG64 seed 12345), '
+                               f'Balanced Forman curvature, full recompute every iteration, remove_edges=True, '
+                               f'tau={args.tau}, removal_bound={args.removal_bound}',
+                   'parallelism': 'replicas only' if world > 1 else 'single GPU'},
+        'rccl_ranks': dist.get_world_size() if dist is not None else 1,
+        'backend': (dist.get_backend() if dist is not None else None),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({**headline, 'pass_engine': pass_engine, 'draws': draws, 'full': False}), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    pass_ms_total, pass_count = G.profile_read()
+    bytes1, bytes1_2s = G.bfc_algorithmic_bytes(one_sided=True), G.bfc_algorithmic_bytes()
 
     # optional mode, reported separately (never `value`): the same iterations with the incremental curvature pass, which
     # recomputes only edges near the previous iteration's edits and leaves the same bits in the buffer
@@ -698,7 +768,6 @@ def main():
             s1m = {'error': f'{type(ex).__name__}: {ex}'[:300]}
     elif not args.no_gcn and world > 1:
         pass  # every rank generates the graph itself in gcn_bench (no broadcast of a 160 MB edge list)
-    draws = {'device': int(getattr(run, 'device_draws', 0)), 'host': int(getattr(run, 'host_draws', 0))}
     run = G = None  # release the SDRF graph before the GCN leg
     out = None
     if rank == 0:
@@ -717,17 +786,7 @@ def main():
         achieved = roof_bytes / (pass_ms * 1e-3) / 1e9
         equivalent = alg_bytes / (pass_ms * 1e-3) / 1e9
         out = {
-            'metric': 'SDRF iterations/sec', 'value': total_steps / elapsed, 'unit': 'iterations/sec',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': elapsed / max(steps_done, 1) * 1e3,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {'workload': f'S100k: preferential-attachment graph N={n} m={args.m} E={E} (PCG64 seed 12345), '
-                                   f'Balanced Forman curvature, full recompute every iteration, remove_edges=True, '
-                                   f'tau={args.tau}, removal_bound={args.removal_bound}',
-                       'parallelism': 'replicas only' if world > 1 else 'single GPU'},
-            'rccl_ranks': dist.get_world_size() if dist is not None else 1,
-            'backend': (dist.get_backend() if dist is not None else None),
+            **headline, 'full': True,
             'bfc_edges_per_sec': E / (pass_ms * 1e-3),
             'bfc_pass_ms': pass_ms,
             'outside_pass_ms': elapsed / max(steps_done, 1) * 1e3 - pass_ms,

@@ -75,17 +75,20 @@ def test_citeseer_shape_on_a_rewired_graph_logits_and_gradients():
         assert (layer.bias.grad.double() - b.grad).abs().max().item() < 1e-5
 
 
-def _s1m_inputs(dev):
+_S1M_REWIRED = {}
+
+
+def _s1m_inputs(dev, ei=None):
     """configs[4] as BASELINE.json words it: the 1M-node / 10M-edge graph REWIRED (rewire('bfc', ...) with the loop parameters of
     tests/golden/sdrf_s1m_oracle.json: three iterations, tau = 163, bound 0.95, numpy seed 0), checked against the edge list the
-    C oracle recorded for the same run (SHA-256 of the int64 edge_index), then the features."""
+    C oracle recorded for the same run (SHA-256 of the int64 edge_index), then the features.  ``ei``: that edge list, already
+    checked (the two-rank workers get it from their parent)."""
     import hashlib
     import json
     from dcr import synthetic
-    path = '/tmp/dcr_s1m_rewired_edge_index.npy'
-    if os.path.exists(path):
-        ei = np.load(path)
-    else:
+    if ei is None:
+        ei = _S1M_REWIRED.get('edge_index')   # (rewired once per session, kept in memory: nothing written outside the repository)
+    if ei is None:
         from dcr.data import Data
         from rewiring.rewire import rewire
         fix = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'sdrf_s1m_oracle.json')))
@@ -95,7 +98,7 @@ def _s1m_inputs(dev):
                     fix['removal_bound'], fix['tau']).numpy()
         assert hashlib.sha256(np.ascontiguousarray(ei).tobytes()).hexdigest() == fix['final']['edge_index_sha256']
         assert ei.shape[1] // 2 == fix['final']['edges'] != raw.shape[1] // 2
-        np.save(path, ei)
+        _S1M_REWIRED['edge_index'] = ei
     n = 1_000_000
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(n, 256, device=dev, generator=g)
@@ -244,14 +247,14 @@ def _s1m_worker(rank, world, port, rows_path, ret):
     from models.gcn import GCN
     from models.gcn_dp import ShardedGCN
     dev = torch.device('cuda', 0)
-    ei, n, x = _s1m_inputs(dev)
+    saved = torch.load(rows_path)
+    ei, n, x = _s1m_inputs(dev, saved['edge_index'].numpy())
     torch.manual_seed(2)
     model = GCN(Dataset(Data(x=x, edge_index=ei, num_nodes=n), 16), hidden=[128], dropout=0.5).to(dev)
     sh = ShardedGCN(model, ei, n)
     sh.eval()
     with torch.no_grad():
         local = sh(sh.shard(x))
-    saved = torch.load(rows_path)
     rows, want = saved['rows'].to(dev), saved['logits'].to(dev)
     where = torch.full((n,), -1, dtype=torch.int64, device=dev)      # position of a node inside this rank's block, or -1
     where[sh.owned] = torch.arange(sh.owned.shape[0], device=dev)
@@ -278,7 +281,7 @@ def test_s1m_logits_fp64_check_and_two_rank_equality(tmp_path):
     assert err < 1e-5, err
     rows = torch.randperm(n, generator=torch.Generator().manual_seed(9))[:2000]
     rows_path = str(tmp_path / 'rows.pt')
-    torch.save({'rows': rows, 'logits': got[rows.to(dev)].cpu()}, rows_path)
+    torch.save({'rows': rows, 'logits': got[rows.to(dev)].cpu(), 'edge_index': ei.cpu()}, rows_path)
     del got, want, model, x, ei
     torch.cuda.empty_cache()
     with socket.socket() as s:
