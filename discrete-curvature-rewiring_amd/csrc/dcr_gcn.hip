@@ -824,7 +824,6 @@ __global__ void __launch_bounds__(256) k_picked_mean_fwd(const float *__restrict
     double *picked_partial = ws->loss_part;
     unsigned &picked_ticket = ws->ticket_fwd;
     __shared__ double red[256];
-    __shared__ int last_sh;
     const int64_t per = (m + gridDim.x - 1) / gridDim.x;
     const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
     double a = 0.0;
@@ -838,13 +837,8 @@ __global__ void __launch_bounds__(256) k_picked_mean_fwd(const float *__restrict
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&picked_partial[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (through the L2, as the head kernels)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        last_sh = atomicAdd(&picked_ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last_sh) return;
+    if (threadIdx.x == 0) __hip_atomic_store(&picked_partial[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!last_arriver(&picked_ticket, gridDim.x)) return;
     red[threadIdx.x] = (int)threadIdx.x < (int)gridDim.x
                            ? __hip_atomic_load(&picked_partial[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     __syncthreads();
@@ -904,9 +898,9 @@ __global__ void __launch_bounds__(256) k_count_argmax_equal(const float *__restr
 //             of per-block sums in block order); correct = number of evaluated rows whose first maximum is their label;
 //   backward: grad[i, c] = (exp(o[i, c] - lse_i) - [c == y_i]) * g / m, and its column sums (per-block partials added in block
 //             order: deterministic) = the gradient of the last layer's bias.
-// The last block to finish (a ticket behind an agent-scope fence) closes each reduction; partials and tickets live in a
-// workspace of the CALLER (advisor, round 4: the round-4 loss kernel kept them in process-global device variables, shared by
-// every stream) whose tickets are zero before the first use and left zero by every launch.
+// The last block to finish (last_arriver) closes each reduction; partials and tickets live in a workspace of the CALLER (as
+// process-global device variables they were shared by every stream) whose tickets are zero before the first use and left
+// zero by every launch.
 
 template <int C>
 __device__ __forceinline__ float head_lse(const float (&o)[C], int classes) {
@@ -945,7 +939,6 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float *__restrict__ o_tr
                                                   long long *__restrict__ out_correct, HeadWs *__restrict__ ws) {
     __shared__ double red[256];
     __shared__ unsigned long long redh[256];
-    __shared__ int last_sh;
     const int b = blockIdx.x;
     double a = 0.0;
     unsigned long long hits = 0ull;
@@ -994,15 +987,10 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float *__restrict__ o_tr
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        // (the partials go through the L2 — sc1 stores — so that no agent-scope fence, an L2 write-back per block, is needed ahead
-        //  of the ticket: csrc/dcr_gcn_first.hip, round 5)
         __hip_atomic_store(&ws->loss_part[b], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&ws->hit_part[b], redh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        last_sh = atomicAdd(&ws->ticket_fwd, 1u) == gridDim.x - 1;
     }
-    __syncthreads();
-    if (!last_sh) return;
+    if (!last_arriver(&ws->ticket_fwd, gridDim.x)) return;
     // at most 256 partials of each kind (head_blocks): one per thread, then the same fixed tree as above.  (First version: one
     // thread adding them one after the other — 782 dependent L2 round trips, 111 us for a kernel whose work is 5 us.)
     red[threadIdx.x] = (int)threadIdx.x < nb_tr ? __hip_atomic_load(&ws->loss_part[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
@@ -1027,7 +1015,6 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float *__restrict__ o_tr
                                                   int classes, const float *__restrict__ g, float *__restrict__ grad,
                                                   float *__restrict__ grad_bias, HeadWs *__restrict__ ws) {
     __shared__ float red[4][HEAD_MAXC];
-    __shared__ int last_sh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float scale = g[0] / (float)m_tr;
     const int64_t per = (m_tr + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * per, hi = lo + per < m_tr ? lo + per : m_tr;
@@ -1068,10 +1055,7 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float *__restrict__ o_tr
         __hip_atomic_store(&ws->col_part[blockIdx.x][threadIdx.x],
                            threadIdx.x < (unsigned)C ? ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x] : 0.f,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();   // (waits for every thread's stores: the barrier carries a workgroup-scope fence)
-    if (threadIdx.x == 0) last_sh = atomicAdd(&ws->ticket_bwd, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last_sh) return;
+    if (!last_arriver(&ws->ticket_bwd, gridDim.x)) return;
     // the blocks' column sums: thread (column c, group j) adds blocks j, j + 8, ... (at most 32 independent loads), the eight
     // groups are then added in group order
     __shared__ float fin[8][HEAD_MAXC];
@@ -1155,11 +1139,7 @@ __global__ void __launch_bounds__(256) k_adam_multi(AdamArgs A, float *__restric
         vv[i] = v;
         pp[i] = p0 - step_size * (m / (sqrtf(v) / bc2_sqrt + A.eps));
     }
-    __shared__ int last_sh;
-    __syncthreads();
-    if (threadIdx.x == 0) last_sh = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (last_sh && threadIdx.x == 0) {
+    if (last_arriver(ticket, gridDim.x) && threadIdx.x == 0) {
         step[0] = t;
         *ticket = 0u;
     }

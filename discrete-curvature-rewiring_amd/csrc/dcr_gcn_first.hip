@@ -369,7 +369,7 @@ static int launch_first_layer(bool train, bool eval, const float *ax, int64_t ld
 //     once in LDS (XOR-swizzled as above; columns past in_features are zeros, so in_features need not be a multiple of 16 —
 //     Â·X is padded to one by the caller) and kept while the workgroup walks its row groups (persistent for large N);
 //   * each wave leaves its partial tile [16 rows x H] in the workspace, part[chunk][row][column]; the LAST workgroup of a row
-//     group to arrive (a ticket per row group behind an agent-scope fence) adds the chunks' partials IN CHUNK ORDER —
+//     group to arrive (a ticket per row group: last_arriver) adds the chunks' partials IN CHUNK ORDER —
 //     deterministic whichever workgroup that is — and runs first_epilogue on the sums: bias, pre, Philox keep bits, both
 //     second-layer contractions.  One launch from Â·X to [z_train | z_eval]; the pre-activation is written once.
 // Citeseer shape (2,120 x 3,712 -> 64): 34 row groups x 15 chunks = 510 workgroups of 69 KB LDS (two per CU), 256 MFMAs per wave.
@@ -385,7 +385,6 @@ __global__ void __launch_bounds__(256, 2) k_first_layer_wide(FirstArgs A, const 
                                                           int64_t n_groups, int64_t rows_padded) {
     constexpr int H = 16 * HM, KCH = wide_kch<HM>(), FS = KCH, HS = H, NM = KCH / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int last_sh;
     float *w1s = lds;               // [H][FS]: this chunk's columns of W1
     float *w2s = w1s + H * FS;      // [16][HS], rows >= C zero
     float *b1s = w2s + 16 * HS;     // [H]
@@ -483,11 +482,8 @@ __global__ void __launch_bounds__(256, 2) k_first_layer_wide(FirstArgs A, const 
                     }
                 }
             }
-            // the partial tile: register r of acc[t] is column 16t + 4g + r of row i.  Written (and read back below) with
-            // agent-scope relaxed atomics, i.e. plain stores / loads that go THROUGH the XCD's L2 (sc1): the tiles are then
-            // visible to the other XCDs without an agent-scope release fence, which writes back and invalidates the whole L2 —
-            // 510 of them cost 45 of the kernel's 80 us at the Citeseer shape (tools/r05_probe9.sh; timing-only build without
-            // fences: 36 us).  What orders tile and ticket is the wait for the stores (workgroup-scope release) ahead of the barrier.
+            // the partial tile: register r of acc[t] is column 16t + 4g + r of row i, stored (and read back below) through the
+            // L2 with agent-scope relaxed atomics (sc1), as last_arriver asks
             unsigned long long *dst = reinterpret_cast<unsigned long long *>(part + ((int64_t)chunk * rows_padded + unit * 16 + i) * H + 4 * g);
 #pragma unroll
             for (int t = 0; t < HM; ++t) {
@@ -497,17 +493,14 @@ __global__ void __launch_bounds__(256, 2) k_first_layer_wide(FirstArgs A, const 
                                    __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        // the next row group's pieces (large N: a workgroup keeps its chunk of W1 and walks row groups) fly under the ticket
+        const bool last = last_arriver(&tickets[rg], (unsigned)n_chunks);
+        // the next row group's pieces (large N: a workgroup keeps its chunk of W1 and walks row groups) fly under the closing
+        // work; issued after the ticket, whose drain would otherwise wait for them too
         if (rg + gridDim.x < n_groups) {
             const int64_t un = (rg + gridDim.x) * 4 + wave;
             load_rows(un < n_units ? un : 0, a);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");    // every wave's tile stores have completed ...
-        __syncthreads();
-        if (threadIdx.x == 0) last_sh = atomicAdd(&tickets[rg], 1u) == (unsigned)(n_chunks - 1);   // ... before the ticket is taken
-        __syncthreads();
-        if (last_sh) {      // uniform over the workgroup: every chunk's tiles of this row group are in memory
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (last) {      // every chunk's tiles of this row group are in memory
             if (have) {
                 f32x4 acc[HM];
 #pragma unroll
@@ -537,7 +530,6 @@ __global__ void __launch_bounds__(256, 2) k_first_layer_wide(FirstArgs A, const 
             }
             if (threadIdx.x == 0) tickets[rg] = 0u;   // (for the next call: the tickets are all-zero between launches)
         }
-        __syncthreads();    // last_sh is rewritten by the next row group
     }
 }
 

@@ -175,6 +175,23 @@ __device__ inline Ext ext_make(double v, int sl) {
     return e;
 }
 
+// ---- last-workgroup ticket: the workgroup that arrives last closes a reduction over every workgroup's partial ----------
+// Call from every thread of the workgroup after its payload stores, which are agent-scope relaxed atomics (sc1: through the L2).
+// Every wave drains its stores (written out: a wait the compiler inserts can be dropped), the workgroup meets, and one lane
+// takes the ticket with a relaxed agent-scope add.  Returns true, in every thread, in the workgroup that arrived last; that
+// workgroup reads the partials with agent-scope relaxed (sc1) loads, or with plain loads behind fence(acquire, "agent").
+// A workgroup-scope fence or a bare barrier is no release for other CUs: it waits for no store (MI355X_MICROARCH.md,
+// § Workgroup dispatch ... inter-workgroup visibility, Valid forms and the first row of its hand-off table).
+template <typename T>
+__device__ inline bool last_arriver(T *ticket, T arrivals) {
+    __shared__ int last;
+    asm volatile("s_waitcnt vmcnt(0) ; dcr ticket drain" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(ticket, (T)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1;
+    __syncthreads();
+    return last;
+}
+
 struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in device memory
     int32_t x, y, dx, dy;
     int32_t T, s1, s2;

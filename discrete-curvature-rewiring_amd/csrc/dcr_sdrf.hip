@@ -568,7 +568,7 @@ __global__ void __launch_bounds__(256) k_imp_bc(RowView g, ImpBuf B, int x, int 
 __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int x, int y, unsigned mask, int words, int curv_type,
                                                          DevResult *res) {
     extern __shared__ uint32_t bits[];
-    __shared__ int cnt_sh, c1_sh, last_sh;
+    __shared__ int cnt_sh, c1_sh;
     __shared__ int shi[16 * 4];
     ImpStats *stp = B.st;
     const int dx = stp->dx, dy = stp->dy;
@@ -594,7 +594,7 @@ __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int
         cnt_sh = 0;
         c1_sh = 0;
         // (what the closing workgroup reads of this one — clsx, rowcount, c1 — is stored through the L2 with agent-scope relaxed
-        //  atomics: see the ticket below)
+        //  atomics, as last_arriver asks; c2 is updated by device-scope atomics)
         if (a < dx) __hip_atomic_store(&B.clsx[a], cls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
@@ -652,20 +652,12 @@ __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int
     if ((threadIdx.x & 63) == 0 && adm) atomicAdd(&cnt_sh, adm);
     __syncthreads();
     if (threadIdx.x == 0) {
-        // Round 5: an agent-scope release fence writes back the whole L2 of its XCD (csrc/dcr_gcn_first.hip found 45 us of them in one
-        // kernel; here 1,400 workgroups' fences were 11 of this kernel's 44 us: the round-4 timing-only build).  The three words the
-        // closing workgroup reads of this one go through the L2 instead (sc1 stores), c2 is updated by device-scope atomics anyway,
-        // and all that orders them against the ticket is the wait for the stores (a workgroup-scope release).
         __hip_atomic_store(&B.rowcount[a], cnt_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (a < dx) __hip_atomic_store(&B.c1[a], counting ? c1_sh : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        last_sh = atomicAdd(&stp->done_rows, 1) == (int)gridDim.x - 1;
     }
-    __syncthreads();
-    if (!last_sh) return;  // uniform
-    // every other workgroup's results are visible from here on: they went through the L2 (sc1 stores, device-scope atomics) before
-    // the tickets; this workgroup only has to drop what its own caches may hold (an agent-scope ACQUIRE: buffer_inv, no write-back
-    // of the L2 as __threadfence() has it)
+    if (!last_arriver(&stp->done_rows, (int)gridDim.x)) return;
+    // imp_close_stats reads c1, c2 and clsx with plain loads, hence the agent-scope acquire (buffer_inv: drops this CU's stale
+    // lines, no write-back of the L2 as __threadfence() has it)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     imp_close_stats(B, curv_type, shi);
     // exclusive scan of rowcount[0 .. rows): the candidates are emitted row by row (sdrf_no_cuda.py:32-37: outer loop over x_nb)
@@ -843,16 +835,9 @@ __device__ void draw_block_sum(const double *__restrict__ imp, const DevResult *
 __global__ void __launch_bounds__(256) k_draw_partial(const double *__restrict__ imp, const int32_t *__restrict__ ci,
                                                        const int32_t *__restrict__ cj, DevResult *res, double tau, double u,
                                                        double *bsum, double margin_scale, ImpStats *st) {
-    __shared__ int last_sh;
     draw_block_sum(imp, res, tau, bsum);
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the block sum's store (sc1) has completed before the ticket is taken
-        last_sh = atomicAdd(&st->done_draw, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last_sh) return;  // uniform
-    // (no agent fence: the block sums are read through the L2 — sc1 loads in draw_pick_block — and everything else this
-    //  workgroup reads was written by earlier kernels)
+    if (!last_arriver(&st->done_draw, (int)gridDim.x)) return;
+    // (the block sums are read with sc1 loads in draw_pick_block; everything else it reads was written by earlier kernels)
     draw_pick_block(imp, ci, cj, res, tau, u, bsum, margin_scale);
 }
 
@@ -871,7 +856,7 @@ __device__ void draw_block_sum(const double *__restrict__ imp, const DevResult *
         if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
         __syncthreads();
     }
-    if (threadIdx.x == 0) __hip_atomic_store(&bsum[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (through the L2: no agent fence below)
+    if (threadIdx.x == 0) __hip_atomic_store(&bsum[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (through the L2: last_arriver)
 }
 
 __device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *__restrict__ ci, const int32_t *__restrict__ cj,

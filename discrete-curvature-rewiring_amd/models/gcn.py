@@ -350,20 +350,34 @@ class _AggregateRowsPair(torch.autograd.Function):
         return gz, None, gb, None, None, None
 
 
-_HEAD_WS = {}
+_WORKSPACES = {}
+
+
+def _workspace(kind, device, stream, *shape):
+    """Partials + tickets of the kernels whose last workgroup closes a reduction: 'head' (dcr_head_*, the picked-mean loss)
+    or 'first' (the K-chunked first layer; shape = (n, feats, hidden), None where W1 stays resident in LDS).  The tickets are
+    zero before the first launch and every launch leaves them zero, so a buffer is zero-filled once, on creation, and needs
+    no fill launch per call.  One buffer per (kind, device, stream, shape), never evicted: a captured epoch replays on the
+    raw pointers it was captured with."""
+    key = (kind, str(device), int(stream)) + tuple(int(v) for v in shape)
+    if key not in _WORKSPACES:
+        from dcr import _lib
+        need = ctypes.c_int64()
+        if kind == 'head':
+            _lib.check(_lib.lib().dcr_head_workspace(ctypes.byref(need)))
+            _WORKSPACES[key] = torch.zeros((need.value + 7) // 8, dtype=torch.int64, device=device)
+        else:
+            _lib.check(_lib.lib().dcr_first_layer_fwd_workspace(*key[3:], ctypes.byref(need)))
+            _WORKSPACES[key] = torch.zeros(need.value, dtype=torch.float32, device=device) if need.value else None
+    return _WORKSPACES[key]
 
 
 def _head_workspace(device, stream):
-    """Partials + tickets of the head kernels (dcr_head_*): zero before the first use, left zero by every launch — allocated
-    once per (device, stream) and kept, so that the captured epoch replays on a buffer that outlives the capture."""
-    from dcr import _lib
-    key = (str(device), int(stream))
-    ws = _HEAD_WS.get(key)
-    if ws is None:
-        need = ctypes.c_int64()
-        _lib.check(_lib.lib().dcr_head_workspace(ctypes.byref(need)))
-        ws = _HEAD_WS[key] = torch.zeros((need.value + 7) // 8, dtype=torch.int64, device=device)
-    return ws
+    return _workspace('head', device, stream)
+
+
+def _first_layer_workspace(device, stream, n, feats, hidden):
+    return _workspace('first', device, stream, n, feats, hidden)
 
 
 def head_ok(z, sel_train, sel_eval, n_classes):
@@ -816,28 +830,6 @@ class _FirstLayerFn(torch.autograd.Function):
             gw1 = atb_hip(gx, ax) if tall else gx.t() @ ax
         gb1 = colsum if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return None, gw1, gb1, (gw2 if ctx.needs_input_grad[3] else None), None, None, None
-
-
-_FIRST_WS = {}
-
-
-def _first_layer_workspace(device, stream, n, feats, hidden):
-    """Workspace of the K-chunked first-layer kernel (None for shapes whose W1 stays resident in LDS): partial tiles + one
-    ticket per 64 rows.  The tickets must be zero before the first launch and every launch leaves them zero, so the buffer is
-    allocated (zeroed) once per (device, stream, shape) and kept: no fill launch per call, and the captured epoch replays on a
-    buffer that outlives the capture."""
-    from dcr import _lib
-    need = ctypes.c_int64()
-    _lib.check(_lib.lib().dcr_first_layer_fwd_workspace(n, feats, hidden, ctypes.byref(need)))
-    if need.value == 0:
-        return None
-    key = (str(device), int(stream), int(n), int(feats), int(hidden))
-    ws = _FIRST_WS.get(key)
-    if ws is None:
-        if len(_FIRST_WS) >= 8:
-            _FIRST_WS.pop(next(iter(_FIRST_WS)))
-        ws = _FIRST_WS[key] = torch.zeros(need.value, dtype=torch.float32, device=device)
-    return ws
 
 
 def first_layer_fused_ok(x, act_fn, first, lin2):

@@ -834,6 +834,26 @@ def test_first_layer_activation_and_next_lin_in_one_kernel(feats, hidden, classe
 
 
 @pytest.mark.gpu
+def test_workspaces_are_kept():
+    """models/gcn.py::_workspace, the one cache behind _first_layer_workspace and _head_workspace: a captured epoch holds raw
+    pointers into these buffers, so none is ever evicted — the first of more than eight first-layer shapes is the same buffer
+    when asked for again; the head's is one per stream; a shape whose W1 stays resident in LDS has none."""
+    from models import gcn
+    dev = torch.device('cuda', 0)
+    cur = torch.cuda.current_stream(dev).cuda_stream
+    first = [gcn._first_layer_workspace(dev, cur, 16 * k, 1433, 128) for k in range(1, 11)]
+    assert all(ws is not None and ws.dtype == torch.float32 for ws in first)
+    assert gcn._first_layer_workspace(dev, cur, 16, 1433, 128).data_ptr() == first[0].data_ptr()
+    assert gcn._first_layer_workspace(dev, cur, 16, 3703, 64).data_ptr() != first[0].data_ptr()
+    assert gcn._first_layer_workspace(dev, cur, 16, 64, 128) is None
+    head = gcn._head_workspace(dev, cur)
+    assert head.dtype == torch.int64
+    assert gcn._head_workspace(dev, cur) is head
+    side = torch.cuda.Stream(dev)
+    assert gcn._head_workspace(dev, side.cuda_stream).data_ptr() != head.data_ptr()
+
+
+@pytest.mark.gpu
 def test_model_with_the_one_kernel_first_layer_equals_the_separate_kernels(monkeypatch):
     """GCN.forward / forward_pair on a shape the one-kernel first layer takes (32 features, hidden 64): logits and gradients
     within float32 rounding of the route through the GEMM library + dcr_act_linear_fwd_f32_dev (DCR_FIRST_FUSED=0), and of the
