@@ -23,6 +23,8 @@ import os
 import torch
 import torch.nn.functional as F
 
+from models.gcn import HEAD_MAX_CLASSES
+
 
 class _PickedMean(torch.autograd.Function):
     """``-log_probs.gather(1, y[:, None]).mean()`` and its backward as one kernel each (csrc/dcr_gcn.hip): the gradient is
@@ -83,26 +85,32 @@ _LABELS_OK = {}
 
 def _head_classes(model):
     """Output width of a model that offers ``forward_head`` (models/gcn.py: loss and accuracy straight from the last
-    aggregation's raw outputs, one kernel each way), else None."""
+    aggregation's raw outputs, one kernel each way), else None — also for a width the head kernels do not take (1..32), so
+    that such a model goes the stock way from the start."""
     if not hasattr(model, 'forward_head') or os.environ.get('DCR_FUSED_HEAD', '1') == '0':
         return None
     layers = getattr(model, 'layers', None)
-    return int(getattr(layers[-1], 'out_channels', 0)) or None if layers is not None and len(layers) > 1 else None
+    if layers is None or len(layers) < 2:
+        return None
+    c = int(getattr(layers[-1], 'out_channels', 0))
+    return c if 1 <= c <= HEAD_MAX_CLASSES else None
 
 
 def _labels_in_range(y, n_classes):
     """The head kernels read labels as int64 class ids in [0, n_classes): F.nll_loss raises on anything else except
     ignore_index = -100, which it leaves out of the mean — such labels keep the stock ops.  One host sync per label tensor
-    (cached on its storage and version)."""
+    (cached on its storage and version).  The entry holds the tensor it was computed for and a hit must be that tensor: its
+    storage cannot be recycled for another label tensor meanwhile, and another tensor over the same memory (with a version
+    counter of its own) is checked afresh."""
     if y.dtype != torch.int64 or not y.is_cuda or y.numel() == 0:
         return False
     key = (y.data_ptr(), y._version, tuple(y.shape), n_classes)
     hit = _LABELS_OK.get(key)
-    if hit is None:
+    if hit is None or hit[1] is not y:
         if len(_LABELS_OK) >= 64:
             _LABELS_OK.clear()
-        hit = _LABELS_OK[key] = bool(int(y.min()) >= 0 and int(y.max()) < n_classes)
-    return hit
+        hit = _LABELS_OK[key] = (bool(int(y.min()) >= 0 and int(y.max()) < n_classes), y)
+    return hit[0]
 
 
 def train(model, optimizer, data):

@@ -50,6 +50,19 @@ def _csr_from_coo(target, source, w, n_rows):
     return rowptr, source[perm].to(torch.int32).contiguous(), w[perm].contiguous()
 
 
+def _weighted_degree(source, target, w, n):
+    """deg = scatter_add(w, target), float32, the same bits on every run.  On the GPU a scatter of float32 atomics adds in the
+    order the threads arrive: weights that are not small integers then gave another Â, and other trained weights, from one
+    run to the next.  There the weights are grouped by target (the CSR of Â's pattern) and each row is summed by the
+    aggregation kernel against a column of ones, which adds a row's entries in a fixed order (csrc/dcr_gcn.hip, k_spmm_csr).
+    Unit weights give exact integer sums either way, the degrees of the published formula.  On the CPU, ``scatter_add_``
+    adds in index order."""
+    if _AGG_BACKEND == 'hip' and w.is_cuda:
+        rowptr, cols, vals = _csr_from_coo(target, source, w, n)
+        return _spmm_hip(rowptr, cols, vals, torch.ones((n, 1), dtype=torch.float32, device=w.device), n)[:, 0]
+    return torch.zeros(n, dtype=torch.float32, device=w.device).scatter_add_(0, target, w)
+
+
 def gcn_norm_csr(edge_index, edge_weight=None, num_nodes=None, add_self_loops=True, row_range=None):
     """PyG 2.0.3 ``gcn_norm`` (flow source_to_target): weights 1 if None;
     ``add_remaining_self_loops(fill_value=1)``; deg = scatter_add(w, target);
@@ -71,7 +84,7 @@ def gcn_norm_csr(edge_index, edge_weight=None, num_nodes=None, add_self_loops=Tr
         row = torch.cat([row[keep], ar])
         col = torch.cat([col[keep], ar])
         w = torch.cat([w[keep], loop_w])
-    deg = torch.zeros(n, dtype=torch.float32, device=dev).scatter_add_(0, col, w)
+    deg = _weighted_degree(row, col, w, n)
     dinv = deg.pow(-0.5)
     dinv[torch.isinf(dinv)] = 0
     norm = dinv[row] * w * dinv[col]
@@ -380,9 +393,13 @@ def _first_layer_workspace(device, stream, n, feats, hidden):
     return _workspace('first', device, stream, n, feats, hidden)
 
 
+HEAD_MAX_CLASSES = 32   # (dcr_head_*: HEAD_MAXC in csrc/dcr_gcn.hip)
+
+
 def head_ok(z, sel_train, sel_eval, n_classes):
-    """Whether the one-kernel head takes these outputs: fp32 on the GPU, at most 32 classes, row selections without repeats."""
-    return (_AGG_BACKEND == 'hip' and z.is_cuda and z.dtype == torch.float32 and 1 <= n_classes <= 32
+    """Whether the one-kernel head takes outputs of ``z``'s device and dtype: fp32 on the GPU, at most 32 classes, row
+    selections without repeats."""
+    return (_AGG_BACKEND == 'hip' and z.is_cuda and z.dtype == torch.float32 and 1 <= n_classes <= HEAD_MAX_CLASSES
             and (sel_train is None or sel_train.expand is None) and (sel_eval is None or sel_eval.expand is None)
             and os.environ.get('DCR_FUSED_HEAD', '1') != '0')
 
@@ -1162,6 +1179,14 @@ def _forward_head(self, data, rows_train=None, y_train=None, rows_eval=None, y_e
         return None
     conv = self.layers[last]
     first = self.layers[0]
+    # eligibility is decided before anything runs: a forward computed and then dropped would have drawn its dropout decisions
+    # (the caller's stock forward draws again, so the run would differ from DCR_FUSED_HEAD=0) and, in a capture, left dead
+    # kernels in the graph.  The last layer's Â and row selections are the ones its aggregation uses below (cached).
+    csr_last = conv.norm_csr(data.edge_index, data.edge_attr, data.x.shape[0])
+    sel_tr = conv.row_selection(rows_train, csr_last) if want_tr else None
+    sel_ev = conv.row_selection(rows_eval, csr_last) if want_ev else None
+    if data.x.dtype != torch.float32 or not head_ok(conv.lin.weight, sel_tr, sel_ev, conv.out_channels):
+        return None
     z_first = self._fused_first(data, want_tr, want_ev)
     if z_first is None:
         if want_tr:
@@ -1185,10 +1210,6 @@ def _forward_head(self, data, rows_train=None, y_train=None, rows_eval=None, y_e
         ref = z_tr if want_tr else z_ev
         csr = layer.norm_csr(data.edge_index, data.edge_attr, ref.shape[0])
         if depth == last:
-            sel_tr = layer.row_selection(rows_train, csr) if want_tr else None
-            sel_ev = layer.row_selection(rows_eval, csr) if want_ev else None
-            if not head_ok(ref, sel_tr, sel_ev, ref.shape[1]):
-                return None
             return _AggregateRowsHead.apply(z_tr, z_ev, layer.bias, csr, sel_tr, sel_ev, y_train, y_eval)
         if want_tr and want_ev:
             o_tr, o_ev = _AggregatePair.apply(z_tr, z_ev, layer.bias, csr)

@@ -158,7 +158,8 @@ class _GatherAggregatePair(torch.autograd.Function):
 
 
 class ShardedGCN(torch.nn.Module):
-    """Wraps a replicated ``GCN`` and runs it on this rank's block of nodes."""
+    """Wraps a replicated ``GCN`` and runs it on this rank's block of nodes.  It takes no edge weights: Â is built with unit
+    weights whatever ``data.edge_attr`` holds (the single-process ``GCN`` reads it)."""
 
     def __init__(self, gcn: GCN, edge_index, num_nodes, group=None):
         super().__init__()

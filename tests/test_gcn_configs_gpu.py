@@ -16,28 +16,15 @@ import numpy as np
 import pytest
 import torch
 
+from gcn_fp64 import gcn_logits
+
 pytestmark = pytest.mark.gpu
 
 
-def _fp64_logits(weights, x, edge_index, n, chunk=4_000_000):
-    """log_softmax(Â·relu(Â·(X·W1ᵀ) + b1)·W2ᵀ + b2) in float64, Â = D^-1/2 (A + I) D^-1/2 from the raw edge list."""
-    (w1, b1), (w2, b2) = weights
-    src, dst = edge_index[0], edge_index[1]
-    loops = torch.arange(n, device=x.device)
-    src, dst = torch.cat([src, loops]), torch.cat([dst, loops])
-    deg = torch.zeros(n, dtype=torch.float64, device=x.device).index_add_(0, dst, torch.ones_like(dst, dtype=torch.float64))
-    dinv = deg.pow(-0.5)
-    val = dinv[src] * dinv[dst]
-
-    def propagate(z):
-        out = torch.zeros((n, z.shape[1]), dtype=torch.float64, device=z.device)
-        for s in range(0, src.shape[0], chunk):
-            e = slice(s, s + chunk)
-            out.index_add_(0, dst[e], z[src[e]] * val[e, None])
-        return out
-    h = propagate(x.double() @ w1.double().t()) + b1.double()
-    h = propagate(torch.relu(h) @ w2.double().t()) + b2.double()
-    return torch.log_softmax(h, dim=1)
+def _fp64_logits(weights, x, edge_index, n, chunk=4_000_000, edge_weight=None):
+    """log_softmax(Â·relu(Â·(X·W1ᵀ) + b1)·W2ᵀ + b2) in float64, Â = D^-1/2 (A + I) D^-1/2 from the raw edge list (with
+    ``edge_weight`` and the self-loops PyG's gcn_norm keeps: tests/gcn_fp64.py)."""
+    return gcn_logits(weights, x, edge_index, n, edge_weight=edge_weight, chunk=chunk)
 
 
 def test_citeseer_shape_on_a_rewired_graph_logits_and_gradients():
