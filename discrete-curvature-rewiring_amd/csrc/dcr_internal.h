@@ -323,6 +323,14 @@ struct dcr_graph {
     dcr::ImpStats *imp_stats = nullptr;
     double *draw_bsum = nullptr;  // device-side draw: partial sums of exp(tau * improvement)
 
+    // Monte-Carlo Cheeger estimate (dcr_cheeger.hip), grown on demand: membership words [n][W], counts [3][64 W], ratios [64 W]
+    uint64_t *chg_members = nullptr;
+    int64_t chg_members_cap = 0;
+    unsigned long long *chg_counts = nullptr;
+    int64_t chg_counts_cap = 0;
+    double *chg_values = nullptr;
+    int64_t chg_values_cap = 0;
+
     dcr::DevResult *dres = nullptr;  // device
     dcr::DevResult *hres = nullptr;  // pinned host
 

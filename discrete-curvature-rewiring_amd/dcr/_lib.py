@@ -56,6 +56,10 @@ SIGNATURES = {
     'dcr_bfc_algorithmic_bytes': (ctypes.c_int, [_vp, _f64p]),
     'dcr_bfc_algorithmic_bytes_one_sided': (ctypes.c_int, [_vp, _f64p]),
     'dcr_pass_engine': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    'dcr_cheeger_counts': (ctypes.c_int, [_vp, _vp, _i64, _i64p]),
+    'dcr_cheeger_philox_counts': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, _i64p]),
+    'dcr_cheeger_philox_values': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, ctypes.c_int, _f64p]),
+    'dcr_cheeger_philox_members': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, _vp]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -28,6 +28,35 @@ def _as_numpy_edge_index(edge_index):
     return ei
 
 
+CHEEGER_DEFINITIONS = {'reference': 0, 'conductance': 1}
+
+
+def pack_members(members, num_nodes):
+    """(uint64 words [n, W], number of subsets) from bool ``[B, n]`` or from the packed words themselves."""
+    m = np.asarray(members)
+    if m.ndim != 2:
+        raise ValueError('members must be bool [B, n] or uint64 [n, W]')
+    if m.dtype == np.uint64:
+        if m.shape[0] != num_nodes or m.shape[1] < 1:
+            raise ValueError('packed members must have shape [num_nodes, W] with W >= 1')
+        return np.ascontiguousarray(m), 64 * m.shape[1]
+    if m.dtype != np.bool_:
+        raise ValueError('members must be bool [B, n] or uint64 [n, W]')
+    B = m.shape[0]
+    if B < 1 or m.shape[1] != num_nodes:
+        raise ValueError('bool members must have shape [B, num_nodes] with B >= 1')
+    W = (B + 63) // 64
+    bits = np.zeros((num_nodes, 64 * W), dtype=np.uint8)
+    bits[:, :B] = m.T
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder='little')).view('<u8').reshape(num_nodes, W), B
+
+
+def _with_outside(counts3, num_edges):
+    out = np.empty((counts3.shape[0], 4), dtype=np.int64)
+    out[:, :3] = counts3
+    out[:, 3] = num_edges - counts3.sum(axis=1)
+    return out
+
 
 class _HostBlock:
     """Carrier of an ``__array_interface__`` for a library-owned host buffer."""
@@ -253,6 +282,38 @@ class DcrGraph:
                                                    ctypes.byref(u), ctypes.byref(v), ctypes.byref(val)))
         rem = None if removed[0] < 0 else (removed[0], removed[1])
         return status.value, n_cand.value, (added[0], added[1]), rem, (u.value, v.value, val.value)
+
+    # ---- Monte-Carlo Cheeger estimate (experiment/compute_cheeger.py) ------------------------------------------------
+    def cheeger_counts(self, members):
+        """Edge counts of many node subsets at once, read-only on the graph.  ``members``: bool ``[B, n]`` (row = subset) or
+        the packed words themselves, uint64 ``[n, W]`` (bit k of word w of node v = v is in subset 64 w + k; B = 64 W).
+        Returns int64 ``[B, 4]`` = (in, lo, hi, out) over the undirected edges a < b: both ends inside, only a, only b,
+        neither (compute_cheeger.py:32-45: boundary_size = lo, vol(S) = 2 in, vol(G - S) = 2 out)."""
+        words, B = pack_members(members, self.num_nodes)
+        out = np.empty((64 * words.shape[1], 3), dtype=np.int64)
+        check(lib().dcr_cheeger_counts(self._h, words.ctypes.data, words.shape[1], out.ctypes.data_as(_lib._i64p)))
+        return _with_outside(out[:B], self.number_of_edges())
+
+    def cheeger_philox_counts(self, seed, first, count):
+        """The same for subsets ``first .. first + count - 1`` of the Philox family of ``seed`` (include/dcr.h), drawn on
+        the device; ``first`` a multiple of 64."""
+        out = np.empty((max(int(count), 0), 3), dtype=np.int64)
+        check(lib().dcr_cheeger_philox_counts(self._h, int(seed), int(first), int(count), out.ctypes.data_as(_lib._i64p)))
+        return _with_outside(out, self.number_of_edges())
+
+    def cheeger_philox_values(self, seed, first, count, definition='reference'):
+        """Their ratios as float64 ``[count]``: ``'reference'`` lo / min(2 in, 2 out), ``'conductance'`` (lo + hi) /
+        min(2 in + lo + hi, 2 out + lo + hi); inf where the smaller volume is zero."""
+        out = np.empty(max(int(count), 0), dtype=np.float64)
+        check(lib().dcr_cheeger_philox_values(self._h, int(seed), int(first), int(count), CHEEGER_DEFINITIONS[definition],
+                                              out.ctypes.data_as(_lib._f64p)))
+        return out
+
+    def cheeger_philox_members(self, seed, first, words):
+        """The device-drawn membership words ``first / 64 .. first / 64 + words - 1`` as uint64 ``[n, words]``."""
+        out = np.empty((self.num_nodes, max(int(words), 0)), dtype=np.uint64)
+        check(lib().dcr_cheeger_philox_members(self._h, int(seed), int(first), int(words), out.ctypes.data))
+        return out
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

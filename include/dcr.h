@@ -159,6 +159,34 @@ int dcr_bfc_algorithmic_bytes(dcr_graph *g, double *out_bytes);
  * graph, so a pass has to read one side only; this is the byte count bench.py's roofline fraction is quoted on. */
 int dcr_bfc_algorithmic_bytes_one_sided(dcr_graph *g, double *out_bytes);
 
+/* ---- Monte-Carlo Cheeger estimate: experiment/compute_cheeger.py ------------------------------------------------------
+ * For a node subset S and every undirected edge a < b (G.edges of to_networkx(data, to_undirected=True), :55, yields each
+ * edge once in that orientation) the reference's cheeger_S (:40-45) is a function of three integers:
+ *     in = #{a in S, b in S}     lo = #{a in S, b not in S}     hi = #{a not in S, b in S}     out = E - in - lo - hi
+ * boundary_size (:32-37) = lo (only the edges whose SMALLER endpoint is inside), vol(G.subgraph(S)) (:27-29, :60) = 2 in,
+ * vol(G - S) (:42-44) = 2 out.  The calls below count many subsets in one sweep of the graph's rows (csrc/dcr_cheeger.hip).
+ * Subsets are packed 64 to a word: a membership matrix is node-major uint64 [num_nodes][W], bit k of word w of node v set
+ * iff v is a member of subset 64 w + k.  All of them are READ-ONLY on the graph (curvature buffer, incremental flags,
+ * edit journal, two-hop edge set and extremum caches untouched), run on the graph's stream and are synchronous on return.
+ * Bad arguments (null pointers, W <= 0, B <= 0, first not a non-negative multiple of 64) return DCR_EINVAL before any
+ * device call.
+ *   dcr_cheeger_counts           members: host [num_nodes][W]; out_counts: host int64 [64 W][3] = (in, lo, hi) per subset
+ *                                (the loop body of estimate_cheeger, :59-60, for 64 W draws of random_subset, :19-24)
+ *   dcr_cheeger_philox_counts    the same for subsets first .. first + B - 1 of the Philox family of `seed`, drawn on the
+ *                                device; out_counts: host int64 [B][3]
+ *   dcr_cheeger_philox_values    their ratios, out_values: host double [B].  definition 0: cheeger_S as the reference
+ *                                computes it (:40-45), lo / min(2 in, 2 out); 1: conductance, (lo + hi) / min(2 in + lo + hi,
+ *                                2 out + lo + hi).  +inf where the smaller volume is 0.  One IEEE float64 division of two
+ *                                exactly represented integers.
+ *   dcr_cheeger_philox_members   the membership words themselves, words first / 64 .. first / 64 + W - 1: host [num_nodes][W]
+ * Philox family: with r[0..3] = Philox-4x32-10 of counter words {v low, v high, (j >> 7) low, (j >> 7) high} under key
+ * {seed low, seed high} (the generator of csrc/dcr_philox.h), node v is a member of subset j iff bit (j & 31) of
+ * r[(j >> 5) & 3] is set.  Membership probability 1/2; a subset depends on (seed, j) only, not on first or B. */
+int dcr_cheeger_counts(dcr_graph *g, const uint64_t *members, int64_t W, int64_t *out_counts);
+int dcr_cheeger_philox_counts(dcr_graph *g, uint64_t seed, int64_t first, int64_t B, int64_t *out_counts);
+int dcr_cheeger_philox_values(dcr_graph *g, uint64_t seed, int64_t first, int64_t B, int definition, double *out_values);
+int dcr_cheeger_philox_members(dcr_graph *g, uint64_t seed, int64_t first, int64_t W, uint64_t *out_members);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
