@@ -284,11 +284,7 @@ __device__ inline Ingredients edge_ingredients(const View &g, int u, int v, unsi
         {
             constexpr int NG = TEAM / 4;
             const int gid = tid >> 2, gl = tid & 3, gsh = (lane >> 2) << 2;
-#ifdef DCR_ABLATE_SHORT
-            for (int b0 = 0; b0 < 0; b0 += NG) {
-#else
             for (int b0 = 0; b0 < nshort; b0 += NG) {
-#endif
                 const int i = b0 + gid;
                 const int2 rk = i < nshort ? desc[i] : make_int2(0, 0);
                 const int hi = rk.x + rk.y;
@@ -315,11 +311,7 @@ __device__ inline Ingredients edge_ingredients(const View &g, int u, int v, unsi
             }
         }
         // (c) long rows: a whole wave per row, 1 KiB per wave-instruction, next piece in flight while probing
-#ifdef DCR_ABLATE_LONG
-        for (int i = wid; i < 0; i += NW) {
-#else
         for (int i = wid; i < nlong; i += NW) {
-#endif
             const int2 rl = desc[DESC_CAP - 1 - i];
             const int hi = rl.x + rl.y;
             int al = (rl.x & ~3) + 4 * lane;
@@ -695,7 +687,7 @@ template <int MODE>
 static int run_pass(dcr_graph *g, int curv_type, double *bytes_total, bool incremental = false, bool nc_rest = false) {
     DCR_TRY(ensure_work(g));
     View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
-            (int32_t)g->n, nc_rest ? 1 : 0, nullptr};
+            (int32_t)g->n, nc_rest ? 1 : 0};
     WorkLists wl;
     for (int b = 0; b < NBINS; ++b) wl.w[b] = g->work[b];
     // can an edge exceed the largest table at all?  (max_deg_bound is an upper bound of every degree)
@@ -716,23 +708,16 @@ static int run_pass(dcr_graph *g, int curv_type, double *bytes_total, bool incre
                        g->curv, wl, g->dres, bytes_total);
     if (curv_type != DCR_CURV_1D || MODE == MODE_BYTES) {
         // the bins are independent: fork them onto side streams so their tails overlap; heaviest first
-        static const bool serial = getenv("DCR_SERIAL_BINS") != nullptr;  // debugging aid: one stream
-        hipStream_t s0 = g->stream, s1 = g->stream, s2 = g->stream, s3 = g->stream;
-        if (!serial) {
-            DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
-            for (int b = 0; b < NBINS - 1; ++b) DCR_HIP(hipStreamWaitEvent(g->side[b], g->ev_fork, 0));
-            s0 = g->side[0]; s1 = g->side[1]; s2 = g->side[2]; s3 = g->side[3];
-        }
+        DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
+        for (int b = 0; b < NBINS - 1; ++b) DCR_HIP(hipStreamWaitEvent(g->side[b], g->ev_fork, 0));
         launch_bin<3, MODE>(g, vw, curv_type, bytes_total, num_cu, g->stream);
-        launch_bin<4, MODE>(g, vw, curv_type, bytes_total, num_cu, s0);
-        launch_bin<2, MODE>(g, vw, curv_type, bytes_total, num_cu, s1);
-        launch_bin<1, MODE>(g, vw, curv_type, bytes_total, num_cu, s2);
-        launch_bin<0, MODE>(g, vw, curv_type, bytes_total, num_cu, s3);
-        if (!serial) {
-            for (int b = 0; b < NBINS - 1; ++b) {
-                DCR_HIP(hipEventRecord(g->ev_join[b], g->side[b]));
-                DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[b], 0));
-            }
+        launch_bin<4, MODE>(g, vw, curv_type, bytes_total, num_cu, g->side[0]);
+        launch_bin<2, MODE>(g, vw, curv_type, bytes_total, num_cu, g->side[1]);
+        launch_bin<1, MODE>(g, vw, curv_type, bytes_total, num_cu, g->side[2]);
+        launch_bin<0, MODE>(g, vw, curv_type, bytes_total, num_cu, g->side[3]);
+        for (int b = 0; b < NBINS - 1; ++b) {
+            DCR_HIP(hipEventRecord(g->ev_join[b], g->side[b]));
+            DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[b], 0));
         }
     }
     DCR_HIP(hipGetLastError());
@@ -813,9 +798,8 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     bool dirty_clear_pending = false;   // the node flags still to be zeroed: by the sweep for the extrema when one follows
     auto argmin_after_pass = [&]() -> int {
         // (a pass of the node-centric kernels — incremental ones above all — leaves no partial extrema: ONE sweep takes both,
-        //  the stale arg-max of the removal step then is a 5 us reduction as behind the two-hop pass; DCR_ARGEXT_BOTH=0: two sweeps)
-        static const bool both = !(getenv("DCR_ARGEXT_BOTH") && atoi(getenv("DCR_ARGEXT_BOTH")) == 0);
-        if (!g->ext_part_valid && both) DCR_TRY(launch_argext_both(g, nullptr, dirty_clear_pending));
+        //  the stale arg-max of the removal step then is a 5 us reduction as behind the two-hop pass)
+        if (!g->ext_part_valid) DCR_TRY(launch_argext_both(g, nullptr, dirty_clear_pending));
         else if (dirty_clear_pending) clear_dirty_flags(g);
         dirty_clear_pending = false;
         return g->ext_part_valid ? launch_argext_from_parts(g, 0) : launch_argext(g, 0, -1, -1);
@@ -909,7 +893,7 @@ int dcr_bfc_ingredients(dcr_graph *g, int32_t u, int32_t v, int64_t out6[6]) {
     const int keys = du + dv + 2;
     int64_t *d_out = nullptr;
     DCR_TRY(dev_alloc(&d_out, 6));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0, nullptr};
+    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
     if (keys <= bin_max_keys(0)) launch_single<0>(g, vw, u, v, d_out);
     else if (keys <= bin_max_keys(1)) launch_single<1>(g, vw, u, v, d_out);
     else if (keys <= bin_max_keys(2)) launch_single<2>(g, vw, u, v, d_out);

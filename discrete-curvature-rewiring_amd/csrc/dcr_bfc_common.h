@@ -18,7 +18,6 @@ struct View {
     const uint8_t *dirty;  // incremental pass: only edges with a flagged endpoint are recomputed (nullptr: all)
     int32_t n;             // number of nodes
     int32_t nc_handles;    // 1: the node-centric kernels take every edge within their degree limits
-    long long *trace;      // diagnostic build aid (DCR_NC_TRACE): per wave {first, last} s_memrealtime stamps, else nullptr
 };
 
 __device__ inline bool row_ok(const View &g, const int2 rk, int code, int a, int b) {

@@ -353,7 +353,7 @@ int process_hub_edges(dcr_graph *g, int curv_type, bool incremental) {
     DCR_HIP(hipMemcpyAsync(hubs.data(), g->hub_list, sizeof(int32_t) * hubs.size(), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
-            (int32_t)g->n, 1, nullptr};
+            (int32_t)g->n, 1};
     for (int q = 0; q < count; ++q) {
         const int h = hubs[(size_t)q * 2], dh = hubs[(size_t)q * 2 + 1];
         if (h < 0 || h >= g->n || dh <= NC_MAXD) DCR_FAIL(DCR_ESTATE, "corrupt hub record");

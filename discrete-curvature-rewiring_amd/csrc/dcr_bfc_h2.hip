@@ -120,9 +120,6 @@ __device__ inline int h2_part(unsigned key, int nparts) {
 // ran at 85 % load; with two bits a singleton needs both taken: 1-2 %.  Both bits go in ONE atomic: two atomics were tried
 // first and were WRONG — two lanes holding the same key in one instruction are served in an order of the hardware's choosing,
 // not necessarily the same for the second atomic, and then neither lane sees both bits set.)
-#ifndef H2_TWO_HASH
-#define H2_TWO_HASH 1
-#endif
 __device__ inline unsigned h2_mul24c(unsigned key) {  // a third multiplier: independent of the bitmaps' first hash and of the tables'
     unsigned prod;
     asm("v_mul_u32_u24 %0, 0xb55a4f, %1" : "=v"(prod) : "v"(key));
@@ -131,7 +128,7 @@ __device__ inline unsigned h2_mul24c(unsigned key) {  // a third multiplier: ind
 // the entry's bits inside word (bit index >> 5) of B1
 __device__ inline unsigned h2_word_mask(unsigned key, unsigned b) {
     unsigned m = 1u << (b & 31u);
-    if (H2_TWO_HASH) m |= 1u << ((h2_mul24c(key) >> 19) & 31u);
+    m |= 1u << ((h2_mul24c(key) >> 19) & 31u);
     return m;
 }
 template <int L1>
@@ -362,25 +359,6 @@ __device__ inline void h2_retry_push(const H2Retry rt, int u, int d, int cls) { 
     for (int j = 0; j < nparts; ++j) rt.units[first + j] = make_int4(u, (nparts << 16) | j, 0, 0);
 }
 
-#ifdef H2_UNIT_TIMES  // diagnostic build (tools/build_variant.sh ut -DH2_UNIT_TIMES): start and duration of every block-class unit
-constexpr unsigned H2_UT_CAP = 16384;
-__device__ int4 h2_ut[2 * H2_UT_CAP];  // {node, class | partitions << 16 | partition, s_memtime ticks, start tick / 16}, {ticks: clear + seed, sweep A, sweep B, third step}
-__device__ int4 h2_ut2[H2_UT_CAP];     // wave 0 of the unit: {ticks in the second sweep's drains, drains, items drained, -}
-__device__ unsigned h2_ut_n;
-__device__ long long h2_ut_t0;
-__global__ void k_h2_ut_mark() { h2_ut_t0 = (long long)__builtin_amdgcn_s_memtime(); h2_ut_n = 0u; }
-#endif
-#ifdef H2_PROF  // diagnostic build (tools/build_variant.sh prof -DH2_PROF): wave-cycles per section of the wave classes
-__device__ unsigned long long h2_prof[32];
-#define H2_STAMP(i)                                                      \
-    {                                                                    \
-        const long long now_ = (long long)__builtin_amdgcn_s_memtime();  \
-        if ((threadIdx.x & 63) == 0) s->prof[i] += (unsigned long long)(now_ - t_prof);              \
-        t_prof = now_;                                                   \
-    }
-#else
-#define H2_STAMP(i) {}
-#endif
 // =====================================================================================================================
 // wave classes: a node of at most 64 neighbours, by one wave
 // =====================================================================================================================
@@ -408,9 +386,6 @@ struct __attribute__((aligned(16))) H2Small {
             unsigned char clr[CLCAP];      // ... and row
         } b;
     };
-#ifdef H2_PROF
-    unsigned long long prof[8];    // per wave, flushed when the kernel ends
-#endif
 };
 
 template <int EXS>
@@ -453,9 +428,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
                                 const H2Retry rt, Mid mid) {
     const int lane = threadIdx.x & 63;
     const unsigned long long below = (1ull << lane) - 1ull;
-#ifdef H2_PROF
-    long long t_prof = (long long)__builtin_amdgcn_s_memtime();
-#endif
     {   // clear: both bitmaps to zero (the second phase's arrays are set up between the sweeps)
         uint4 *z = reinterpret_cast<uint4 *>(s->b2);
         constexpr int NZ = ((1 << L1) / 32 + (1 << (L1 - 2)) / 32) / 4;  // b2, then b1 directly behind it
@@ -464,7 +436,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         for (int i = lane; i < NZ; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
     }
     h2_wave_sync();
-    H2_STAMP(0)
     // the members of N(u): seeded into both bitmaps (into the exact table between the sweeps)
     bool full = false;
     if (lane >= ru.y || k < 0 || k >= g.n || k == u) {
@@ -481,7 +452,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
     s->a.poff[lane] = poff_lane;
     if (lane == 0) s->a.poff[64] = P;
     h2_wave_sync();
-    H2_STAMP(1)
     if (P > 64 * NP) full = true;  // (cannot happen: the class bounds the weight; such a node would be redone elsewhere)
     // every piece of the node is requested at once and kept: meta = valid-entry mask | row << 4 | first slot of the piece << 12
     int4 w[NP];
@@ -501,7 +471,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
             meta[q] = (unsigned long long)h2_piece_mask(a, d.x, d.x + d.y) | ((unsigned long long)r << 4) | ((unsigned long long)(unsigned)a << 12);
         }
     }
-    H2_STAMP(2)
     // sweep A
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -530,7 +499,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         else s->b.exlo[slot] = (unsigned)lane;
     }
     h2_wave_sync();
-    H2_STAMP(3)
     // sweep B: entries whose B2 bit is set are queued and settled against the exact table 64 at a time
     int qn = 0, cln = 0;  // uniform
     auto drain = [&]() {
@@ -610,7 +578,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         if (!stop) break;
     }
     h2_wave_sync();
-    H2_STAMP(4)
     if (__ballot(full) != 0ull) {  // a table or the list filled up: nothing is published, the node is redone elsewhere
         if (lane == 0) h2_retry_push(rt, u, ru.y, L1 == 14 ? 0 : L1 == 15 ? 1 : 2);
         h2_wave_sync();
@@ -637,7 +604,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         }
     }
     h2_wave_sync();  // the arrays are rewritten by the next node
-    H2_STAMP(5)
 }
 
 // Units are taken grid-stride from a list laid out heaviest first: every wave gets a similar mix.  A node is a chain of
@@ -669,9 +635,6 @@ __global__ void __launch_bounds__(64 * WPB, (L1 == 14 ? H2_OCC0 : L1 == 15 ? H2_
     }
     const int64_t stride = (int64_t)gridDim.x * WPB;
     int64_t it = (int64_t)blockIdx.x * WPB + wid;
-#ifdef H2_PROF
-    if (lane < 8) sm[wid].prof[lane] = 0ull;
-#endif
     const int4 none = make_int4(-1, 0, 0, 0);
     auto unit_ok = [&](const int4 un) {
         return un.x >= 0 && un.x < g.n && un.w > 0 && un.w <= H2_SMALL_DEG && un.z >= 0 && (int64_t)un.z + un.w <= g.cap_total;
@@ -700,10 +663,6 @@ __global__ void __launch_bounds__(64 * WPB, (L1 == 14 ? H2_OCC0 : L1 == 15 ? H2_
         un1 = un2;
         k1 = (unit_ok(un1) && lane < un1.w) ? g.col[un1.z + lane] : -1;
     }
-#ifdef H2_PROF
-    h2_wave_sync();
-    if (lane < 8) atomicAdd(&h2_prof[lane], sm[wid].prof[lane]);
-#endif
 }
 
 // =====================================================================================================================
@@ -770,13 +729,6 @@ struct H2Scratch {
     unsigned char plr[H2_PLCAP];  // ... and the row each was met in
     int pln;                      // how many (counting past the capacity)
     unsigned char trank[64];      // rank of each row of the batch among the rows present (its task is tbase + rank)
-#ifdef H2_UNIT_TIMES
-    long long ut_drain;           // ticks this wave spent in the second sweep's drains (diagnostic)
-    int ut_ndrain, ut_nitems;
-#endif
-#ifdef H2_PROF
-    unsigned long long prof[16];
-#endif
 };
 
 // the LDS arrays of a unit
@@ -785,15 +737,7 @@ struct H2Tab {
     unsigned *key;  // [EXS] 4-slot buckets
     unsigned *cnt;  // [EXS / 2] their state, 16 bits each
     int *full;      // set when the table fills up
-#ifdef H2_UNIT_TIMES
-    long long *ut;  // [4] phase boundaries of the current unit (thread 0)
-#endif
 };
-#ifdef H2_UNIT_TIMES
-#define H2_UT_PHASE(i) { if (threadIdx.x == 0) t.ut[i] = (long long)__builtin_amdgcn_s_memtime(); }
-#else
-#define H2_UT_PHASE(i) {}
-#endif
 
 // M_u(w) and whether w is a member of N(u); {1, false} for a key this unit keeps no exact state for
 template <int L1, int EXS>
@@ -1122,10 +1066,6 @@ __device__ inline void h2_drain(const H2Tab t, H2Scratch *sc, int &n, const H2Ta
                                 int nparts) {
     const int lane = threadIdx.x & 63;
     const unsigned long long below = (1ull << lane) - 1ull;
-#ifdef H2_UNIT_TIMES
-    const long long ut_d0 = (long long)__builtin_amdgcn_s_memtime();
-    if (PHASE == 1 && lane == 0) { sc->ut_ndrain += 1; sc->ut_nitems += n; }
-#endif
     h2_wave_sync();
     int pln = PHASE == 2 ? sc->pln : 0;  // uniform
     for (int base = 0; base < n; base += 64) {
@@ -1165,9 +1105,6 @@ __device__ inline void h2_drain(const H2Tab t, H2Scratch *sc, int &n, const H2Ta
     }
     if (PHASE == 2 && lane == 0) sc->pln = pln;
     h2_wave_sync();
-#ifdef H2_UNIT_TIMES
-    if (PHASE == 1 && lane == 0) sc->ut_drain += (long long)__builtin_amdgcn_s_memtime() - ut_d0;
-#endif
     n = 0;
 }
 
@@ -1228,9 +1165,6 @@ __device__ inline void h2_batch_end(const View &g, const H2Tasks tk, H2Alloc &al
     // are in the pool already (listed by the drain); its partners go there now and its task says where they are:
     // k_h2_triangles publishes its counts, here it contributes none.  The tasks of all other rows are void.
     bool listed = tbase >= 0 && k >= 0 && T > 0 && pos > 0 && rev >= 0 && rev < g.cap_total;
-#ifdef H2_NO_STEPC  // timing-only build (results wrong)
-    listed = false;
-#endif
     int ep;
     const int Pn = h2_prefix(listed ? T : 0, ep);
     int p0 = 0;
@@ -1313,10 +1247,6 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
     int qn = 0;  // queued items (uniform)
     int lcur = 0;  // third step from the list: next item (uniform)
     if (PHASE == 0 && ru.y > 64 * NW * H2_REV_BATCHES) ls.over = true;  // more batches than the list's row array holds
-#ifdef H2_PROF
-    long long t_prof = (long long)__builtin_amdgcn_s_memtime();
-    H2Scratch *s = sc;
-#endif
     for (int base = 0; base < ru.y; base += 64 * NW) {
         const int i = base + lane * NW + wid;
         int k = k0;
@@ -1344,13 +1274,10 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
             // the third step from the second sweep's list: no row is streamed, no entry tested or looked up again
             h2_batch_begin(tk, al, sc, k, tbase, trow, ls.revs[bidx * 64 + lane]);
             h2_wave_sync();
-            H2_STAMP(8)
             const int lfrom = lcur;
             h2_settle_items<L1, EXS>(t, sc, ls, lcur, bidx, tk, al, tbase);
-            H2_STAMP(9)
             h2_batch_end<L1, EXS, PARTS>(g, tk, al, u, ru, i, k, rk, tbase, trow, part, t, sc, rec, ls.items, lfrom, lcur);
             h2_wave_sync();  // the scratch is rewritten by the next batch
-            H2_STAMP(11)
             continue;
         }
         if (PHASE == 0 && !ls.over) ls.revs[bidx * 64 + lane] = -1;
@@ -1359,7 +1286,6 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
         if (lane == 0) sc->poff[64] = P;
         if (PHASE == 2) h2_batch_begin(tk, al, sc, k, tbase, trow);
         h2_wave_sync();
-        if (PHASE == 2) H2_STAMP(8)
         const bool listing = PHASE == 1 && !ls.over;  // uniform
         auto flags = [&](const int4 w, unsigned vm, int r, int a) -> unsigned {
             const unsigned kk[4] = {(unsigned)w.x, (unsigned)w.y, (unsigned)w.z, (unsigned)w.w};
@@ -1388,14 +1314,11 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
                                  if (PHASE == 1) sc->qb[idx] = (unsigned char)bidx;
                              },
                              [&]() { h2_drain<L1, EXS, PHASE, PARTS>(t, sc, qn, tk, al, tbase, ls, part, nparts); });
-        if (PHASE == 2) H2_STAMP(9)
         if (PHASE == 2) {
             h2_drain<L1, EXS, PHASE, PARTS>(t, sc, qn, tk, al, tbase, ls, part, nparts);  // the row totals are read next
-            H2_STAMP(10)
             h2_batch_end<L1, EXS, PARTS>(g, tk, al, u, ru, i, k, rk, tbase, trow, part, t, sc, rec);
         }
         h2_wave_sync();  // the scratch is rewritten by the next batch
-        if (PHASE == 2) H2_STAMP(11)
     }
     if (qn > 0) h2_drain<L1, EXS, PHASE, PARTS>(t, sc, qn, tk, al, -1, ls, part, nparts);  // (after the loop: a wave's last batches may be empty; PHASE 1 only)
 }
@@ -1412,10 +1335,6 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
     constexpr int NT = 64 * NW, NP = H2_NPB;
     const unsigned long long below = (1ull << lane) - 1ull;
     if (ru.y > 64 * NW) return false;  // uniform
-#ifdef H2_PROF
-    long long t_prof = (long long)__builtin_amdgcn_s_memtime();
-    H2Scratch *s = sc;
-#endif
     const int i = lane * NW + wid;
     int k = -1;
     int2 rk = make_int2(0, 0);
@@ -1466,8 +1385,6 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
         }
     }
     __syncthreads();  // the tables are cleared
-    H2_STAMP(0 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(0)
     if (k >= 0) {     // the members of N(u): flagged table entries (in every partition's tables)
         const int sl = h2_insert<EXS>(t.key, (unsigned)k);
         if (sl < 0) *t.full = 1;
@@ -1490,8 +1407,6 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
         h2_mark4<L1>(t.b1, t.b2, kk, valid);
     }
     __syncthreads();
-    H2_STAMP(1 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(1)
     // Sweep B: flagged entries are queued, the drain has one call site.  It lists its exact-path entries (slot and row) and
     // where u sits in each row; the third step is then one pass over that list (h2_settle_items) — unless the list overflowed:
     // that wave streams its rows for the third sweep (h2_stream, the path of the units that do not fit the registers).
@@ -1542,8 +1457,6 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
         }
     }
     __syncthreads();
-    H2_STAMP(2 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(2)
     ok = *t.full == 0;  // uniform
     if (ok) {
         if (!ls.over) {  // uniform over the wave
@@ -1551,12 +1464,9 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
             const int myrev = sc->rowRev[lane];
             h2_wave_sync();
             h2_batch_begin(tk, al, sc, k, tbase, trow, myrev);
-            H2_STAMP(12)
             h2_wave_sync();
             h2_settle_items<L1, EXS>(t, sc, ls, lcur, 0, tk, al, tbase);
-            H2_STAMP(13)
             h2_batch_end<L1, EXS, PARTS>(g, tk, al, u, ru, i, k, rk, tbase, trow, part, t, sc, rec, ls.items, 0, lcur);
-            H2_STAMP(15)
         } else {
             h2_stream<L1, EXS, NW, PARTS, 2>(g, tk, al, u, ru, part, nparts, t, sc, rec, k, rk, ls);
         }
@@ -1571,16 +1481,10 @@ __device__ inline bool h2_node(const View &g, const H2Tasks tk, H2Alloc &al, int
                                const H2Tab t, H2Scratch *sc, uint4 *rec, H2List &ls) {
     const int tid = (int)threadIdx.x;
     constexpr int NT = 64 * NW;
-#ifndef H2_NO_FAST
     if constexpr (!PARTS) {  // (with 16 waves per unit the registers it needs spill: measured slower for the split class)
         bool ok_fast = true;
         if (h2_node_fast<L1, EXS, NW, PARTS>(g, tk, al, u, ru, part, nparts, t, sc, rec, ok_fast, ls)) return ok_fast;
     }
-#endif
-#ifdef H2_PROF
-    long long t_prof = (long long)__builtin_amdgcn_s_memtime();
-    H2Scratch *s = sc;
-#endif
     // this lane's row of the first batch of every sweep (requested before the tables are cleared)
     int k0 = -1;
     int2 rk0 = make_int2(0, 0);
@@ -1617,20 +1521,13 @@ __device__ inline bool h2_node(const View &g, const H2Tasks tk, H2Alloc &al, int
         }
     }
     __syncthreads();
-    H2_STAMP(8 - 8 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(0)
     h2_stream<L1, EXS, NW, PARTS, 0>(g, tk, al, u, ru, part, nparts, t, sc, rec, k0, rk0, ls);
     __syncthreads();
-    H2_STAMP(1 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(1)
     h2_stream<L1, EXS, NW, PARTS, 1>(g, tk, al, u, ru, part, nparts, t, sc, rec, k0, rk0, ls);
     __syncthreads();
-    H2_STAMP(2 + (PARTS ? 4 : 0))
-    H2_UT_PHASE(2)
     const bool ok = *t.full == 0;  // uniform
     if (ok) h2_stream<L1, EXS, NW, PARTS, 2>(g, tk, al, u, ru, part, nparts, t, sc, rec, k0, rk0, ls);
     __syncthreads();  // the tables are rewritten by the next unit
-    H2_STAMP(3 + (PARTS ? 4 : 0))
     return ok;
 }
 
@@ -1651,16 +1548,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
         row_ok(g, make_int2(-1, total), 37, 0, 0);
         return;
     }
-#ifdef H2_UNIT_TIMES
-    __shared__ long long ut_sh[4];
-    const H2Tab t{bits, bits + (1 << L1) / 32, key, cnt, &full, ut_sh};
-#else
     const H2Tab t{bits, bits + (1 << L1) / 32, key, cnt, &full};
-#endif
     H2Alloc al;
-#ifdef H2_PROF
-    if ((threadIdx.x & 63) < 16) sc_all[wid].prof[threadIdx.x & 63] = 0ull;
-#endif
     for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {  // every value steering the barriers is uniform
         const int4 un = units[it];
         const int u = un.x;
@@ -1673,22 +1562,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
         }
         if (!ok) continue;
         H2List ls = h2_list_of(tk.lists, NW);  // (fresh per unit)
-#ifdef H2_UNIT_TIMES
-        const long long ut0 = (long long)__builtin_amdgcn_s_memtime();
-        if ((threadIdx.x & 63) == 0) { sc_all[wid].ut_drain = 0; sc_all[wid].ut_ndrain = 0; sc_all[wid].ut_nitems = 0; }
-#endif
         const bool unit_ok = h2_node<L1, EXS, NW, PARTS>(g, tk, al, u, ru, part, nparts, t, &sc_all[wid], rec, ls);
-#ifdef H2_UNIT_TIMES
-        if (threadIdx.x == 0 && !is_retry) {
-            const long long ut1 = (long long)__builtin_amdgcn_s_memtime();
-            const unsigned slot = atomicAdd(&h2_ut_n, 1u);
-            if (slot < H2_UT_CAP) {
-                h2_ut[2 * slot] = make_int4(u, (PARTS ? 0x40000000 : 0) | (nparts << 16) | part, (int)(ut1 - ut0), (int)((ut0 - h2_ut_t0) >> 4));
-                h2_ut[2 * slot + 1] = make_int4((int)(ut_sh[0] - ut0), (int)(ut_sh[1] - ut_sh[0]), (int)(ut_sh[2] - ut_sh[1]), (int)(ut1 - ut_sh[2]));
-                h2_ut2[slot] = make_int4((int)sc_all[0].ut_drain, sc_all[0].ut_ndrain, sc_all[0].ut_nitems, 0);
-            }
-        }
-#endif
         if (!unit_ok) {
             if (threadIdx.x == 0) {  // every partition of the node is redone (the retry starts from zeroed records)
                 if (is_retry) {
@@ -1702,10 +1576,6 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
     }
     h2_void_candidates(tk, al.c_cur, al.c_end);
     h2_void_tasks(tk, al.t_cur, al.t_end);
-#ifdef H2_PROF
-    h2_wave_sync();
-    if ((threadIdx.x & 63) < 16) atomicAdd(&h2_prof[8 + (threadIdx.x & 63)], sc_all[wid].prof[threadIdx.x & 63]);
-#endif
 }
 
 // how many of the partners pt[0..np) are adjacent to w: one probe of the edge set per pair, eight in flight, most of
@@ -1773,11 +1643,7 @@ __global__ void __launch_bounds__(256) k_h2_triangles(H2EdgeSet es, H2Tasks tk, 
             const bool skip = ts.z == H2_TASK_VOID || (!(ts.w & 0x80000000u) && ((unsigned)tk.weight[ts.w & 0x7FFFFFFFu] & 0x80000000u));
             if (!skip) {
                 slot = ts.x;
-#ifdef H2_NO_PROBE  // timing-only build (results wrong)
-                c = cd.y;
-#else
                 c = cd.y - h2_probe_partners(es, cd.x, tk.part + ts.y, (int)ts.z);
-#endif
             }
         }
         // the candidates of an edge are adjacent: one pair of atomics per run of equal record slots (segmented scan)
@@ -2104,9 +1970,8 @@ bool h2_can_take(const dcr_graph *g, int curv_type, bool incremental) {
     if (curv_type != DCR_CURV_BFC || incremental || g->max_deg_bound > H2_MAXDEG || g->cap_total >= (int64_t)1 << 30) return false;
     if (g->pass_impl == 3) return true;
     if (g->pass_impl != 0 || g->n < 3000) return false;
-    static const double max_share = getenv("DCR_H2_MAX_SHARE") ? atof(getenv("DCR_H2_MAX_SHARE")) : 0.045;
     const double n = (double)g->n, sd2 = g->sum_deg2, s = sd2 / n, share = s / n;
-    if (share > max_share) return false;
+    if (share > 0.045) return false;
     // (round 5: the fixed cost of a two-hop pass went from 0.19 to about 0.10 ms with the three-stream layout — re-fitted, kept a
     //  little above the measurements: on a 500 k-node graph of two edges per node the per-node cost is underestimated — and small
     //  graphs have a third candidate, a workgroup per edge: nc_edges_full_ms)
@@ -2151,27 +2016,9 @@ static int ensure_h2(dcr_graph *g) {
     DCR_TRY(dev_regrow(&g->h2_part, &g->h2_part_cap, 2 * std::max<int64_t>(g->cap_total + 65536, g->h2_want[2])));
     // the third step's per-wave lists: the split class (one workgroup of 16 waves per CU; the retry launch reuses its part)
     // and class M (three workgroups of 4 waves per CU)
-    static const bool use_lists = !(getenv("DCR_H2_LISTS") && atoi(getenv("DCR_H2_LISTS")) == 0);
-    if (use_lists) {
-        const int cus = g->num_cu > 0 ? g->num_cu : 256;
-        DCR_TRY(dev_regrow(&g->h2_lists, &g->h2_lists_cap, (int64_t)cus * (16 + 12) * H2_LIST_WORDS));
-    }
+    const int cus = g->num_cu > 0 ? g->num_cu : 256;
+    DCR_TRY(dev_regrow(&g->h2_lists, &g->h2_lists_cap, (int64_t)cus * (16 + 12) * H2_LIST_WORDS));
     return DCR_OK;
-}
-
-// Share of its full-chip grid each class kernel is launched with, in percent: {split class, class M, wave classes 2, 1, 0}.
-// All five are persistent kernels that deal their units out up front; each sized for the whole chip, the ones launched first
-// hold the LDS and the others' workgroups queue behind them (round 3 timeline: the fifth kernel started 0.7 ms late).
-// DCR_H2_SHARE="l,m,s2,s1,s0" overrides (tuning aid, read at every pass).
-static int h2_share(int idx, int64_t n_nodes) {
-    static const int small_graph[5] = {100, 100, 100, 100, 100};
-    static const int large_graph[5] = {100, 100, 100, 100, 100};
-    int v = (n_nodes >= 400000 ? large_graph : small_graph)[idx];
-    if (const char *e = getenv("DCR_H2_SHARE")) {
-        int a[5];
-        if (sscanf(e, "%d,%d,%d,%d,%d", &a[0], &a[1], &a[2], &a[3], &a[4]) == 5 && a[idx] > 0 && a[idx] <= 400) v = a[idx];
-    }
-    return v;
 }
 
 template <int C>
@@ -2191,11 +2038,7 @@ static void launch_h2_small(dcr_graph *g, const View &vw, const H2Retry &rt, hip
         }
         per_cu_res = nb < 1 ? 1 : nb;
     }
-    int per_cu = per_cu_res;
-    int64_t grid = (int64_t)g->num_cu * per_cu;
-    static const int64_t cap = getenv("DCR_H2_GRID") ? atoll(getenv("DCR_H2_GRID")) : 0;  // tuning aid: workgroups per CU
-    if (cap > 0) grid = cap * g->num_cu;
-    grid = grid * h2_share(4 - C, g->n) / 100;
+    int64_t grid = (int64_t)g->num_cu * per_cu_res;
     const int64_t units = g->h2_last_count[C] >= 0 ? (int64_t)g->h2_last_count[C] + g->h2_last_count[C] / 32 + 8 : g->n;
     if (grid > (units + H2_WPB - 1) / H2_WPB) grid = (units + H2_WPB - 1) / H2_WPB;  // small graphs: no idle workgroups
     if (grid < 1) grid = 1;
@@ -2206,72 +2049,13 @@ static void launch_h2_small(dcr_graph *g, const View &vw, const H2Retry &rt, hip
 template <int C, bool PARTS>
 static void launch_h2_block(dcr_graph *g, const View &vw, const H2Tasks &tk, const H2Retry &rt, const int4 *units,
                             const int32_t *count, int64_t cap, int64_t units_hint, int is_retry, hipStream_t st) {
+    // (at most the workgroups the list pool has places for: one of the split class, three of class M per CU)
     int64_t grid = units_hint;
-    int64_t most = (int64_t)g->num_cu * (C == 3 ? 3 : 1);
-    if (!is_retry) most = most * h2_share(C == 3 ? 1 : 0, g->n) / 100;
+    const int64_t most = (int64_t)g->num_cu * (C == 3 ? 3 : 1);
     if (grid > most) grid = most;
     if (grid < 1) grid = 1;
-    H2Tasks tkl = tk;
-    if (grid > (int64_t)g->num_cu * (C == 3 ? 3 : 1)) tkl.lists = nullptr;  // (more workgroups than the list pool has places for)
     hipLaunchKernelGGL((k_h2_block<h2_l1(C), h2_exs(C), h2_waves(C), PARTS>), dim3((unsigned)grid), dim3(64 * h2_waves(C)), 0,
-                       st, vw, tkl, units, count, cap, g->h2_rec, rt, is_retry);
-}
-
-#ifdef H2_UNIT_TIMES
-static void h2_print_unit_times(dcr_graph *g) {
-    (void)hipStreamSynchronize(g->stream);
-    (void)hipDeviceSynchronize();
-    static int4 h[2 * H2_UT_CAP];
-    unsigned n = 0;
-    (void)hipMemcpyFromSymbol(&n, HIP_SYMBOL(h2_ut_n), sizeof(n));
-    if (n > H2_UT_CAP) n = H2_UT_CAP;
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(h2_ut), sizeof(int4) * 2 * n);
-    static int4 h2[H2_UT_CAP];
-    (void)hipMemcpyFromSymbol(h2, HIP_SYMBOL(h2_ut2), sizeof(int4) * n);
-    std::vector<int2> ri(g->n);
-    std::vector<int32_t> wt(g->n);
-    (void)hipMemcpy(ri.data(), g->rowinfo, sizeof(int2) * g->n, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(wt.data(), g->h2_weight, sizeof(int32_t) * g->n, hipMemcpyDeviceToHost);
-    for (int cls = 0; cls < 2; ++cls) {
-        std::vector<unsigned> v;
-        double sum = 0, ph[4] = {0, 0, 0, 0};
-        long long first = -1, last = 0;
-        for (unsigned i = 0; i < n; ++i)
-            if (((h[2 * i].y >> 30) & 1) == cls) {
-                v.push_back(i);
-                sum += h[2 * i].z;
-                ph[0] += h[2 * i + 1].x; ph[1] += h[2 * i + 1].y; ph[2] += h[2 * i + 1].z; ph[3] += h[2 * i + 1].w;
-                const long long st = (long long)h[2 * i].w * 16, en = st + h[2 * i].z;
-                if (first < 0 || st < first) first = st;
-                if (en > last) last = en;
-            }
-        if (v.empty()) continue;
-        std::sort(v.begin(), v.end(), [&](unsigned a, unsigned b) { return h[2 * a].z > h[2 * b].z; });
-        fprintf(stderr, "[h2 units] class %s: %zu units; first start to last end %.0f kticks (= the kernel); sum of unit times %.0f kticks; phases (sum, kticks): clear + seed %.0f, "
-                "sweep A %.0f, sweep B %.0f, third step %.0f\n", cls ? "L (split)" : "M", v.size(), (last - first) / 1e3, sum / 1e3, ph[0] / 1e3, ph[1] / 1e3, ph[2] / 1e3, ph[3] / 1e3);
-        fprintf(stderr, "    unit time percentiles (kticks): 50%% %.1f  90%% %.1f  99%% %.1f  max %.1f\n", h[2 * v[v.size() / 2]].z / 1e3, h[2 * v[v.size() / 10]].z / 1e3,
-                h[2 * v[v.size() / 100]].z / 1e3, h[2 * v[0]].z / 1e3);
-        for (size_t i = 0; i < v.size() && i < 8; ++i) {
-            const int4 a = h[2 * v[i]], b = h[2 * v[i] + 1];
-            fprintf(stderr, "    node %6d deg %5d W %8d part %d/%d: %7.1f kticks (clear + seed %.1f, A %.1f, B %.1f, third %.1f); wave 0 in B: %d drains of %d items, %.1f kticks\n", a.x, ri[a.x].y,
-                    wt[a.x] & 0x7FFFFFFF, a.y & 0xFFFF, (a.y >> 16) & 0x3FFF, a.z / 1e3, b.x / 1e3, b.y / 1e3, b.z / 1e3, b.w / 1e3, h2[v[i]].y, h2[v[i]].z, h2[v[i]].x / 1e3);
-        }
-    }
-}
-#endif
-
-// DCR_H2_DEBUG: the counters of the pass just enqueued (synchronises)
-static int h2_debug_print(dcr_graph *g) {
-    DevResult h;
-    DCR_HIP(hipStreamSynchronize(g->stream));
-    DCR_HIP(hipMemcpy(&h, g->dres, sizeof(h), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[h2] units per class %d %d %d %d %d, retry units %d (stage %s), status %d, failed per class %d %d %d %d %d retry %d\n",
-            h.h2_count[0], h.h2_count[1], h.h2_count[2], h.h2_count[3], h.h2_count[4], h.h2_retry, g->h2_expect_retry ? "on" : "off", h.h2_status,
-            h.h2_failed[0], h.h2_failed[1], h.h2_failed[2], h.h2_failed[3], h.h2_failed[4], h.h2_failed[5]);
-    fprintf(stderr, "[h2] triangle step: split class + retry %d tasks, %d candidates, %d partners; class M %d, %d, %d (pool slots, chunk tails "
-            "included; pools of %lld %lld %lld each)\n", h.h2_ntask[0], h.h2_ncand[0], h.h2_npart[0], h.h2_ntask[1], h.h2_ncand[1], h.h2_npart[1],
-            (long long)g->h2_task_cap / 2, (long long)g->h2_cand_cap / 2, (long long)g->h2_part_cap / 2);
-    return DCR_OK;
+                       st, vw, tk, units, count, cap, g->h2_rec, rt, is_retry);
 }
 
 int launch_curvature_pass_h2(dcr_graph *g) {
@@ -2282,7 +2066,7 @@ int launch_curvature_pass_h2(dcr_graph *g) {
             g->num_cu = prop.multiProcessorCount;
     }
     DCR_TRY(ensure_h2(g));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0, nullptr};
+    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
     H2Lists L;
     for (int c = 0; c < H2_CLASSES; ++c) {
         L.units[c] = g->h2_units[c];
@@ -2292,7 +2076,7 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     const H2Retry rt{g->h2_retry, g->h2_retry_cap, g->h2_weight, g->dres};
     const int64_t tcap = g->h2_task_cap / 2, ccap = g->h2_cand_cap / 2, pcap = g->h2_part_cap / 2;
     DevResult *dr = g->dres;
-    unsigned *lists_L = g->h2_lists, *lists_M = g->h2_lists ? g->h2_lists + (int64_t)g->num_cu * 16 * H2_LIST_WORDS : nullptr;
+    unsigned *lists_L = g->h2_lists, *lists_M = g->h2_lists + (int64_t)g->num_cu * 16 * H2_LIST_WORDS;
     H2Tasks tk{g->h2_task, g->h2_cand, g->h2_part, tcap, ccap, pcap, &dr->h2_ntask[0], &dr->h2_ncand[0], &dr->h2_npart[0],
                &dr->h2_ncand_done[0], g->dres, g->h2_weight, 0u, lists_L};  // pool 0: the split class and the retry launch
     const H2Tasks tkM{g->h2_task + tcap, g->h2_cand + ccap, g->h2_part + pcap, tcap, ccap, pcap, &dr->h2_ntask[1], &dr->h2_ncand[1],
@@ -2305,7 +2089,6 @@ int launch_curvature_pass_h2(dcr_graph *g) {
                            g->n, reinterpret_cast<unsigned *>(g->dirty), whole ? g->n / 4 : (int64_t)0);
         g->h2_cleared_dirty = whole;
     }
-    static const bool serial = getenv("DCR_SERIAL_BINS") != nullptr;
     const int64_t sblocks = (g->cap_total + 255) / 256;
     const H2EdgeSet es{g->h2_eset, g->h2_eset_bits, g->h2_bloom, g->h2_bloom_bits};
     if (sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight);
@@ -2319,189 +2102,70 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     // records of split nodes are accumulated with atomics: start from zero
     hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4],
                        g->h2_rec);
-    // Round 5: a layout with FEWER streams (DCR_H2_LAYOUT="l,m,s2,s1,s0": the stream, 0 = main, 1-3 = side streams, each class
-    // kernel is launched on; kernels on one stream run one after the other).  Five persistent full-chip kernels on five streams
-    // do not run five abreast anyway (the runtime maps streams onto four hardware queues, and the split class's workgroups
-    // hold 125 KB of a CU's LDS), and every stream the closing kernel has to join costs a barrier packet of 10-15 us on the
-    // critical path (the 48-75 us hole in front of k_h2_final in the round-4 timelines).
-#ifdef H2_UNIT_TIMES
-    hipLaunchKernelGGL(k_h2_ut_mark, dim3(1), dim3(1), 0, g->stream);
-#endif
-    // Measured (profiles/r05_layouts.txt, interleaved rounds, pass ms): S100k five streams 1.020, "0,1,2,2,1" 0.962, "0,1,1,2,2"
-    // 0.962, "0,1,2,2,2" 0.984, "0,1,2,3,3" 0.983, "0,1,1,1,1" 1.094; S1M five streams 10.10, "0,1,2,2,1" 10.70 — the fixed
-    // costs do not matter there and five abreast packs the chip better.  Default: three streams below 400k nodes.
-    static const char *layout_env = getenv("DCR_H2_LAYOUT");
-    const bool layout_default = !layout_env && g->n < 400000;
-    if ((layout_default || (layout_env && strcmp(layout_env, "five") != 0)) && !serial) {
-        int lay[5] = {0, 1, 2, 2, 1};
-        int a[5];
-        if (layout_env && sscanf(layout_env, "%d,%d,%d,%d,%d", &a[0], &a[1], &a[2], &a[3], &a[4]) == 5)
-            for (int c = 0; c < 5; ++c) lay[c] = a[c] < 0 ? 0 : a[c] > 3 ? 3 : a[c];
-        hipStream_t pool[4] = {g->stream, g->side[1], g->low[0], g->low[1]};
-        hipEvent_t done[4] = {nullptr, g->ev_join[1], g->ev_join[2], g->ev_join[3]};
-        bool used[4] = {true, false, false, false};
-        DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
-        auto on = [&](int c) {
-            const int si = lay[c];
-            if (!used[si]) {
-                used[si] = true;
-                (void)hipStreamWaitEvent(pool[si], g->ev_fork, 0);   // (an error surfaces at hipGetLastError below)
-            }
-            return pool[si];
-        };
-        const int64_t hint4 = g->h2_last_count[4] >= 0 ? (int64_t)g->h2_last_count[4] + 8 : g->num_cu;
-        const int64_t hint3 = g->h2_last_count[3] >= 0 ? (int64_t)g->h2_last_count[3] + 8 : 3 * (int64_t)g->num_cu;
-        static const bool keep_eset2 = !(getenv("DCR_H2_ESET_KEEP") && atoi(getenv("DCR_H2_ESET_KEEP")) == 0);
-        const bool patch2 = keep_eset2 && g->h2_eset_valid && g->h2_eset_pending <= EDIT_LOG_CAP &&
-                            g->h2_eset_tombs + g->h2_eset_pending <= ((int64_t)1 << g->h2_eset_bits) / 16;
-        // the edge set first (probed by the triangle steps only): patched by one thread on the main stream ahead of the split
-        // class, or rebuilt on the aux stream beside everything
-        bool eset_on_aux = false;
-        if (patch2) {
-            if (g->h2_eset_pending > 0) {
-                hipLaunchKernelGGL(k_h2_eset_apply, dim3(1), dim3(64), 0, g->stream, es, g->dres, status);
-                g->h2_eset_tombs += g->h2_eset_pending;
-                DCR_HIP(hipEventRecord(g->ev_fork, g->stream));   // (the side streams start behind it: their triangle steps probe the set)
-            }
-        } else {
-            DCR_HIP(hipStreamWaitEvent(g->aux, g->ev_fork, 0));
-            DCR_HIP(hipMemsetAsync(g->h2_eset, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, g->aux));
-            DCR_HIP(hipMemsetAsync(g->h2_bloom, 0, sizeof(unsigned) * (((size_t)1 << g->h2_bloom_bits) / 32), g->aux));
-            if (sblocks > 0) hipLaunchKernelGGL(k_h2_eset_build, dim3((unsigned)sblocks), dim3(256), 0, g->aux, vw, es, status, g->dres);
-            g->h2_eset_tombs = 0;
-            DCR_HIP(hipEventRecord(g->ev_aux, g->aux));
-            eset_on_aux = true;
+    // The stream each class kernel is launched on ({split class, class M, wave classes 2, 1, 0}: an index into `pool`; kernels on
+    // one stream run one after the other).  The split class stays on the main stream, launched first: its workgroups need most
+    // of a CU's LDS and find no CU free once the other kernels are resident (measured: started 60 us late, finished last).
+    // Round 5: five persistent full-chip kernels on five streams do not run five abreast anyway (the runtime maps streams onto
+    // four hardware queues, and the split class's workgroups hold 125 KB of a CU's LDS), and every stream the closing kernel has
+    // to join costs a barrier packet of 10-15 us on the critical path (the 48-75 us hole in front of k_h2_final in the round-4
+    // timelines).  Measured (profiles/r05_layouts.txt, interleaved rounds, pass ms): S100k five streams 1.020, {0,1,2,2,1} 0.962,
+    // {0,1,1,2,2} 0.962, {0,1,2,2,2} 0.984, {0,1,2,3,3} 0.983, {0,1,1,1,1} 1.094; S1M five streams 10.10, {0,1,2,2,1} 10.70 —
+    // the fixed costs do not matter there and five abreast packs the chip better.
+    static const int three_streams[H2_CLASSES] = {0, 1, 2, 2, 1}, five_streams[H2_CLASSES] = {0, 1, 2, 3, 4};
+    const int *lay = g->n < 400000 ? three_streams : five_streams;
+    hipStream_t pool[5] = {g->stream, g->side[1], g->low[0], g->low[1], g->side[2]};
+    hipEvent_t done[5] = {nullptr, g->ev_join[1], g->ev_join[2], g->ev_join[3], g->ev_aux2};
+    bool used[5] = {true, false, false, false, false};
+    DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
+    auto on = [&](int c) {
+        const int si = lay[c];
+        if (!used[si]) {
+            used[si] = true;
+            (void)hipStreamWaitEvent(pool[si], g->ev_fork, 0);   // (an error surfaces at hipGetLastError below)
         }
-        g->h2_eset_valid = true;
-        g->h2_eset_pending = 0;
-        // launch order = the order of the classes in the layout string's streams: split class, M, then the wave classes
-        launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, on(0));
-        launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, on(1));
-        // each block class's triangle step right behind it on its own stream
-        if (eset_on_aux) DCR_HIP(hipStreamWaitEvent(pool[lay[0]], g->ev_aux, 0));
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
-        if (eset_on_aux && lay[1] != lay[0]) DCR_HIP(hipStreamWaitEvent(pool[lay[1]], g->ev_aux, 0));
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
-        launch_h2_small<2>(g, vw, rt, on(2));
-        launch_h2_small<1>(g, vw, rt, on(3));
-        launch_h2_small<0>(g, vw, rt, on(4));
-        for (int si = 1; si < 4; ++si)
-            if (used[si]) {
-                DCR_HIP(hipEventRecord(done[si], pool[si]));
-                DCR_HIP(hipStreamWaitEvent(g->stream, done[si], 0));
-            }
-        if (!g->ext_part) {
-            Ext *p = nullptr;
-            DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
-            g->ext_part = p;
-        }
-        int64_t fb = (sblocks + H2_FINAL_Q - 1) / H2_FINAL_Q;
-        if (fb > H2_FINAL_BLOCKS) fb = H2_FINAL_BLOCKS;
-        if (fb > EXT_PART_BLOCKS / 4) fb = EXT_PART_BLOCKS / 4;
-        if (fb < 1) fb = 1;
-        const bool retry2 = g->h2_expect_retry;
-        if (retry2) {
-            hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap,
-                               g->h2_rec);
-            tk.retry_flag = 0x80000000u;
-            launch_h2_block<4, true>(g, vw, tk, rt, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap, 64, 1, g->stream);
-            hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 2)), dim3(256), 0, g->stream, es, tk, g->h2_rec, status, 1);
-        }
-        hipLaunchKernelGGL(k_h2_final, dim3((unsigned)fb), dim3(256), 0, g->stream, vw, g->h2_rec, g->curv, status, (Ext *)g->ext_part,
-                           (Ext *)g->ext_part + EXT_PART_BLOCKS, &g->dres->h2_retry, retry2 ? 1 : 0);
-        g->ext_part_n = (int)fb * 4;
-        g->ext_part_valid = true;
-        DCR_HIP(hipGetLastError());
-#ifdef H2_UNIT_TIMES
-        h2_print_unit_times(g);
-#endif
-        if (getenv("DCR_H2_DEBUG")) DCR_TRY(h2_debug_print(g));
-        return DCR_OK;
-    }
-    // Streams: the block classes (long units; the triangle step waits for them only) on two high-priority streams, the
-    // wave classes on three low-priority ones, the edge set on a stream of its own, the triangle step on a fourth
-    // high-priority stream as soon as block classes and edge set are done — beside the wave classes, which list nothing.
-    hipStream_t sL = g->stream, sM = g->stream, sS2 = g->stream, sS1 = g->stream, sS0 = g->stream, sT = g->stream, sa = g->stream;
-    if (!serial) {
-        // (the split class stays on the main stream, launched first: its workgroups need most of a CU's LDS and find no
-        //  CU free once the other kernels are resident — measured: started 60 us late, finished last)
-        sM = g->side[1];
-        sT = g->side[3];
-        sS2 = g->low[0];
-        sS1 = g->low[1];
-        sS0 = g->side[2];
-        sa = g->aux;
-        DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
-    }
-    // (each stream's wait is enqueued right before its kernel: the GPU is through the preamble before the host is through
-    //  these calls, so every call ahead of a launch is time the chip waits)
-    const int64_t hint4 = g->h2_last_count[4] >= 0 ? (int64_t)g->h2_last_count[4] + 8 : g->num_cu;
-    const int64_t hint3 = g->h2_last_count[3] >= 0 ? (int64_t)g->h2_last_count[3] + 8 : 3 * (int64_t)g->num_cu;
-    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, sL);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(sM, g->ev_fork, 0));
-    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, sM);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(sS2, g->ev_fork, 0));
-    launch_h2_small<2>(g, vw, rt, sS2);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(sS1, g->ev_fork, 0));
-    launch_h2_small<1>(g, vw, rt, sS1);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(sS0, g->ev_fork, 0));
-    launch_h2_small<0>(g, vw, rt, sS0);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(sa, g->ev_fork, 0));
-    // the edge set (probed by k_h2_triangles only): kept from the last pass and patched with the journaled edits, or rebuilt
-    // (32 MB of fill and a million atomics beside the class kernels: 0.17 ms of chip time per pass on the bench graph)
-    static const bool keep_eset = !(getenv("DCR_H2_ESET_KEEP") && atoi(getenv("DCR_H2_ESET_KEEP")) == 0);
-    const bool patch = keep_eset && g->h2_eset_valid && g->h2_eset_pending <= EDIT_LOG_CAP &&
+        return pool[si];
+    };
+    // the edge set (probed by the triangle steps only): kept from the last pass and patched with the journaled edits by one
+    // thread on the main stream ahead of the class kernels, or rebuilt on the aux stream beside them (32 MB of fill and a
+    // million atomics: 0.17 ms of chip time per pass on the bench graph)
+    const bool patch = g->h2_eset_valid && g->h2_eset_pending <= EDIT_LOG_CAP &&
                        g->h2_eset_tombs + g->h2_eset_pending <= ((int64_t)1 << g->h2_eset_bits) / 16;
+    bool eset_on_aux = false;
     if (patch) {
         if (g->h2_eset_pending > 0) {
-            hipLaunchKernelGGL(k_h2_eset_apply, dim3(1), dim3(64), 0, sa, es, g->dres, status);
+            hipLaunchKernelGGL(k_h2_eset_apply, dim3(1), dim3(64), 0, g->stream, es, g->dres, status);
             g->h2_eset_tombs += g->h2_eset_pending;
+            DCR_HIP(hipEventRecord(g->ev_fork, g->stream));   // (the side streams start behind it: their triangle steps probe the set)
         }
     } else {
-        DCR_HIP(hipMemsetAsync(g->h2_eset, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, sa));
-        DCR_HIP(hipMemsetAsync(g->h2_bloom, 0, sizeof(unsigned) * (((size_t)1 << g->h2_bloom_bits) / 32), sa));
-        if (sblocks > 0) hipLaunchKernelGGL(k_h2_eset_build, dim3((unsigned)sblocks), dim3(256), 0, sa, vw, es, status, g->dres);
+        DCR_HIP(hipStreamWaitEvent(g->aux, g->ev_fork, 0));
+        DCR_HIP(hipMemsetAsync(g->h2_eset, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, g->aux));
+        DCR_HIP(hipMemsetAsync(g->h2_bloom, 0, sizeof(unsigned) * (((size_t)1 << g->h2_bloom_bits) / 32), g->aux));
+        if (sblocks > 0) hipLaunchKernelGGL(k_h2_eset_build, dim3((unsigned)sblocks), dim3(256), 0, g->aux, vw, es, status, g->dres);
         g->h2_eset_tombs = 0;
+        DCR_HIP(hipEventRecord(g->ev_aux, g->aux));
+        eset_on_aux = true;
     }
     g->h2_eset_valid = true;
     g->h2_eset_pending = 0;
-    // The tail.  Without a retry stage (the usual case) everything below runs on the MAIN stream, behind the split class that is
-    // already there: its candidates' triangle step, class M's when M is through, the closing kernel when the wave classes are —
-    // the critical path (split class -> triangle steps -> closing kernel) crosses no stream.  (Round 3 had the triangle steps on
-    // a stream of their own and the main stream joined five streams before the closing kernel: two hops of 15-30 us each.)
-    const bool retry_stage = g->h2_expect_retry;
-    if (!serial && !retry_stage) sT = g->stream;
-    if (!serial) {
-        DCR_HIP(hipEventRecord(g->ev_aux, sa));
-        DCR_HIP(hipEventRecord(g->ev_join[1], sM));
-        if (sT != sL) {
-            DCR_HIP(hipEventRecord(g->ev_join[0], sL));
-            DCR_HIP(hipStreamWaitEvent(sT, g->ev_join[0], 0));
+    const int64_t hint4 = g->h2_last_count[4] >= 0 ? (int64_t)g->h2_last_count[4] + 8 : g->num_cu;
+    const int64_t hint3 = g->h2_last_count[3] >= 0 ? (int64_t)g->h2_last_count[3] + 8 : 3 * (int64_t)g->num_cu;
+    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, on(0));
+    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, on(1));
+    // each block class's triangle step right behind it on its own stream (class M's behind the split class's: 292 us beside
+    // the other classes, 60 alone — it started 90 us after M's end and sat on the critical path)
+    if (eset_on_aux) DCR_HIP(hipStreamWaitEvent(pool[lay[0]], g->ev_aux, 0));
+    hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
+    if (eset_on_aux && lay[1] != lay[0]) DCR_HIP(hipStreamWaitEvent(pool[lay[1]], g->ev_aux, 0));
+    hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
+    launch_h2_small<2>(g, vw, rt, on(2));
+    launch_h2_small<1>(g, vw, rt, on(3));
+    launch_h2_small<0>(g, vw, rt, on(4));
+    for (int si = 1; si < 5; ++si)
+        if (used[si]) {
+            DCR_HIP(hipEventRecord(done[si], pool[si]));
+            DCR_HIP(hipStreamWaitEvent(g->stream, done[si], 0));
         }
-        DCR_HIP(hipStreamWaitEvent(sT, g->ev_aux, 0));
-    }
-    // the split class's candidates as soon as IT is done (beside class M and the wave classes), class M's when M is — on M's own
-    // stream: behind the split class's triangle step (292 us beside the other classes, 60 alone) it started 90 us after M's end
-    // and sat on the critical path (DCR_H2_TRI_OWN=0: the round-4 order)
-    static const bool tri_own = !(getenv("DCR_H2_TRI_OWN") && atoi(getenv("DCR_H2_TRI_OWN")) == 0);
-    hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, sT, es, tk, g->h2_rec, status, 0);
-    if (!serial && tri_own) {
-        DCR_HIP(hipStreamWaitEvent(sM, g->ev_aux, 0));
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, sM, es, tkM, g->h2_rec, status, 0);
-        DCR_HIP(hipEventRecord(g->ev_join[1], sM));
-        DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[1], 0));
-    } else {
-        if (!serial) DCR_HIP(hipStreamWaitEvent(sT, g->ev_join[1], 0));
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, sT, es, tkM, g->h2_rec, status, 0);
-    }
-    if (!serial) {
-        if (sT != g->stream) DCR_HIP(hipEventRecord(g->ev_join[3], sT));
-        DCR_HIP(hipEventRecord(g->ev_join[2], sS0));
-        DCR_HIP(hipEventRecord(g->ev_aux2, sS1));
-        DCR_HIP(hipEventRecord(g->ev_fork, sS2));
-        if (sT != g->stream) DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[3], 0));
-        for (hipEvent_t ev : {g->ev_join[2], g->ev_aux2, g->ev_fork}) DCR_HIP(hipStreamWaitEvent(g->stream, ev, 0));
-    }
     if (!g->ext_part) {
         Ext *p = nullptr;
         DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
@@ -2511,6 +2175,7 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     if (fblocks > H2_FINAL_BLOCKS) fblocks = H2_FINAL_BLOCKS;
     if (fblocks > EXT_PART_BLOCKS / 4) fblocks = EXT_PART_BLOCKS / 4;  // (a pair of partial extrema per WAVE)
     if (fblocks < 1) fblocks = 1;
+    const bool retry_stage = g->h2_expect_retry;
     if (retry_stage) {
         // nodes whose tables filled up in their class: zero their records, redo them with worst-case partitions
         hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap,
@@ -2524,29 +2189,6 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     g->ext_part_n = (int)fblocks * 4;
     g->ext_part_valid = true;  // (dropped again by the caller if the pass reports a failure, and by every edit)
     DCR_HIP(hipGetLastError());
-    static const bool debug = getenv("DCR_H2_DEBUG") != nullptr;
-#ifdef H2_UNIT_TIMES
-    h2_print_unit_times(g);
-#endif
-#ifdef H2_PROF
-    {
-        unsigned long long h[32];
-        DCR_HIP(hipStreamSynchronize(g->stream));
-        DCR_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(h2_prof), sizeof(h)));
-        fprintf(stderr, "[h2 prof] wave-Mcycles: clear %.1f; seed + prefix %.1f; piece rows + loads %.1f; sweep A (+ wait for the loads) %.1f; "
-                "sweep B + drains %.1f; step C + publish %.1f\n", h[0] / 1e6, h[1] / 1e6, h[2] / 1e6, h[3] / 1e6, h[4] / 1e6, h[5] / 1e6);
-        fprintf(stderr, "[h2 prof] block classes, wave-Mcycles: M: clear + seed %.1f; sweep A %.1f; sweep B %.1f; sweep C + listing %.1f | "
-                "L: clear + seed %.1f; sweep A %.1f; sweep B %.1f; sweep C + listing %.1f\n", h[8] / 1e6, h[9] / 1e6, h[10] / 1e6,
-                h[11] / 1e6, h[12] / 1e6, h[13] / 1e6, h[14] / 1e6, h[15] / 1e6);
-        fprintf(stderr, "[h2 prof] sweep C of both block classes: batch set-up %.1f; pieces + drains %.1f; last drain %.1f; batch end %.1f\n",
-                h[16] / 1e6, h[17] / 1e6, h[18] / 1e6, h[19] / 1e6);
-        fprintf(stderr, "[h2 prof] class M (register-resident path), third sweep: batch set-up %.1f; flags + queue + drains %.1f; batch end %.1f\n",
-                h[20] / 1e6, h[21] / 1e6, h[23] / 1e6);
-        unsigned long long z[32] = {0};
-        DCR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(h2_prof), z, sizeof(z)));
-    }
-#endif
-    if (debug) DCR_TRY(h2_debug_print(g));
     return DCR_OK;
 }
 

@@ -76,9 +76,6 @@ constexpr unsigned NC_EMPTY = 0xFFFFFFFDu;
 template <int SLOTS>
 __device__ inline unsigned hash_bucket(unsigned key) {
     constexpr int BITS = __builtin_ctz(SLOTS / 4);
-#ifdef DCR_HASH_MUL32
-    return (key * 0x9E3779B1u) >> (32 - BITS);
-#else
     // Fibonacci hashing in a 24-bit word: v_mul_u32_u24 is a full-rate instruction, the 32-bit v_mul_lo_u32 is
     // quarter rate and this runs once per streamed neighbour id.  Only the low 24 bits of the id are hashed (the
     // bucket stores the whole id, so ids that differ above bit 23 merely share a home bucket).
@@ -86,7 +83,6 @@ __device__ inline unsigned hash_bucket(unsigned key) {
     unsigned prod;
     asm("v_mul_u32_u24 %0, 0x9e3779, %1" : "=v"(prod) : "v"(key));
     return (prod >> (24 - BITS)) & ((1u << BITS) - 1);
-#endif
 }
 
 // position of key inside the bucket (0..3) or -1; go_on: not found and the bucket is full (its slots fill in order,
@@ -137,24 +133,6 @@ __device__ inline unsigned cnt_add(unsigned *cnt, int h) {
 // equality compares and a "bucket full" compare per id (nc_probe_flags).  Pieces are compared raw; ids outside the row,
 // slack included, are masked off afterwards.  What passes the test is queued for the full look-up (slot position, walk
 // to the next bucket, slot counter update), see NC_QCAP below.
-#ifdef NC_DIRTY_STATS  // diagnostic build (tools/build_variant.sh dstats -DNC_DIRTY_STATS): what an incremental pass's units hold
-__device__ unsigned long long nc_dstats[4 * 8];  // per class of table size: units, units with an edge to compute, such edges, their rows' entries
-#endif
-#ifdef NC_STATS  // diagnostic build (tools/build_variant.sh stats -DNC_STATS): how often the fast test fails
-__device__ unsigned long long nc_stats[8];
-#define NC_STATS_COUNT(look_any)                                                             \
-    {                                                                                        \
-        const unsigned long long act = __ballot(true), lk = __ballot(look_any);              \
-        if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) {                        \
-            atomicAdd(&nc_stats[0], 1ull);                                                   \
-            atomicAdd(&nc_stats[1], lk ? 1ull : 0ull);                                       \
-            atomicAdd(&nc_stats[2], (unsigned long long)__popcll(act));                      \
-            atomicAdd(&nc_stats[3], (unsigned long long)__popcll(lk));                       \
-        }                                                                                    \
-    }
-#else
-#define NC_STATS_COUNT(look_any)
-#endif
 
 // ovf (uniform): the table has keys outside their home buckets, so a full home bucket without a match is not yet a miss
 // vskip: the other endpoint v of the edge.  It is in the table (a neighbour of u) and in EVERY streamed row (their nodes
@@ -176,7 +154,6 @@ __device__ inline unsigned nc_probe_flags(const unsigned *tab, const int4 w, uns
     unsigned f = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) f |= (bucket_look(e[j], k[j], ovf, vskip) ? 1u : 0u) << j;
-    NC_STATS_COUNT((f & vmask) != 0u)
     return f & vmask;
 }
 
@@ -563,20 +540,6 @@ __device__ inline void nc_chunk(const View &g, int u, int2 ru, int sub, int nsub
             if (own && g.dirty) own = edge_dirty(g.dirty[u], g.dirty[v]);
         }
     }
-#ifdef NC_DIRTY_STATS
-    if (g.dirty) {
-        const unsigned long long m = __ballot(own);
-        int len = own ? rv.y : 0;
-        for (int off = 32; off > 0; off >>= 1) len += __shfl_xor(len, off);
-        if (lane == 0) {
-            const int c = SLOTS == 256 ? 0 : SLOTS == 512 ? 1 : SLOTS == 2048 ? 2 : 3;
-            atomicAdd(&nc_dstats[c * 8 + 0], 1ull);
-            atomicAdd(&nc_dstats[c * 8 + 1], m ? 1ull : 0ull);
-            atomicAdd(&nc_dstats[c * 8 + 2], (unsigned long long)__popcll(m));
-            atomicAdd(&nc_dstats[c * 8 + 3], (unsigned long long)len);
-        }
-    }
-#endif
     const bool trivial = curv_type == DCR_CURV_BFC && (ru.y < rv.y ? ru.y : rv.y) == 1;  // bfc_naive.py:18-19
     if (own && trivial && u < v) {
         curv[ru.x + p] = 0.0;  // the slot is in the owner's own row: nothing to look up
@@ -673,8 +636,6 @@ __global__ void __launch_bounds__(256, NC_WAVE_OCC) k_nc_wave(View g, const int2
         row_ok(g, make_int2(-1, total), 14, 0, 0);
         return;
     }
-    long long *tr = g.trace ? g.trace + 2 * ((SLOTS == nc_slots(0) ? 0 : 16384) + (int)(blockIdx.x * WPB + wid) % 16384) : nullptr;
-    if (tr && lane == 0) tr[0] = (long long)__builtin_amdgcn_s_memrealtime();
     // The unit list is dealt round-robin to NC_QUEUES queues, each with its own cursor on its own cache line: one
     // cursor for all waves saturates at ~90 dequeues per microsecond on MI355X and was 40 % of the pass.  A wave
     // starts on the queue of its workgroup (blockIdx % 8: workgroups that share an XCD) and moves on when it is empty.
@@ -711,7 +672,6 @@ __global__ void __launch_bounds__(256, NC_WAVE_OCC) k_nc_wave(View g, const int2
                 wave_sync();
                 nc_chunk<SLOTS, MODE>(g, u, ru, sub, nsub, tab, cnt, sc, &sc->spilled, curv_type, curv);
             }
-            if (tr && lane == 0) tr[1] = (long long)__builtin_amdgcn_s_memrealtime();
         }
     }
 }
@@ -722,15 +682,13 @@ __global__ void __launch_bounds__(256, NC_WAVE_OCC) k_nc_wave(View g, const int2
 template <int SLOTS, int W, int BW, int MODE>
 __device__ inline void nc_block_units(const View &g, const int2 *units, const int32_t *count, int64_t unit_cap,
                                       int32_t *next, int curv_type, double *curv, unsigned *tab, unsigned *cnt_base,
-                                      NcScratch *sc_all, int *it_sh, int trace_slot) {
+                                      NcScratch *sc_all, int *it_sh) {
     const int wid = threadIdx.x >> 6;
     const int total = *count;
     if (total < 0 || total > unit_cap) {  // uniform
         row_ok(g, make_int2(-1, total), 17, 0, 0);
         return;
     }
-    long long *tr = g.trace ? g.trace + 2 * (trace_slot * 16384 + (int)(blockIdx.x * BW + wid) % 16384) : nullptr;
-    if (tr && (threadIdx.x & 63) == 0 && wid < W) tr[0] = (long long)__builtin_amdgcn_s_memrealtime();
     // dynamic dequeue: thread 0 pulls the next unit and publishes it through LDS between two barriers, so every value
     // that steers control flow around the barriers is uniform in the workgroup
     for (int round = 0; round <= total; ++round) {
@@ -766,7 +724,6 @@ __device__ inline void nc_block_units(const View &g, const int2 *units, const in
         if (wid < W && sub < nsub)
             nc_chunk<SLOTS, MODE>(g, u, ru, sub, nsub, tab, cnt_base + wid * (SLOTS / 2), &sc_all[wid], &sc_all[0].spilled,
                                   curv_type, curv);
-        if (tr && (threadIdx.x & 63) == 0 && wid < W) tr[1] = (long long)__builtin_amdgcn_s_memrealtime();
         __syncthreads();  // the table and the unit index are rewritten by the next round
     }
 }
@@ -778,8 +735,7 @@ __global__ void __launch_bounds__(64 * W) k_nc_block(View g, const int2 *units, 
     __shared__ __attribute__((aligned(16))) unsigned cnt_all[W * (SLOTS / 2)];
     __shared__ NcScratch sc_all[W];
     __shared__ int it_sh;
-    nc_block_units<SLOTS, W, W, MODE>(g, units, count, unit_cap, next, curv_type, curv, tab, cnt_all, sc_all, &it_sh,
-                                      SLOTS == 2048 ? 2 : 3);
+    nc_block_units<SLOTS, W, W, MODE>(g, units, count, unit_cap, next, curv_type, curv, tab, cnt_all, sc_all, &it_sh);
 }
 
 // The two largest classes in ONE kernel.  Their workgroups need most of a CU's LDS (table 64 KB + 2 x 32 KB of slot
@@ -795,8 +751,8 @@ __global__ void __launch_bounds__(256) k_nc_block_big(View g, const int2 *units4
     __shared__ __attribute__((aligned(16))) unsigned cnt_all[2 * (16384 / 2)];  // = 4 * (8192 / 2)
     __shared__ NcScratch sc_all[4];
     __shared__ int it_sh;
-    nc_block_units<16384, 2, 4, MODE>(g, units4, count4, cap4, next4, curv_type, curv, tab, cnt_all, sc_all, &it_sh, 4);
-    nc_block_units<8192, 4, 4, MODE>(g, units3, count3, cap3, next3, curv_type, curv, tab, cnt_all, sc_all, &it_sh, 3);
+    nc_block_units<16384, 2, 4, MODE>(g, units4, count4, cap4, next4, curv_type, curv, tab, cnt_all, sc_all, &it_sh);
+    nc_block_units<8192, 4, 4, MODE>(g, units3, count3, cap3, next3, curv_type, curv, tab, cnt_all, sc_all, &it_sh);
 }
 
 // ---- plan: one thread per node appends its units to the list of its degree class -----------------------------
@@ -992,13 +948,7 @@ static int run_nc(dcr_graph *g, int curv_type, bool incremental) {
             g->num_cu = prop.multiProcessorCount;
     }
     View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
-            (int32_t)g->n, 1, nullptr};
-    static const bool want_trace = getenv("DCR_NC_TRACE") != nullptr;
-    if (want_trace) {
-        if (!g->nc_trace) DCR_TRY(dev_alloc(&g->nc_trace, NC_CLASSES * 16384 * 2));
-        DCR_HIP(hipMemsetAsync(g->nc_trace, 0, sizeof(long long) * NC_CLASSES * 16384 * 2, g->stream));
-        vw.trace = g->nc_trace;
-    }
+            (int32_t)g->n, 1};
     NcLists L;
     for (int c = 0; c < NC_CLASSES; ++c) {
         L.units[c] = g->nc_units[c];
@@ -1025,82 +975,30 @@ static int run_nc(dcr_graph *g, int curv_type, bool incremental) {
                            g->dres);
     }
     // the classes are independent: fork them onto side streams; the rarest, longest-running units first
-    static const bool serial = getenv("DCR_SERIAL_BINS") != nullptr;  // debugging aid: one stream
-    hipStream_t s1 = g->stream, s2 = g->stream, s3 = g->stream;
-    if (!serial) {
-        DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
-        s1 = g->side[0]; s2 = g->side[1]; s3 = g->side[2];
-    }
+    DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
     // a class whose smallest degree exceeds the (host-tracked upper bound of the) largest degree has no units: on
     // small graphs that saves the dispatch of up to four full persistent grids.  (Each side stream's wait is enqueued
     // right before its kernel: the chip is through the plan before the host is through these calls.)
     if (g->max_deg_bound > nc_maxdeg(3)) launch_nc_block_big<MODE>(g, vw, curv_type, g->stream);  // classes 4 and 3
     else if (g->max_deg_bound > nc_maxdeg(2)) launch_nc_block<3, MODE>(g, vw, curv_type, g->stream);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(s1, g->ev_fork, 0));
-    if (g->max_deg_bound > nc_maxdeg(1)) launch_nc_block<2, MODE>(g, vw, curv_type, s1);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(s2, g->ev_fork, 0));
-    if (g->max_deg_bound > nc_maxdeg(0)) launch_nc_wave<1, MODE>(g, vw, curv_type, s2);
-    if (!serial) DCR_HIP(hipStreamWaitEvent(s3, g->ev_fork, 0));
-    launch_nc_wave<0, MODE>(g, vw, curv_type, s3);
-    if (!serial) {
-        for (int b = 0; b < 3; ++b) {
-            DCR_HIP(hipEventRecord(g->ev_join[b], g->side[b]));
-            DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[b], 0));
-        }
+    DCR_HIP(hipStreamWaitEvent(g->side[0], g->ev_fork, 0));
+    if (g->max_deg_bound > nc_maxdeg(1)) launch_nc_block<2, MODE>(g, vw, curv_type, g->side[0]);
+    DCR_HIP(hipStreamWaitEvent(g->side[1], g->ev_fork, 0));
+    if (g->max_deg_bound > nc_maxdeg(0)) launch_nc_wave<1, MODE>(g, vw, curv_type, g->side[1]);
+    DCR_HIP(hipStreamWaitEvent(g->side[2], g->ev_fork, 0));
+    launch_nc_wave<0, MODE>(g, vw, curv_type, g->side[2]);
+    for (int b = 0; b < 3; ++b) {
+        DCR_HIP(hipEventRecord(g->ev_join[b], g->side[b]));
+        DCR_HIP(hipStreamWaitEvent(g->stream, g->ev_join[b], 0));
     }
     DCR_HIP(hipGetLastError());
-#ifdef NC_DIRTY_STATS
-    if (incremental) {
-        unsigned long long h[32];
-        DCR_HIP(hipStreamSynchronize(g->stream));
-        DCR_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(nc_dstats), sizeof(h)));
-        for (int c = 0; c < 4; ++c)
-            fprintf(stderr, "[nc dirty stats] class %d: units %llu, with work %llu, edges %llu, row entries %llu\n", c, h[c * 8], h[c * 8 + 1],
-                    h[c * 8 + 2], h[c * 8 + 3]);
-        unsigned long long z[32] = {0};
-        DCR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(nc_dstats), z, sizeof(z)));
-    }
-#endif
-#ifdef NC_STATS
-    {
-        unsigned long long h[8];
-        DCR_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(nc_stats), sizeof(h)));
-        fprintf(stderr, "[nc stats] piece probes (wave level) %llu, slow path %llu (%.1f%%), lanes active %.1f of 64, lanes with a candidate per slow probe %.2f\n",
-                h[0], h[1], 100.0 * h[1] / (h[0] ? h[0] : 1), (double)h[2] / (h[0] ? h[0] : 1), (double)h[3] / (h[1] ? h[1] : 1));
-        unsigned long long z[8] = {0};
-        DCR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(nc_stats), z, sizeof(z)));
-    }
-#endif
-    if (want_trace) {  // per class: when did the waves start / make their last progress (100 MHz ticks -> microseconds)
-        std::vector<long long> h(NC_CLASSES * 16384 * 2);
-        DCR_HIP(hipStreamSynchronize(g->stream));
-        DCR_HIP(hipMemcpy(h.data(), g->nc_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        long long t0 = 0;
-        for (size_t i = 0; i < h.size(); i += 2)
-            if (h[i] && (!t0 || h[i] < t0)) t0 = h[i];
-        for (int c = 0; c < NC_CLASSES; ++c) {
-            std::vector<double> st, en;
-            for (int w = 0; w < 16384; ++w) {
-                const long long a = h[2 * (c * 16384 + w)], b = h[2 * (c * 16384 + w) + 1];
-                if (!a) continue;
-                st.push_back((a - t0) * 0.01);
-                en.push_back(((b ? b : a) - t0) * 0.01);
-            }
-            if (st.empty()) continue;
-            std::sort(st.begin(), st.end());
-            std::sort(en.begin(), en.end());
-            auto q = [](const std::vector<double> &v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
-            fprintf(stderr, "[nc trace] class %d: %zu waves; start p0 %.0f p50 %.0f p100 %.0f us; last progress p10 %.0f p50 %.0f p90 %.0f p99 %.0f p100 %.0f us\n",
-                    c, st.size(), st.front(), q(st, 0.5), st.back(), q(en, 0.1), q(en, 0.5), q(en, 0.9), q(en, 0.99), en.back());
-        }
-    }
     return DCR_OK;
 }
 
 // =====================================================================================================================
 // Round 5: the incremental pass behind a few exactly flagged edits (an SDRF iteration), edge by edge
 // =====================================================================================================================
-// Such a pass recomputes about a hundred edges (tools/build_variant.sh dstats -DNC_DIRTY_STATS).  Through the class kernels
+// Such a pass recomputes about a hundred edges (counted with a diagnostic build since removed).  Through the class kernels
 // above it cost what their longest unit costs: a wave builds a table and streams its unit's edges one after the other, the
 // rows of a long edge batch by batch (class of 63-254 neighbours: 178 us with units of 16 positions, 102 with 4), behind a
 // sweep over the slots for the touched nodes and the two plan launches.  Here: ONE sweep over the slots lists the edges to
@@ -1389,7 +1287,7 @@ static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental) {
         g->nc_fine_cap = need;
     }
     if (!g->nc_queues) DCR_TRY(dev_alloc(&g->nc_queues, 2 * NC_QUEUES * NC_QUEUE_STRIDE));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr, (int32_t)g->n, 1, nullptr};
+    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr, (int32_t)g->n, 1};
     hipLaunchKernelGGL(k_nc_clear, dim3(1), dim3(256), 0, g->stream, g->dres, g->nc_queues, 0, (unsigned *)nullptr, (int64_t)0);
     // (the sweep over every slot costs 11 us per 2.6 M slots, the rows of the flagged nodes a chain of five dependent reads, 14 us
     //  whatever the graph's size: S100k 0.203 / 0.208 ms per iteration sweep / rows, S1M 0.540 / 0.452 — by rows from 4 M slots;
@@ -1432,7 +1330,7 @@ double nc_edges_full_ms(const dcr_graph *g) {
 int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental) {
     const char *fine_env = getenv("DCR_NC_FINE");   // (read per call: the tests run both routes in one process)
     const bool fine_on = !(fine_env && atoi(fine_env) == 0);
-    if (incremental && fine_on && g->pending_edits <= DIRTY_EDITS && !getenv("DCR_NC_TRACE")) {
+    if (incremental && fine_on && g->pending_edits <= DIRTY_EDITS) {
         if (curv_type == DCR_CURV_BFC) return run_nc_fine<MODE_BFC>(g, curv_type, true);
         return run_nc_fine<MODE_TRI>(g, curv_type, true);
     }
@@ -1442,7 +1340,7 @@ int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental) {
     // lowest (nc_edges_full_ms against the two models of h2_can_take; automatic engine choice only: DCR_PASS=nc keeps the class
     // kernels); DCR_NC_FINE_FULL=<slots> forces it for graphs of at most that many adjacency slots (A/B aid).
     bool full_edges = false;
-    if (!incremental && fine_on && !getenv("DCR_NC_TRACE")) {
+    if (!incremental && fine_on) {
         const char *full_env = getenv("DCR_NC_FINE_FULL");
         if (full_env) full_edges = g->cap_total <= atoll(full_env);
         else full_edges = g->pass_impl == 0 && nc_edges_full_ms(g) < nc_class_full_ms(g);

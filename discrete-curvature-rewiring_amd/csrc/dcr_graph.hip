@@ -18,14 +18,10 @@ static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 
 // Events that order the streams of a pass against each other.  A device-scope release when recorded (hipEventReleaseToDevice,
-// -DDCR_EVENT_DEVICE_SCOPE) instead of the default system-scope fence was measured: the gap between the split class and its
-// triangle step shrank from 50 to 6 us on the timeline, and the pass got 4 % SLOWER (1.053 against 1.004 ms on S100k, 10.75
+// measured with a build switch since removed) instead of the default system-scope fence: the gap between the split class and
+// its triangle step shrank from 50 to 6 us on the timeline, and the pass got 4 % SLOWER (1.053 against 1.004 ms on S100k, 10.75
 // against 10.44 on S1M, four interleaved rounds: profiles/r04_event_scope_ab.txt).  The default stays.
-#ifdef DCR_EVENT_DEVICE_SCOPE
-#define DCR_EVENT_FLAGS (hipEventDisableTiming | hipEventReleaseToDevice)
-#else
 #define DCR_EVENT_FLAGS (hipEventDisableTiming)
-#endif
 
 static inline int32_t slack_for(int32_t deg) {
     int32_t s = deg / 4;
@@ -510,7 +506,7 @@ int dcr_graph_destroy(dcr_graph *g) {
                         g->imp_table, g->imp_posx, g->imp_posy, g->imp_c1, g->imp_c2, g->imp_b, g->imp_c,
                         g->imp_rowcount, g->imp_rowoff, g->imp_adjbits, g->imp_out, g->imp_ci, g->imp_cj,
                         g->imp_stats, g->draw_bsum, g->dres, g->dirty, g->nc_units[0], g->nc_units[1], g->nc_units[2],
-                        g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_trace, g->nc_queues, g->giant_list,
+                        g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_queues, g->giant_list,
                         g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight,
                         g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
                         g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists, g->chg_members, g->chg_counts, g->chg_values};

@@ -235,7 +235,6 @@ struct dcr_graph {
     // node-centric pass (dcr_bfc_nc.hip): unit lists per degree class
     int2 *nc_units[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // {node, first sub-unit}
     int64_t nc_cap[5] = {0, 0, 0, 0, 0};
-    long long *nc_trace = nullptr;  // DCR_NC_TRACE diagnostic: [5 classes][16384 waves][2]
     int32_t *nc_queues = nullptr;  // dequeue cursors of the two wave-class kernels, one cache line each
     uint8_t *nc_touch = nullptr;  // [n] incremental pass: node has a flagged neighbour
     int64_t nc_touch_cap = 0;

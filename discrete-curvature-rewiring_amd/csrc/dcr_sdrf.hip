@@ -12,7 +12,6 @@
 //   * every other admissible pair leaves all ingredients unchanged: improvement = +0.0.
 #include <cstdlib>
 #include "dcr_internal.h"
-#include <chrono>
 #include <cstdio>
 
 namespace dcr {
@@ -1083,10 +1082,6 @@ int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want
     if (x < 0 || y < 0 || x >= g->n || y >= g->n || x == y) DCR_FAIL(DCR_EINVAL, "bad node ids");
     if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
     DCR_HIP(hipSetDevice(g->device));
-#ifdef DCR_IMP_TIMING
-    static double t_enq = 0, t_sync = 0; static long t_n = 0;
-    const auto T0 = std::chrono::steady_clock::now();
-#endif
     int64_t upper = 0;
     DCR_TRY(imp_enqueue(g, x, y, curv_type, &upper));
     // one host sync: the result block and the values go out together; the candidate count is not known yet, so the
@@ -1105,16 +1100,7 @@ int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want
         DCR_HIP(hipMemcpyAsync(g->imp_ci_h, g->imp_ci, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipMemcpyAsync(g->imp_cj_h, g->imp_cj, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
     }
-#ifdef DCR_IMP_TIMING
-    const auto T1 = std::chrono::steady_clock::now();
-#endif
     DCR_TRY(sync_result(g));
-#ifdef DCR_IMP_TIMING
-    const auto T2 = std::chrono::steady_clock::now();
-    t_enq += std::chrono::duration<double, std::micro>(T1 - T0).count();
-    t_sync += std::chrono::duration<double, std::micro>(T2 - T1).count();
-    if (++t_n % 50 == 0) fprintf(stderr, "[imp timing] enqueue %.1f us, sync wait %.1f us (avg of %ld)\n", t_enq / t_n, t_sync / t_n, t_n);
-#endif
     const int64_t n = g->hres->n_cand;
     if (n < 0 || n > upper) DCR_FAIL(DCR_ESTATE, "candidate count outside its bound");
     g->imp_n = n;
@@ -1372,8 +1358,7 @@ int dcr_sdrf_iteration_device_draw(dcr_graph *g, int32_t x, int32_t y, int curv_
     // (Round 5: not in front of an INCREMENTAL pass — three launches on this one stream, 0.08 ms: there the round trip costs a
     //  tenth of the iteration and saves nothing; an undecided draw makes the tail a no-op (it reads the verdict in the result
     //  block), the pass then finds nothing flagged, and the verdict comes over with the pass's result.)
-    static const int sync_env = getenv("DCR_DRAW_SYNC") ? atoi(getenv("DCR_DRAW_SYNC")) : -1;   // 1: always, 0: never (A/B aid)
-    if (sync_env < 0 ? !incremental : sync_env != 0) {
+    if (!incremental) {
         DCR_TRY(sync_result(g));
         g->imp_n = g->hres->n_cand;
         *out_n_cand = g->hres->n_cand;

@@ -1,5 +1,4 @@
-"""Incremental SDRF iterations at the bench shape: step and pass time; DCR_NC_TRACE=1 prints when the waves of every class of
-the node-centric pass started and made their last progress (K small then)."""
+"""Incremental SDRF iterations at the bench shape: step and pass time."""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, 'discrete-curvature-rewiring_amd')]
