@@ -254,16 +254,22 @@ class GraphedEpoch:
         self.optimizer.step()
         return loss
 
+    def _count(self, log_probs, at_val_rows):
+        """Correct arg-max predictions on the validation split (int64 0-dim) from log-probabilities of its rows only
+        (``at_val_rows``: one kernel where the labels fit it) or of every node."""
+        if not at_val_rows:
+            return log_probs.index_select(0, self.val_idx).max(1)[1].eq(self.y_val).sum()
+        if _fused_ok(log_probs) and self._labels_fit(log_probs.shape[1]):
+            return _count_correct(log_probs, self.y_val)
+        return log_probs.max(1)[1].eq(self.y_val).sum()
+
     def _val_correct(self):
         with torch.no_grad():
             head = self._head(False, True)
             if head is not None:
                 return head[1]
-            if self.rows:
-                lp = self.model(self.data, rows=self.val_idx)
-                return _count_correct(lp, self.y_val) if _fused_ok(lp) and self._labels_fit(lp.shape[1]) else lp.max(1)[1].eq(self.y_val).sum()
-            log_probs = self.model(self.data)
-        return log_probs.index_select(0, self.val_idx).max(1)[1].eq(self.y_val).sum()
+            log_probs = self.model(self.data, rows=self.val_idx) if self.rows else self.model(self.data)
+        return self._count(log_probs, self.rows)
 
     def __call__(self):
         """Runs one epoch; returns the validation accuracy."""
@@ -330,11 +336,9 @@ class LaggedGraphedEpoch(GraphedEpoch):
             return correct_prev
         if self.rows:
             lp_train, lp_eval = self.model.forward_pair(self.data, rows_train=self.train_idx, rows_eval=self.val_idx)
-            correct_prev = (_count_correct(lp_eval, self.y_val) if _fused_ok(lp_eval) and self._labels_fit(lp_eval.shape[1])
-                            else lp_eval.max(1)[1].eq(self.y_val).sum())
         else:
             lp_train, lp_eval = self.model.forward_pair(self.data)
-            correct_prev = lp_eval.index_select(0, self.val_idx).max(1)[1].eq(self.y_val).sum()
+        correct_prev = self._count(lp_eval, self.rows)
         loss = self._nll(lp_train)
         loss.backward()
         self.optimizer.step()

@@ -21,6 +21,8 @@ from typing import List
 import torch
 from torch.nn import Dropout, ModuleList, Parameter, ReLU
 
+from dcr import _lib   # (the loader only: the library itself is opened at the first call of _lib.lib())
+
 # 'hip': the product path (ROCm tensors only, raises otherwise).
 # 'torch': plain-torch aggregation; selected explicitly by CPU-only tests (gloo) — never automatically.
 _AGG_BACKEND = 'hip'
@@ -31,6 +33,15 @@ def set_aggregate_backend(name):
     if name not in ('hip', 'torch'):
         raise ValueError(name)
     _AGG_BACKEND = name
+
+
+def _stream(t):
+    """The current stream of ``t``'s device, as the kernels' stream argument."""
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 class NormCSR:
@@ -104,18 +115,13 @@ def _spmm_hip(rowptr, col, val, B, n_rows, bias=None, relu=False):
     if not B.is_cuda:
         raise RuntimeError('GCN aggregation runs on the MI355X HIP kernel: move the model and data to a ROCm '
                            'device (there is no CPU fallback)')
-    from dcr import _lib
     B = B.contiguous()
     if B.dtype != torch.float32:
         raise TypeError('dcr_spmm_csr_f32_dev is fp32')
     F = B.shape[1]
     C = torch.empty((n_rows, F), dtype=torch.float32, device=B.device)
-    stream = torch.cuda.current_stream(B.device).cuda_stream
-    rc = _lib.lib().dcr_spmm_csr_f32_dev(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), B.data_ptr(),
-                                         C.data_ptr(), n_rows, F, F, F,
-                                         bias.data_ptr() if bias is not None else None, int(relu),
-                                         ctypes.c_void_p(stream))
-    _lib.check(rc)
+    _lib.check(_lib.lib().dcr_spmm_csr_f32_dev(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), B.data_ptr(), C.data_ptr(),
+                                               n_rows, F, F, F, _ptr(bias), int(relu), _stream(B)))
     return C
 
 
@@ -143,22 +149,40 @@ def spmm_pair(rowptr, col, val, B2, n_rows, n_feat, bias=None, split=False):
         return (a, b) if split else torch.cat([a, b], 1)
     if not B2.is_cuda:
         raise RuntimeError('GCN aggregation runs on the MI355X HIP kernel (there is no CPU fallback)')
-    from dcr import _lib
     B2 = B2.contiguous()
-    stream = torch.cuda.current_stream(B2.device).cuda_stream
     if split and n_feat % 4 == 0:
         C = torch.empty((2, n_rows, n_feat), dtype=torch.float32, device=B2.device)
         _lib.check(_lib.lib().dcr_spmm_csr_f32_pair_split_dev(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), B2.data_ptr(),
                                                               C[0].data_ptr(), C[1].data_ptr(), n_rows, n_feat, 2 * n_feat, n_feat,
-                                                              bias.data_ptr() if bias is not None else None, 0,
-                                                              ctypes.c_void_p(stream)))
+                                                              _ptr(bias), 0, _stream(B2)))
         return C[0], C[1]
     C = torch.empty((n_rows, 2 * n_feat), dtype=torch.float32, device=B2.device)
-    _lib.check(_lib.lib().dcr_spmm_csr_f32_pair_dev(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), B2.data_ptr(),
-                                                    C.data_ptr(), n_rows, n_feat, 2 * n_feat, 2 * n_feat,
-                                                    bias.data_ptr() if bias is not None else None, 0,
-                                                    ctypes.c_void_p(stream)))
+    _lib.check(_lib.lib().dcr_spmm_csr_f32_pair_dev(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), B2.data_ptr(), C.data_ptr(),
+                                                    n_rows, n_feat, 2 * n_feat, 2 * n_feat, _ptr(bias), 0, _stream(B2)))
     return (C[:, :n_feat].contiguous(), C[:, n_feat:].contiguous()) if split else C
+
+
+def _aggregate_backward(csr, sel, grad, z_shape, need_z, need_b):
+    """(dZ, db) of out = (Â·Z + b)[sel.idx] (``sel`` None: every row) from ``grad``, the gradient of out: dZ = Âᵀ[:, sel.idx]·grad,
+    zeros of ``z_shape`` for an empty selection; db = Σ_rows grad.  Either is None when not needed."""
+    grad = grad.contiguous()
+    gz = None
+    if need_z:
+        if sel is None:
+            gz = spmm(csr.rowptr_t, csr.col_t, csr.val_t, grad, csr.n_cols)
+        elif sel.n == 0:
+            gz = grad.new_zeros(z_shape)
+        else:
+            gz = spmm(*sel.transposed(), grad, csr.n_cols)
+    return gz, (grad.sum(0) if need_b else None)
+
+
+def _halves_of_one_buffer(z_train, z_eval):
+    """Whether the two operands are the column blocks [z_train | z_eval] of ONE fp32 matrix on the GPU: act_then_linear and the
+    one-kernel first layer write them that way, and the pair aggregations then read both without a concatenation."""
+    f = z_train.shape[1]
+    return (z_train.is_cuda and z_train.dtype == torch.float32 and z_train.stride() == (2 * f, 1) and z_eval.stride() == (2 * f, 1)
+            and z_eval.data_ptr() == z_train.data_ptr() + 4 * f)
 
 
 class _Aggregate(torch.autograd.Function):
@@ -172,11 +196,8 @@ class _Aggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        csr = ctx.csr
-        grad_out = grad_out.contiguous()
-        gz = spmm(csr.rowptr_t, csr.col_t, csr.val_t, grad_out, csr.n_cols) if ctx.needs_input_grad[0] else None
-        gb = grad_out.sum(0) if ctx.has_bias and ctx.needs_input_grad[1] else None
-        return gz, gb, None
+        need = ctx.needs_input_grad
+        return _aggregate_backward(ctx.csr, None, grad_out, None, need[0], ctx.has_bias and need[1]) + (None,)
 
 
 def aggregate(z, bias, csr):
@@ -191,20 +212,26 @@ class _AggregatePair(torch.autograd.Function):
         ctx.csr = csr
         ctx.has_bias = bias is not None
         f = z_train.shape[1]
-        if (z_train.is_cuda and z_train.stride() == (2 * f, 1) and z_eval.stride() == (2 * f, 1)
-                and z_eval.data_ptr() == z_train.data_ptr() + 4 * f and z_train.dtype == torch.float32):
-            b2 = torch.as_strided(z_train, (z_train.shape[0], 2 * f), (2 * f, 1))   # the two halves of one buffer (act_then_linear)
+        if _halves_of_one_buffer(z_train, z_eval):
+            b2 = torch.as_strided(z_train, (z_train.shape[0], 2 * f), (2 * f, 1))
         else:
             b2 = torch.cat([z_train, z_eval], 1)
         return spmm_pair(csr.rowptr, csr.col, csr.val, b2, csr.n_rows, f, bias=bias, split=True)
 
     @staticmethod
     def backward(ctx, grad_train, grad_eval):
-        csr = ctx.csr
-        grad_train = grad_train.contiguous()
-        gz = spmm(csr.rowptr_t, csr.col_t, csr.val_t, grad_train, csr.n_cols) if ctx.needs_input_grad[0] else None
-        gb = grad_train.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        need = ctx.needs_input_grad
+        gz, gb = _aggregate_backward(ctx.csr, None, grad_train, None, need[0], ctx.has_bias and need[2])
         return gz, None, gb, None
+
+
+def _aggregate_wanted(z_train, z_eval, bias, csr):
+    """(Â·Z_train + b, Â·Z_eval + b) at every row for the operands wanted (None: not wanted), both in one sweep of the graph."""
+    if z_train is not None and z_eval is not None:
+        return _AggregatePair.apply(z_train, z_eval, bias, csr)
+    if z_train is not None:
+        return aggregate(z_train, bias, csr), None
+    return None, aggregate(z_eval, bias, csr)
 
 
 class RowSelection:
@@ -281,12 +308,25 @@ def spmm_rows(csr, sel, B, bias=None):
     C = torch.empty((sel.n, F), dtype=torch.float32, device=B.device)
     if sel.n == 0:
         return C
-    from dcr import _lib
-    stream = torch.cuda.current_stream(B.device).cuda_stream
     _lib.check(_lib.lib().dcr_spmm_csr_rows_f32_dev(csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(),
                                                     sel.idx.data_ptr(), sel.n, B.data_ptr(), C.data_ptr(), F, B.stride(0), F,
-                                                    bias.data_ptr() if bias is not None else None, 0, ctypes.c_void_p(stream)))
+                                                    _ptr(bias), 0, _stream(B)))
     return C
+
+
+def _spmm_rows_pair(csr, sel_train, sel_eval, z_train, z_eval, bias):
+    """(rows ``sel_train`` of Â·Z_train + b, rows ``sel_eval`` of Â·Z_eval + b): ONE launch (``dcr_spmm_csr_rows2_f32_dev``) when
+    the two operands are the halves of one buffer, two ``spmm_rows`` calls otherwise; every row as ``spmm_rows`` computes it."""
+    f = z_train.shape[1]
+    if not (_AGG_BACKEND == 'hip' and f % 4 == 0 and sel_train.n > 0 and sel_eval.n > 0 and _halves_of_one_buffer(z_train, z_eval)):
+        out_ev = spmm_rows(csr, sel_eval, z_eval, bias)
+        return spmm_rows(csr, sel_train, z_train, bias), out_ev
+    both = sel_train.joined_with(sel_eval)
+    C = torch.empty((sel_train.n + sel_eval.n, f), dtype=torch.float32, device=z_train.device)
+    _lib.check(_lib.lib().dcr_spmm_csr_rows2_f32_dev(csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(), both.data_ptr(),
+                                                     sel_train.n, sel_train.n + sel_eval.n, z_train.data_ptr(), f, C.data_ptr(), f,
+                                                     2 * f, f, _ptr(bias), 0, _stream(z_train)))
+    return C[:sel_train.n], C[sel_train.n:]
 
 
 class _AggregateRows(torch.autograd.Function):
@@ -301,17 +341,8 @@ class _AggregateRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        csr, sel = ctx.csr, ctx.sel
-        grad_out = grad_out.contiguous()
-        gz = None
-        if ctx.needs_input_grad[0]:
-            if sel.n == 0:
-                gz = grad_out.new_zeros(ctx.z_shape)
-            else:
-                rp, ci, va = sel.transposed()
-                gz = spmm(rp, ci, va, grad_out, csr.n_cols)
-        gb = grad_out.sum(0) if ctx.has_bias and ctx.needs_input_grad[1] else None
-        return gz, gb, None, None
+        need = ctx.needs_input_grad
+        return _aggregate_backward(ctx.csr, ctx.sel, grad_out, ctx.z_shape, need[0], ctx.has_bias and need[1]) + (None, None)
 
 
 def aggregate_rows(z, bias, csr, sel):
@@ -328,38 +359,14 @@ class _AggregateRowsPair(torch.autograd.Function):
         ctx.csr, ctx.sel = csr, sel_train
         ctx.has_bias = bias is not None
         ctx.z_shape = z_train.shape
-        f = z_train.shape[1]
-        joined = (_AGG_BACKEND == 'hip' and z_train.is_cuda and z_train.dtype == torch.float32 and f % 4 == 0
-                  and z_train.stride() == (2 * f, 1) and z_eval.stride() == (2 * f, 1)
-                  and z_eval.data_ptr() == z_train.data_ptr() + 4 * f and sel_train.n > 0 and sel_eval.n > 0)
-        if not joined:
-            out_ev = spmm_rows(csr, sel_eval, z_eval, bias)
-            ctx.mark_non_differentiable(out_ev)
-            return spmm_rows(csr, sel_train, z_train, bias), out_ev
-        from dcr import _lib
-        both = sel_train.joined_with(sel_eval)
-        C = torch.empty((sel_train.n + sel_eval.n, f), dtype=torch.float32, device=z_train.device)
-        stream = torch.cuda.current_stream(z_train.device).cuda_stream
-        _lib.check(_lib.lib().dcr_spmm_csr_rows2_f32_dev(csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(), both.data_ptr(),
-                                                         sel_train.n, sel_train.n + sel_eval.n, z_train.data_ptr(), f, C.data_ptr(), f,
-                                                         2 * f, f, bias.data_ptr() if bias is not None else None, 0,
-                                                         ctypes.c_void_p(stream)))
-        out_tr, out_ev = C[:sel_train.n], C[sel_train.n:]
+        out_tr, out_ev = _spmm_rows_pair(csr, sel_train, sel_eval, z_train, z_eval, bias)
         ctx.mark_non_differentiable(out_ev)
         return out_tr, out_ev
 
     @staticmethod
     def backward(ctx, grad_train, grad_eval):
-        csr, sel = ctx.csr, ctx.sel
-        grad_train = grad_train.contiguous()
-        gz = None
-        if ctx.needs_input_grad[0]:
-            if sel.n == 0:
-                gz = grad_train.new_zeros(ctx.z_shape)
-            else:
-                rp, ci, va = sel.transposed()
-                gz = spmm(rp, ci, va, grad_train, csr.n_cols)
-        gb = grad_train.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        need = ctx.needs_input_grad
+        gz, gb = _aggregate_backward(ctx.csr, ctx.sel, grad_train, ctx.z_shape, need[0], ctx.has_bias and need[2])
         return gz, None, gb, None, None, None
 
 
@@ -372,9 +379,9 @@ def _workspace(kind, device, stream, *shape):
     zero before the first launch and every launch leaves them zero, so a buffer is zero-filled once, on creation, and needs
     no fill launch per call.  One buffer per (kind, device, stream, shape), never evicted: a captured epoch replays on the
     raw pointers it was captured with."""
+    stream = getattr(stream, 'value', stream) or 0          # (an integer handle, or what ``_stream`` gives)
     key = (kind, str(device), int(stream)) + tuple(int(v) for v in shape)
     if key not in _WORKSPACES:
-        from dcr import _lib
         need = ctypes.c_int64()
         if kind == 'head':
             _lib.check(_lib.lib().dcr_head_workspace(ctypes.byref(need)))
@@ -415,18 +422,17 @@ class _AggregateRowsHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_train, z_eval, bias, csr, sel_train, sel_eval, y_train, y_eval):
-        from dcr import _lib
         have_tr, have_ev = z_train is not None, z_eval is not None
         ref = z_train if have_tr else z_eval
         f = ref.shape[1]
         out_tr = out_ev = None
         if have_tr and have_ev:
-            out_tr, out_ev = _AggregateRowsPair.forward(_NoCtx(), z_train, z_eval, bias, csr, sel_train, sel_eval)
+            out_tr, out_ev = _spmm_rows_pair(csr, sel_train, sel_eval, z_train, z_eval, bias)
         elif have_tr:
             out_tr = spmm_rows(csr, sel_train, z_train, bias)
         else:
             out_ev = spmm_rows(csr, sel_eval, z_eval, bias)
-        stream = torch.cuda.current_stream(ref.device).cuda_stream
+        stream = _stream(ref)
         ws = _head_workspace(ref.device, stream)
         loss = torch.empty((), dtype=torch.float32, device=ref.device) if have_tr else None
         correct = torch.empty((), dtype=torch.int64, device=ref.device) if have_ev else None
@@ -436,8 +442,7 @@ class _AggregateRowsHead(torch.autograd.Function):
             _lib.check(_lib.lib().dcr_head_fwd_f32_dev(
                 out_tr.data_ptr() if m_tr else None, out_tr.stride(0) if m_tr else f, y_train.data_ptr() if m_tr else None, m_tr,
                 out_ev.data_ptr() if m_ev else None, out_ev.stride(0) if m_ev else f, y_eval.data_ptr() if m_ev else None, m_ev, f,
-                loss.data_ptr() if have_tr else None, correct.data_ptr() if have_ev else None, ws.data_ptr(), ws.numel() * 8,
-                ctypes.c_void_p(stream)))
+                _ptr(loss), _ptr(correct), ws.data_ptr(), ws.numel() * 8, stream))
         if have_tr and not m_tr:
             loss.fill_(float('nan'))          # (the mean over no rows, as F.nll_loss gives it)
         if have_ev and not m_ev:
@@ -451,37 +456,23 @@ class _AggregateRowsHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_correct):
-        from dcr import _lib
-        csr, sel, out_tr = ctx.csr, ctx.sel, ctx.out_tr
+        out_tr, need = ctx.out_tr, ctx.needs_input_grad
         if g_loss is None or out_tr is None:
-            return None, None, None, None, None, None, None, None
+            return (None,) * 8
         m, f = out_tr.shape
-        gz = gb = None
-        if m == 0:
-            return (out_tr.new_zeros(ctx.z_shape) if ctx.needs_input_grad[0] else None, None,
-                    out_tr.new_zeros(f) if ctx.has_bias and ctx.needs_input_grad[2] else None, None, None, None, None, None)
+        need_b = ctx.has_bias and need[2]
+        if m == 0:   # (no training rows: zero gradients, no head kernel)
+            gz, _ = _aggregate_backward(ctx.csr, ctx.sel, out_tr, ctx.z_shape, need[0], False)
+            return (gz, None, out_tr.new_zeros(f) if need_b else None) + (None,) * 5
         g = g_loss.contiguous().float()
         grad = torch.empty((m, f), dtype=torch.float32, device=out_tr.device)
-        gb_buf = torch.empty(f, dtype=torch.float32, device=out_tr.device)
-        stream = torch.cuda.current_stream(out_tr.device).cuda_stream
+        gb = torch.empty(f, dtype=torch.float32, device=out_tr.device)
+        stream = _stream(out_tr)
         ws = _head_workspace(out_tr.device, stream)
         _lib.check(_lib.lib().dcr_head_bwd_f32_dev(out_tr.data_ptr(), out_tr.stride(0), ctx.y_train.data_ptr(), m, f, g.data_ptr(),
-                                                   grad.data_ptr(), gb_buf.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                                   ctypes.c_void_p(stream)))
-        if ctx.needs_input_grad[0]:
-            rp, ci, va = sel.transposed()
-            gz = spmm(rp, ci, va, grad, csr.n_cols)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = gb_buf
-        return gz, None, gb, None, None, None, None, None
-
-
-class _NoCtx:
-    """Stands in for an autograd context where a Function's forward is reused as a plain function."""
-    needs_input_grad = (False,) * 8
-
-    def mark_non_differentiable(self, *a):
-        pass
+                                                   grad.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream))
+        gz, _ = _aggregate_backward(ctx.csr, ctx.sel, grad, ctx.z_shape, need[0], False)   # (db came out of the head kernel)
+        return (gz, None, gb if need_b else None) + (None,) * 5
 
 
 def atb_hip(a, b):
@@ -489,7 +480,6 @@ def atb_hip(a, b):
     (csrc/dcr_gemm.hip, ``dcr_atb_f32_dev``)."""
     if not (a.is_cuda and b.is_cuda):
         raise RuntimeError('dcr_atb_f32_dev runs on the MI355X (there is no CPU fallback)')
-    from dcr import _lib
     a, b = a.contiguous(), b.contiguous()
     if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape[0] != b.shape[0]:
         raise TypeError('atb_hip: fp32 [K, M] and [K, N] expected')
@@ -498,9 +488,8 @@ def atb_hip(a, b):
     _lib.check(_lib.lib().dcr_atb_f32_workspace(K, M, N, ctypes.byref(need)))
     ws = torch.empty(max(need.value, 1), dtype=torch.float32, device=a.device)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    stream = torch.cuda.current_stream(a.device).cuda_stream
     _lib.check(_lib.lib().dcr_atb_f32_dev(a.data_ptr(), b.data_ptr(), out.data_ptr(), K, M, N, M, N, N, ws.data_ptr(),
-                                          need.value, ctypes.c_void_p(stream)))
+                                          need.value, _stream(a)))
     return out
 
 
@@ -526,15 +515,18 @@ class _LinearFn(torch.autograd.Function):
             # and 3.9x slower at 1M nodes); for wide layers on small graphs the library is as fast
             tall = x.shape[0] >= 64 * max(x.shape[1], grad_out.shape[1])
             gw = atb_hip(grad_out, x) if tall else grad_out.t() @ x
-        gb = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            ready = getattr(grad_out, '_dcr_colsum', None)   # left there by the kernel that produced this gradient
-            if ready is not None and ready[:2] == (grad_out.data_ptr(), grad_out._version):
-                gb = ready[2]
-                _LinearFn.colsum_handoffs += 1
-            else:
-                gb = grad_out.sum(0)
+        gb = _column_sums(grad_out) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb
+
+
+def _column_sums(grad):
+    """``grad.sum(0)`` — a bias gradient — taken from the kernel that produced ``grad`` where it left them there
+    (``_dcr_colsum``, see ``_act_linear_backward``), computed otherwise."""
+    ready = getattr(grad, '_dcr_colsum', None)
+    if ready is not None and ready[:2] == (grad.data_ptr(), grad._version):
+        _LinearFn.colsum_handoffs += 1
+        return ready[2]
+    return grad.sum(0)
 
 
 _dropout_ctr = {}  # per device: int64 call counter IN DEVICE MEMORY = offset of the Philox stream (one step per fused
@@ -549,35 +541,44 @@ def _dropout_counter(device):
     return _dropout_ctr[key]
 
 
+def _dropout_bits(numel, device):
+    """(keep bits of a tensor of ``numel`` elements, one bit each, uninitialised; the device's dropout counter)."""
+    words = ctypes.c_int64()
+    _lib.check(_lib.lib().dcr_relu_dropout_bits_words(numel, ctypes.byref(words)))
+    return torch.empty(max(words.value, 1), dtype=torch.int64, device=device), _dropout_counter(device)
+
+
+def _train_eval_outputs(n, classes, want_train, want_eval, like):
+    """(z_train, z_eval, their leading dimension) of a kernel that writes either or both: both as the halves of ONE buffer
+    [z_train | z_eval] — what the pair aggregations read, without a concatenation; None for the one not wanted."""
+    if want_train and want_eval:
+        both = torch.empty((n, 2 * classes), dtype=like.dtype, device=like.device)
+        return both[:, :classes], both[:, classes:], 2 * classes
+    z = torch.empty((n, classes), dtype=like.dtype, device=like.device)
+    return (z, None, classes) if want_train else (None, z, classes)
+
+
 class _ReluDropoutFn(torch.autograd.Function):
     """y = dropout(relu(x)) in one pass each way (csrc/dcr_gcn.hip), the keep mask packed to one bit per element."""
 
     @staticmethod
     def forward(ctx, x, p):
-        from dcr import _lib
         x = x.contiguous()
-        n = x.numel()
-        words = ctypes.c_int64()
-        _lib.check(_lib.lib().dcr_relu_dropout_bits_words(n, ctypes.byref(words)))
-        bits = torch.empty(max(words.value, 1), dtype=torch.int64, device=x.device)
+        bits, ctr = _dropout_bits(x.numel(), x.device)
         y = torch.empty_like(x)
-        ctr = _dropout_counter(x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.lib().dcr_relu_dropout_fwd_f32_ctr_dev(x.data_ptr(), y.data_ptr(), bits.data_ptr(), n, float(p),
+        _lib.check(_lib.lib().dcr_relu_dropout_fwd_f32_ctr_dev(x.data_ptr(), y.data_ptr(), bits.data_ptr(), x.numel(), float(p),
                                                                torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0,
-                                                               ctr.data_ptr(), ctypes.c_void_p(stream)))
+                                                               ctr.data_ptr(), _stream(x)))
         ctr.add_(1)
         ctx.bits, ctx.p = bits, float(p)
         return y
 
     @staticmethod
     def backward(ctx, grad_out):
-        from dcr import _lib
         grad_out = grad_out.contiguous()
         gin = torch.empty_like(grad_out)
-        stream = torch.cuda.current_stream(grad_out.device).cuda_stream
         _lib.check(_lib.lib().dcr_relu_dropout_bwd_f32_dev(grad_out.data_ptr(), gin.data_ptr(), ctx.bits.data_ptr(),
-                                                           grad_out.numel(), ctx.p, ctypes.c_void_p(stream)))
+                                                           grad_out.numel(), ctx.p, _stream(grad_out)))
         return gin, None
 
 
@@ -598,30 +599,16 @@ class _ActLinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, p, want_train, want_eval):
-        from dcr import _lib
         x = x.contiguous()
         w = weight.contiguous()
         n, hidden = x.shape
         classes = w.shape[0]
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if want_train and want_eval:  # one buffer [z_train | z_eval]: what the pair aggregation reads, without a concatenation
-            both = torch.empty((n, 2 * classes), dtype=x.dtype, device=x.device)
-            z_tr, z_ev = both[:, :classes], both[:, classes:]
-        else:
-            z_tr = torch.empty((n, classes), dtype=x.dtype, device=x.device) if want_train else None
-            z_ev = torch.empty((n, classes), dtype=x.dtype, device=x.device) if want_eval else None
-        ldz = 2 * classes if (want_train and want_eval) else classes
-        bits = ctr = None
-        if want_train:
-            words = ctypes.c_int64()
-            _lib.check(_lib.lib().dcr_relu_dropout_bits_words(x.numel(), ctypes.byref(words)))
-            bits = torch.empty(max(words.value, 1), dtype=torch.int64, device=x.device)
-            ctr = _dropout_counter(x.device)
+        z_tr, z_ev, ldz = _train_eval_outputs(n, classes, want_train, want_eval, x)
+        bits, ctr = _dropout_bits(x.numel(), x.device) if want_train else (None, None)
         # (no training activation is stored: the backward kernel rebuilds it from x and the keep bits)
         _lib.check(_lib.lib().dcr_act_linear_fwd_f32_dev(
-            x.data_ptr(), w.data_ptr(), None, z_tr.data_ptr() if want_train else None,
-            z_ev.data_ptr() if want_eval else None, ldz, bits.data_ptr() if want_train else None, n, hidden, classes, float(p),
-            torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0, ctr.data_ptr() if want_train else None, ctypes.c_void_p(stream)))
+            x.data_ptr(), w.data_ptr(), None, _ptr(z_tr), _ptr(z_ev), ldz, _ptr(bits), n, hidden, classes, float(p),
+            torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0, _ptr(ctr), _stream(x)))
         if want_train:
             ctr.add_(1)
             ctx.save_for_backward(x, w)
@@ -632,26 +619,30 @@ class _ActLinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_tr, g_ev):
-        from dcr import _lib
         x, w = ctx.saved_tensors
-        g_tr = g_tr.contiguous()
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None, None, None
-        # one pass over x (dcr_act_linear_bwd_fused_f32_dev): dx, its column sums — the bias gradient of the layer that
-        # produced x, which _LinearFn.backward picks up instead of reading the N x H gradient once more — and dW
-        stream = torch.cuda.current_stream(g_tr.device).cuda_stream
-        n, hidden = x.shape
-        gx = torch.empty_like(x)
-        gw = torch.empty_like(w)
-        colsum = torch.empty(hidden, dtype=torch.float32, device=x.device)
-        need = ctypes.c_int64()
-        _lib.check(_lib.lib().dcr_act_linear_bwd_fused_workspace(n, hidden, ctypes.byref(need)))
-        ws = torch.empty(max(need.value, 1), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().dcr_act_linear_bwd_fused_f32_dev(g_tr.data_ptr(), w.data_ptr(), ctx.bits.data_ptr(), x.data_ptr(),
-                                                               gx.data_ptr(), gw.data_ptr(), colsum.data_ptr(), ws.data_ptr(),
-                                                               need.value, n, hidden, w.shape[0], ctx.p, ctypes.c_void_p(stream)))
+        gx, gw, colsum = _act_linear_backward(g_tr.contiguous(), w, ctx.bits, x, ctx.p)
+        # (the column sums of dx are the bias gradient of the layer that produced x: _column_sums picks them up there instead of
+        #  reading the N x H gradient once more)
         gx._dcr_colsum = (gx.data_ptr(), gx._version, colsum)
         return (gx if ctx.needs_input_grad[0] else None), (gw if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def _act_linear_backward(g, w, bits, x, p):
+    """(dx, dW, column sums of dx) of z = dropout(relu(x))·Wᵀ from dz = ``g`` in one pass over x
+    (``dcr_act_linear_bwd_fused_f32_dev``): the activation is rebuilt from x and the keep bits."""
+    n, hidden = x.shape
+    gx = torch.empty_like(x)
+    gw = torch.empty_like(w)
+    colsum = torch.empty(hidden, dtype=torch.float32, device=x.device)
+    need = ctypes.c_int64()
+    _lib.check(_lib.lib().dcr_act_linear_bwd_fused_workspace(n, hidden, ctypes.byref(need)))
+    ws = torch.empty(max(need.value, 1), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dcr_act_linear_bwd_fused_f32_dev(g.data_ptr(), w.data_ptr(), bits.data_ptr(), x.data_ptr(), gx.data_ptr(),
+                                                           gw.data_ptr(), colsum.data_ptr(), ws.data_ptr(), need.value, n, hidden,
+                                                           w.shape[0], p, _stream(g)))
+    return gx, gw, colsum
 
 
 def act_then_linear(x, act_fn, dropout, lin, want_train=True, want_eval=False):
@@ -675,6 +666,23 @@ def act_then_linear(x, act_fn, dropout, lin, want_train=True, want_eval=False):
     return z_tr, z_ev
 
 
+def _act_then_linear_pair(o_train, o_eval, act_fn, dropout, lin, eval_grad=False):
+    """``act_then_linear`` for the training and the evaluation operand of one layer (None: not wanted), which call for which:
+    ONE pass for both exactly when the evaluation operand is the detached training tensor (the first hidden layer); from
+    the second hidden layer on the two differ (dropout), so training first, then evaluation.  ``eval_grad`` (an evaluation
+    operand that may carry a gradient — not on the training path): the stock modules when it does."""
+    if o_train is not None and o_eval is not None and o_eval.data_ptr() == o_train.data_ptr():
+        return act_then_linear(o_train, act_fn, dropout, lin, want_train=True, want_eval=True)
+    z_train = z_eval = None
+    if o_train is not None:
+        z_train, _ = act_then_linear(o_train, act_fn, dropout, lin, want_train=True, want_eval=False)
+    if o_eval is not None and eval_grad and torch.is_grad_enabled() and o_eval.requires_grad:
+        z_eval = lin(dropout(act_fn(o_eval)))
+    elif o_eval is not None:
+        _, z_eval = act_then_linear(o_eval, act_fn, dropout, lin, want_train=False, want_eval=True)
+    return z_train, z_eval
+
+
 class _DropoutAhead:
     """The dropout decisions of the NEXT training call of the one-kernel first layer, drawn on a side stream while the rest of
     the current epoch runs (dcr_dropout_words_dev; round 5).  The Philox instructions of the decisions were most of the vector
@@ -688,7 +696,6 @@ class _DropoutAhead:
     ends), or at the next forward."""
 
     def __init__(self, device, n, hidden, p):
-        from dcr import _lib
         words = ctypes.c_int64()
         _lib.check(_lib.lib().dcr_dropout_words_count(n, hidden, ctypes.byref(words)))
         self.words = torch.zeros(words.value, dtype=torch.int64, device=device)   # (stamp of no call: rows = 0)
@@ -698,7 +705,6 @@ class _DropoutAhead:
         self.forked = False
 
     def draw(self):
-        from dcr import _lib
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         _lib.check(_lib.lib().dcr_dropout_words_dev(self.words.data_ptr(), self.n, self.hidden, self.p,
@@ -751,7 +757,6 @@ class _FirstLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ax, w1, b1, w2, p, want_train, want_eval):
-        from dcr import _lib
         w1, w2 = w1.contiguous(), w2.contiguous()
         # ax: Â·X, [n, feats] or (round 5) [n, feats rounded up to 16] with zero pad columns — what the K-chunked kernel for
         # input widths like Cora's 1,433 and Citeseer's 3,703 reads (GCNConv.propagated_input(..., pad16=True))
@@ -762,33 +767,20 @@ class _FirstLayerFn(torch.autograd.Function):
         f16 = (feats + 15) // 16 * 16
         if ax.shape[1] < f16:                      # (a caller that did not pad: pad here, once per call)
             ax = torch.nn.functional.pad(ax, (0, f16 - ax.shape[1]))
-        ldx = ax.stride(0)
-        stream = torch.cuda.current_stream(ax.device).cuda_stream
-        if want_train and want_eval:
-            both = torch.empty((n, 2 * classes), dtype=ax.dtype, device=ax.device)
-            z_tr, z_ev = both[:, :classes], both[:, classes:]
-        else:
-            z_tr = torch.empty((n, classes), dtype=ax.dtype, device=ax.device) if want_train else None
-            z_ev = torch.empty((n, classes), dtype=ax.dtype, device=ax.device) if want_eval else None
-        ldz = 2 * classes if (want_train and want_eval) else classes
+        stream = _stream(ax)
+        z_tr, z_ev, ldz = _train_eval_outputs(n, classes, want_train, want_eval, ax)
         bits = ctr = pre = None
         if want_train:
-            words = ctypes.c_int64()
-            _lib.check(_lib.lib().dcr_relu_dropout_bits_words(n * hidden, ctypes.byref(words)))
-            bits = torch.empty(max(words.value, 1), dtype=torch.int64, device=ax.device)
-            ctr = _dropout_counter(ax.device)
+            bits, ctr = _dropout_bits(n * hidden, ax.device)
             pre = torch.empty((n, hidden), dtype=ax.dtype, device=ax.device)
         ws = _first_layer_workspace(ax.device, stream, n, feats, hidden)
         ahead = _dropout_ahead(ax.device, n, hidden, p) if (want_train and p > 0.0 and n > 0) else None
         if ahead is not None:
             ahead.join()
         _lib.check(_lib.lib().dcr_first_layer_fwd_ws_f32_dev(
-            ax.data_ptr(), ldx, w1.data_ptr(), None if b1 is None else b1.data_ptr(), w2.data_ptr(),
-            None if pre is None else pre.data_ptr(), z_tr.data_ptr() if want_train else None,
-            z_ev.data_ptr() if want_eval else None, ldz, bits.data_ptr() if want_train else None,
+            ax.data_ptr(), ax.stride(0), w1.data_ptr(), _ptr(b1), w2.data_ptr(), _ptr(pre), _ptr(z_tr), _ptr(z_ev), ldz, _ptr(bits),
             None if ahead is None else ahead.words.data_ptr(), n, feats, hidden, classes,
-            float(p), torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0, ctr.data_ptr() if want_train else None,
-            None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), ctypes.c_void_p(stream)))
+            float(p), torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, 0, _ptr(ctr), _ptr(ws), 0 if ws is None else ws.numel(), stream))
         ctx.ahead = ahead
         if want_train:
             ctr.add_(1)
@@ -803,7 +795,6 @@ class _FirstLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_tr, g_ev):
-        from dcr import _lib
         if ctx.ahead is not None:
             ctx.ahead.join()   # (inside the same capture as the fork, when there is one)
         if g_tr is None:
@@ -811,7 +802,6 @@ class _FirstLayerFn(torch.autograd.Function):
         ax, w2 = ctx.saved_tensors
         pre = ctx.pre
         g_tr = g_tr.contiguous()
-        stream = torch.cuda.current_stream(g_tr.device).cuda_stream
         n, hidden = pre.shape
         aligned = all(t.data_ptr() % 16 == 0 for t in (ax, g_tr, pre, ctx.bits))   # (the kernel's stage copies move 16-byte pieces)
         feats = ctx.feats
@@ -827,20 +817,12 @@ class _FirstLayerFn(torch.autograd.Function):
             _lib.check(_lib.lib().dcr_first_layer_bwd_f32_dev(g_tr.data_ptr(), w2.data_ptr(), ctx.bits.data_ptr(), pre.data_ptr(),
                                                               ax.data_ptr(), ax.stride(0), gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(),
                                                               ws.data_ptr(), need.value, n, feats, hidden, w2.shape[0], ctx.p,
-                                                              ctypes.c_void_p(stream)))
+                                                              _stream(g_tr)))
             return (None, gw1 if ctx.needs_input_grad[1] else None, gb1 if (ctx.has_bias and ctx.needs_input_grad[2]) else None,
                     gw2 if ctx.needs_input_grad[3] else None, None, None, None)
         if ax.shape[1] != feats:
             ax = ax[:, :feats].contiguous()      # (the separate kernels take the unpadded matrix)
-        gx = torch.empty_like(pre)
-        gw2 = torch.empty_like(w2)
-        colsum = torch.empty(hidden, dtype=torch.float32, device=pre.device)
-        need = ctypes.c_int64()
-        _lib.check(_lib.lib().dcr_act_linear_bwd_fused_workspace(n, hidden, ctypes.byref(need)))
-        ws = torch.empty(max(need.value, 1), dtype=torch.float32, device=pre.device)
-        _lib.check(_lib.lib().dcr_act_linear_bwd_fused_f32_dev(g_tr.data_ptr(), w2.data_ptr(), ctx.bits.data_ptr(), pre.data_ptr(),
-                                                               gx.data_ptr(), gw2.data_ptr(), colsum.data_ptr(), ws.data_ptr(),
-                                                               need.value, n, hidden, w2.shape[0], ctx.p, ctypes.c_void_p(stream)))
+        gx, gw2, colsum = _act_linear_backward(g_tr, w2, ctx.bits, pre, ctx.p)
         gw1 = None
         if ctx.needs_input_grad[1]:
             tall = n >= 64 * max(ax.shape[1], hidden)   # (as _LinearFn.backward)
@@ -857,7 +839,6 @@ def first_layer_fused_ok(x, act_fn, first, lin2):
         return False
     if os.environ.get('DCR_FIRST_FUSED', '1') == '0':
         return False
-    from dcr import _lib
     return bool(_lib.lib().dcr_first_layer_fits(int(first.lin.weight.shape[1]), int(first.lin.weight.shape[0]), int(lin2.weight.shape[0])))
 
 
@@ -905,12 +886,7 @@ class _SparseFirstFn(torch.autograd.Function):
             dh = spmm(csr.rowptr_t, csr.col_t, csr.val_t, g, csr.n_cols)
             gw1 = spmm(xs.rowptr_t, xs.col_t, xs.val_t, dh, xs.f).t()    # [H, F] as a view of the [F, H] product
         if ctx.has_bias and ctx.needs_input_grad[1]:
-            ready = getattr(g, '_dcr_colsum', None)         # left there by the kernel that produced this gradient
-            if ready is not None and ready[:2] == (g.data_ptr(), g._version):
-                gb1 = ready[2]
-                _LinearFn.colsum_handoffs += 1
-            else:
-                gb1 = g.sum(0)
+            gb1 = _column_sums(g)
         return gw1, gb1, None, None
 
 
@@ -1096,132 +1072,99 @@ class GCN(torch.nn.Module):
 
     supports_rows = True   # forward(data, rows=...) / forward_pair(data, rows_train=..., rows_eval=...)
 
-    def forward(self, data, rows=None):
-        # models/gcn.py:32-44.  The activation after a layer is computed together with the next layer's lin
-        # (act_then_linear: one pass over the hidden activation where the fused kernel applies).
-        # rows (a boolean node mask or an index tensor): return the log-probabilities of those nodes only, [len, C] in
-        # index order — what ``model(data)[rows]`` holds, value for value; the last aggregation is evaluated at those
-        # rows and nowhere else.
+    def _walk(self, data, want_tr, want_ev, eval_grad, finish):
+        """models/gcn.py:32-44 for the training operand (dropout on, autograd graph attached), the evaluation operand, or both
+        in ONE traversal of the layers: the two differ only in the dropout between the layers, so the first layer's output is
+        computed once (the evaluation operand is its detached copy) and every later aggregation serves both in one sweep of
+        the graph.  The activation after a layer is computed together with the next layer's lin (``_fused_first``,
+        ``_act_then_linear_pair``), each operand on the route it would take alone.  ``eval_grad``: gradients attach to an
+        evaluation operand asked for alone (``forward`` in evaluation mode); otherwise that walk runs under ``torch.no_grad()``.
+        Returns ``finish(conv, csr, z_tr, z_ev)``: the last layer, its Â and the operands of its aggregation (None: not
+        wanted).  A one-layer model's only aggregation is inside its GCNConv: ``finish(None, None, o_tr, o_ev)`` on its outputs."""
         layers = list(self.layers)
-        z_first = self._fused_first(data, self.training, not self.training) if len(layers) > 1 else None
-        if z_first is None:
-            h = layers[0](data.x, data.edge_index, edge_weight=data.edge_attr)
-            if rows is not None and len(layers) == 1:
-                h = h[rows] if rows.dtype == torch.bool else h.index_select(0, rows)
-        for conv in layers[1:]:
-            if z_first is not None:          # first layer, activation and this layer's lin came out of one kernel
-                z, n_nodes = z_first[0 if self.training else 1], z_first[0 if self.training else 1].shape[0]
-                z_first = None
-            else:
-                n_nodes = h.shape[0]
-                if self.training:
-                    z, _ = act_then_linear(h, self.act_fn, self.dropout, conv.lin, want_train=True, want_eval=False)
-                elif torch.is_grad_enabled() and h.requires_grad:
-                    z = conv.lin(self.dropout(self.act_fn(h)))   # evaluation mode WITH a gradient (not on the training path)
+        last = len(layers) - 1
+        z_first = self._fused_first(data, want_tr, want_ev) if last > 0 else None
+        with torch.set_grad_enabled(torch.is_grad_enabled() and (want_tr or eval_grad)):
+            conv = csr = o_tr = o_ev = None
+            if z_first is None:
+                o = layers[0](data.x, data.edge_index, edge_weight=data.edge_attr)
+                o_tr, o_ev = (o if want_tr else None), ((o.detach() if want_tr else o) if want_ev else None)
+            z_tr, z_ev = o_tr, o_ev
+            for depth, conv in enumerate(layers[1:], start=1):
+                if z_first is not None:          # first layer, activation and this layer's lin came out of one kernel
+                    (z_tr, z_ev), z_first = z_first, None
                 else:
-                    _, z = act_then_linear(h, self.act_fn, self.dropout, conv.lin, want_train=False, want_eval=True)
-            csr = conv.norm_csr(data.edge_index, data.edge_attr, n_nodes)
-            if rows is not None and conv is layers[-1]:
-                sel = conv.row_selection(rows, csr)
-                h = sel.expanded(aggregate_rows(z, conv.bias, csr, sel))
+                    z_tr, z_ev = _act_then_linear_pair(o_tr, o_ev, self.act_fn, self.dropout, conv.lin, eval_grad)
+                csr = conv.norm_csr(data.edge_index, data.edge_attr, (z_ev if z_tr is None else z_tr).shape[0])
+                if depth < last:
+                    o_tr, o_ev = _aggregate_wanted(z_tr, z_ev, conv.bias, csr)
+        return finish(conv, csr, z_tr, z_ev)
+
+    @staticmethod
+    def _log_probs(rows_tr, rows_ev):
+        """The finisher of ``forward`` / ``forward_pair``: the last aggregation at every row (no rows given) or at the rows
+        asked for and nowhere else, then log_softmax; (training, evaluation) log-probabilities, None where not wanted."""
+        def pick(t, r):      # (one-layer model)
+            return t if t is None or r is None else t[r] if r.dtype == torch.bool else t.index_select(0, r)
+
+        def finish(conv, csr, z_tr, z_ev):
+            if conv is None:
+                o_tr, o_ev = pick(z_tr, rows_tr), pick(z_ev, rows_ev)
+            elif rows_tr is None and rows_ev is None:
+                o_tr, o_ev = _aggregate_wanted(z_tr, z_ev, conv.bias, csr)
             else:
-                h = aggregate(z, conv.bias, csr)
-        return torch.nn.functional.log_softmax(h, dim=1)
+                sel_tr = None if z_tr is None else conv.row_selection(rows_tr, csr)
+                sel_ev = None if z_ev is None else conv.row_selection(rows_ev, csr)
+                if z_tr is not None and z_ev is not None:
+                    o_tr, o_ev = _AggregateRowsPair.apply(z_tr, z_ev, conv.bias, csr, sel_tr, sel_ev)
+                else:
+                    o_tr = None if z_tr is None else aggregate_rows(z_tr, conv.bias, csr, sel_tr)
+                    o_ev = None if z_ev is None else aggregate_rows(z_ev, conv.bias, csr, sel_ev)
+                o_tr = None if z_tr is None else sel_tr.expanded(o_tr)
+                o_ev = None if z_ev is None else sel_ev.expanded(o_ev)
+            return tuple(None if o is None else torch.nn.functional.log_softmax(o, dim=1) for o in (o_tr, o_ev))
+        return finish
+
+    def forward(self, data, rows=None):
+        # models/gcn.py:32-44.  rows (a boolean node mask or an index tensor): return the log-probabilities of those nodes
+        # only, [len, C] in index order — what ``model(data)[rows]`` holds, value for value; the last aggregation is evaluated
+        # at those rows and nowhere else.
+        if self.training:
+            return self._walk(data, True, False, True, self._log_probs(rows, None))[0]
+        return self._walk(data, False, True, True, self._log_probs(None, rows))[1]
 
     def forward_pair(self, data, rows_train=None, rows_eval=None):
         """(training-mode log-probabilities with their autograd graph, evaluation-mode log-probabilities) of the SAME
         weights in one pass: what ``model.train(); model(data)`` and ``model.eval(); model(data)`` return, value for
-        value.  The two differ only in the dropout between the layers, so the first layer's output is computed once and
-        every later aggregation serves both operands in one sweep of the graph (``spmm_pair``).  The validation forward
-        of one epoch and the training forward of the next see the same weights (experiment/training_loop.py:25-26:
-        train, then evaluate, then train again), which is what ``LaggedGraphedEpoch`` builds on.  Call in training mode.
+        value (``_walk`` with both operands).  The validation forward of one epoch and the training forward of the next see
+        the same weights (experiment/training_loop.py:25-26: train, then evaluate, then train again), which is what
+        ``LaggedGraphedEpoch`` builds on.  Call in training mode.
         ``rows_train`` / ``rows_eval`` (both or neither): only those nodes' rows of the two outputs, as ``forward(data, rows)``."""
         if (rows_train is None) != (rows_eval is None):
             raise ValueError('rows_train and rows_eval go together')
-        last = len(self.layers) - 1
-        first = self.layers[0]
-        z_first = self._fused_first(data, True, True) if last > 0 else None
-        if z_first is None:
-            o_tr = first(data.x, data.edge_index, edge_weight=data.edge_attr)
-            o_ev = o_tr.detach()
-        for depth, conv in enumerate(list(self.layers)[1:], start=1):
-            if z_first is not None:                      # first layer, activation and this layer's lin out of one kernel
-                (z_tr, z_ev), z_first = z_first, None
-            elif o_ev.data_ptr() == o_tr.data_ptr():     # the same pre-activation (first hidden layer): one pass for both
-                z_tr, z_ev = act_then_linear(o_tr, self.act_fn, self.dropout, conv.lin, want_train=True, want_eval=True)
-            else:                                        # (dropout is the identity in evaluation mode)
-                z_tr, _ = act_then_linear(o_tr, self.act_fn, self.dropout, conv.lin, want_train=True, want_eval=False)
-                _, z_ev = act_then_linear(o_ev, self.act_fn, self.dropout, conv.lin, want_train=False, want_eval=True)
-            csr = conv.norm_csr(data.edge_index, data.edge_attr, z_tr.shape[0])
-            if rows_train is not None and depth == last:
-                sel_tr, sel_ev = conv.row_selection(rows_train, csr), conv.row_selection(rows_eval, csr)
-                o_tr, o_ev = _AggregateRowsPair.apply(z_tr, z_ev, conv.bias, csr, sel_tr, sel_ev)
-                o_tr, o_ev = sel_tr.expanded(o_tr), sel_ev.expanded(o_ev)
-            else:
-                o_tr, o_ev = _AggregatePair.apply(z_tr, z_ev, conv.bias, csr)
-        if rows_train is not None and last == 0:
-            pick = lambda t, r: t[r] if r.dtype == torch.bool else t.index_select(0, r)
-            o_tr, o_ev = pick(o_tr, rows_train), pick(o_ev, rows_eval)
-        log_softmax = torch.nn.functional.log_softmax
-        return log_softmax(o_tr, dim=1), log_softmax(o_ev, dim=1)
+        return self._walk(data, True, True, False, self._log_probs(rows_train, rows_eval))
 
-
-def _forward_head(self, data, rows_train=None, y_train=None, rows_eval=None, y_eval=None):
-    """(loss, correct) of one epoch's two readings of the model in ONE pass, without the log-probabilities in between:
-    ``loss = F.nll_loss(model(data)[rows_train], y_train)`` in training mode (dropout on, autograd graph attached) and
-    ``correct = (model(data)[rows_eval].argmax(1) == y_eval).sum()`` in evaluation mode, of the SAME weights (see
-    ``forward_pair``).  Either half may be left out (rows_* = None): the training step alone, or the evaluation alone.
-    Returns None when a shape, a mode or the backend asks for the separate kernels (the caller then takes the log-probabilities
-    from ``forward`` / ``forward_pair``): two or more layers, row index tensors without repeats, at most 32 classes."""
-    want_tr, want_ev = rows_train is not None, rows_eval is not None
-    last = len(self.layers) - 1
-    if last < 1 or not (want_tr or want_ev) or (want_tr and not self.training):
-        return None
-    conv = self.layers[last]
-    first = self.layers[0]
-    # eligibility is decided before anything runs: a forward computed and then dropped would have drawn its dropout decisions
-    # (the caller's stock forward draws again, so the run would differ from DCR_FUSED_HEAD=0) and, in a capture, left dead
-    # kernels in the graph.  The last layer's Â and row selections are the ones its aggregation uses below (cached).
-    csr_last = conv.norm_csr(data.edge_index, data.edge_attr, data.x.shape[0])
-    sel_tr = conv.row_selection(rows_train, csr_last) if want_tr else None
-    sel_ev = conv.row_selection(rows_eval, csr_last) if want_ev else None
-    if data.x.dtype != torch.float32 or not head_ok(conv.lin.weight, sel_tr, sel_ev, conv.out_channels):
-        return None
-    z_first = self._fused_first(data, want_tr, want_ev)
-    if z_first is None:
-        if want_tr:
-            o_tr = first(data.x, data.edge_index, edge_weight=data.edge_attr)
-            o_ev = o_tr.detach()
-        else:
-            with torch.no_grad():
-                o_ev = first(data.x, data.edge_index, edge_weight=data.edge_attr)
-            o_tr = None
-    z_tr = z_ev = None
-    for depth, layer in enumerate(list(self.layers)[1:], start=1):
-        if z_first is not None:
-            (z_tr, z_ev), z_first = z_first, None
-        elif want_tr and want_ev and o_ev.data_ptr() == o_tr.data_ptr():
-            z_tr, z_ev = act_then_linear(o_tr, self.act_fn, self.dropout, layer.lin, want_train=True, want_eval=True)
-        else:
-            z_tr = act_then_linear(o_tr, self.act_fn, self.dropout, layer.lin, want_train=True, want_eval=False)[0] if want_tr else None
-            if want_ev:
-                with torch.no_grad():
-                    z_ev = act_then_linear(o_ev, self.act_fn, self.dropout, layer.lin, want_train=False, want_eval=True)[1]
-        ref = z_tr if want_tr else z_ev
-        csr = layer.norm_csr(data.edge_index, data.edge_attr, ref.shape[0])
-        if depth == last:
-            return _AggregateRowsHead.apply(z_tr, z_ev, layer.bias, csr, sel_tr, sel_ev, y_train, y_eval)
-        if want_tr and want_ev:
-            o_tr, o_ev = _AggregatePair.apply(z_tr, z_ev, layer.bias, csr)
-        elif want_tr:
-            o_tr = aggregate(z_tr, layer.bias, csr)
-        else:
-            with torch.no_grad():
-                o_ev = aggregate(z_ev, layer.bias, csr)
-    return None
-
-
-GCN.forward_head = _forward_head
+    def forward_head(self, data, rows_train=None, y_train=None, rows_eval=None, y_eval=None):
+        """(loss, correct) of one epoch's two readings of the model in ONE pass, without the log-probabilities in between:
+        ``loss = F.nll_loss(model(data)[rows_train], y_train)`` in training mode (dropout on, autograd graph attached) and
+        ``correct = (model(data)[rows_eval].argmax(1) == y_eval).sum()`` in evaluation mode, of the SAME weights (see
+        ``forward_pair``).  Either half may be left out (rows_* = None): the training step alone, or the evaluation alone.
+        Returns None when a shape, a mode or the backend asks for the separate kernels (the caller then takes the log-probabilities
+        from ``forward`` / ``forward_pair``): two or more layers, row index tensors without repeats, at most 32 classes."""
+        want_tr, want_ev = rows_train is not None, rows_eval is not None
+        if len(self.layers) < 2 or not (want_tr or want_ev) or (want_tr and not self.training):
+            return None
+        last = self.layers[-1]
+        # eligibility is decided before anything runs: a forward computed and then dropped would have drawn its dropout decisions
+        # (the caller's stock forward draws again, so the run would differ from DCR_FUSED_HEAD=0) and, in a capture, left dead
+        # kernels in the graph.  The last layer's Â and row selections are the ones its aggregation uses below (cached).
+        csr_last = last.norm_csr(data.edge_index, data.edge_attr, data.x.shape[0])
+        sel_tr = last.row_selection(rows_train, csr_last) if want_tr else None
+        sel_ev = last.row_selection(rows_eval, csr_last) if want_ev else None
+        if data.x.dtype != torch.float32 or not head_ok(last.lin.weight, sel_tr, sel_ev, last.out_channels):
+            return None
+        return self._walk(data, want_tr, want_ev, False, lambda conv, csr, z_tr, z_ev: _AggregateRowsHead.apply(
+            z_tr, z_ev, conv.bias, csr, sel_tr, sel_ev, y_train, y_eval))
 
 
 def dense_reference_logits(model, x, edge_index, num_nodes):

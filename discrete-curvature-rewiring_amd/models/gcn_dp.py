@@ -23,8 +23,8 @@ import os
 import torch
 import torch.distributed as dist
 
-from models.gcn import (GCN, RowSelection, _FirstLayerFn, first_layer_fused_ok, act_then_linear, aggregate, aggregate_rows, gcn_norm_csr, relu_dropout, spmm, spmm_pair,
-                        spmm_rows)
+from models.gcn import (GCN, RowSelection, _FirstLayerFn, _act_then_linear_pair, first_layer_fused_ok, aggregate, aggregate_rows, gcn_norm_csr, relu_dropout, spmm,
+                        spmm_pair, spmm_rows)
 
 
 def block_range(n, world, rank):
@@ -270,11 +270,8 @@ class ShardedGCN(torch.nn.Module):
         for layer in layers[1:]:
             if z_first is not None:
                 (z_tr, z_ev), z_first = z_first, None
-            elif o_ev.data_ptr() == o_tr.data_ptr():
-                z_tr, z_ev = act_then_linear(o_tr, self.gcn.act_fn, self.gcn.dropout, layer.lin, want_train=True, want_eval=True)
             else:
-                z_tr, _ = act_then_linear(o_tr, self.gcn.act_fn, self.gcn.dropout, layer.lin, want_train=True, want_eval=False)
-                _, z_ev = act_then_linear(o_ev, self.gcn.act_fn, self.gcn.dropout, layer.lin, want_train=False, want_eval=True)
+                z_tr, z_ev = _act_then_linear_pair(o_tr, o_ev, self.gcn.act_fn, self.gcn.dropout, layer.lin)
             if rows_train is not None and layer is layers[-1]:
                 o_tr, o_ev = _GatherAggregatePair.apply(z_tr, z_ev, layer.bias, self.csr, self.n, self.per, self.group,
                                                         rows_train, rows_eval)
