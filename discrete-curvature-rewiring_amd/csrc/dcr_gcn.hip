@@ -290,7 +290,8 @@ extern "C" int dcr_spmm_csr_rows2_f32_dev(const int64_t *rowptr, const int32_t *
 // activations in each direction, with the keep mask packed to one bit per element: forward reads x, writes y and the
 // bits (N*F/8 bytes); backward reads the gradient and the bits.  The stock path is four element-wise kernels and a
 // byte mask (4.9 GB of traffic per training step at 1M x 128; this is 2.1 GB).  Random numbers: Philox-4x32-10 keyed by
-// (seed, call offset), counter = element-quad index, so a run is reproducible for a given torch seed.
+// (seed, call offset), counter = element-quad index >> 1 (two quads share a call: dcr_philox.h, philox_quad16; the rule is
+// written out in include/dcr.h), so a run is reproducible for a given torch seed.
 namespace dcr {
 
 // thread t owns elements 4t .. 4t+3; wave w stores the four keep-ballots of its 256 elements in bits[4w .. 4w+3]

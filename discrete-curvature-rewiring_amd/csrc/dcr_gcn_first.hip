@@ -606,15 +606,19 @@ __global__ void __launch_bounds__(256) k_dropout_words(unsigned long long *__res
                 m[q] |= ((r[q] >> 16) >= threshold ? 1u : 0u) << (2 * k + 1);
             }
         }
-        // the row's LPR-bit field of the four 64-bit words of its group of RPW rows (little-endian halves / quarters of a word)
+        // the row's LPR-bit field of the four 64-bit words of its group of RPW rows (little-endian halves / quarters of a word);
+        // the last row also clears the fields of its group's rows past the end: bits of no element are 0, as in `bits`
+        const int f0 = (int)(row % RPW), f1 = row == n_rows - 1 ? RPW : f0 + 1;
         if (LPR == 32) {
-            uint32_t *dst = reinterpret_cast<uint32_t *>(dwords + (row / RPW) * 4) + (row % RPW);
+            uint32_t *dst = reinterpret_cast<uint32_t *>(dwords + (row / RPW) * 4);
+            for (int f = f0; f < f1; ++f)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) dst[2 * q] = m[q];
+                for (int q = 0; q < 4; ++q) dst[2 * q + f] = f == f0 ? m[q] : 0u;
         } else {
-            uint16_t *dst = reinterpret_cast<uint16_t *>(dwords + (row / RPW) * 4) + (row % RPW);
+            uint16_t *dst = reinterpret_cast<uint16_t *>(dwords + (row / RPW) * 4);
+            for (int f = f0; f < f1; ++f)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) dst[4 * q] = (uint16_t)m[q];
+                for (int q = 0; q < 4; ++q) dst[4 * q + f] = f == f0 ? (uint16_t)m[q] : (uint16_t)0;
         }
     }
 }

@@ -267,7 +267,23 @@ int dcr_atb_f32_dev(const float *A_dev, const float *B_dev, float *C_dev, int64_
  * models/gcn.py:38-42 (x = act_fn(x); x = dropout(x)) as one pass per direction: y = x > 0 and kept ? x / (1 - p) : 0,
  * the keep decisions packed one bit per element into `bits` (dcr_relu_dropout_bits_words(n) 64-bit words); backward
  * scales the incoming gradient by the same bits.  Philox-4x32-10 keyed by (seed, offset): reproducible for a seed.
- * Sixteen random bits per element: an element is kept with probability 1 - floor(p * 65536) / 65536 (exact at p = 0.5). */
+ * Sixteen random bits per element: an element is kept with probability 1 - floor(p * 65536) / 65536 (exact at p = 0.5).
+ *
+ * The stream, for every kernel of this section and the next (tests/dropout_ref.py restates it; tests/test_dropout_stream_gpu.py
+ * compares every bit).  For a tensor of n elements in row-major order, element e = 4t + j (quad t, j in 0..3), with
+ * o = offset + *offset_dev as a 64-bit sum (offset alone where there is no offset_dev):
+ *     r        = Philox-4x32-10(counter = {lo32(t >> 1), hi32(t >> 1), lo32(o), hi32(o)}, key = {lo32(seed), hi32(seed)})
+ *     draw     = (r[j] >> 16 * (t & 1)) & 0xFFFF
+ *     decision = draw >= min(floor(p * 65536), 65535)
+ *     keep     = decision && x[e] > 0
+ *     y[e]     = keep ? x[e] * float32(1 / (1 - p)) : 0
+ *     bit t & 63 of word 4 * (t >> 6) + j of `bits` is keep
+ *     bits that belong to no element are 0 in every word a forward kernel writes
+ * For a row-structured [n_rows x H] activation this is the same rule with t = row * H/4 + col/4 and j = col % 4 (RPW = 256 / H
+ * rows share four words; a forward kernel writes the ceil(n_rows / RPW) * 4 words its rows reach, dcr_relu_dropout_fwd all
+ * dcr_relu_dropout_bits_words(n) of them).  dcr_dropout_words_dev writes `decision` without the sign test in the same places,
+ * then the four-word stamp {o, seed, threshold, n_rows} at word ceil(n_rows / RPW) * 4.  The backward kernels read `bits` by
+ * this layout alone: any mask packed this way is theirs to apply. */
 int dcr_relu_dropout_bits_words(int64_t n, int64_t *out_words);
 int dcr_relu_dropout_fwd_f32_dev(const float *x_dev, float *y_dev, uint64_t *bits_dev, int64_t n, double p, uint64_t seed,
                                  uint64_t offset, void *hip_stream);
