@@ -330,6 +330,24 @@ struct dcr_graph {
     double *chg_values = nullptr;
     int64_t chg_values_cap = 0;
 
+    // spectral gap and connected components (dcr_spectral.hip), grown on demand
+    int32_t *spc_label = nullptr;   // [n] smallest node id of the node's component
+    int64_t spc_label_cap = 0;
+    unsigned *spc_ctl = nullptr;    // {a sweep of the components changed a label, reduction ticket, -, -}
+    int64_t spc_ctl_cap = 0;
+    double *spc_vec = nullptr;      // [4][n]: scale s, null-space weights k, z = s ⊙ v of the newest column, work vector w
+    int64_t spc_vec_cap = 0;
+    double *spc_basis = nullptr;    // [columns][n] Lanczos basis
+    int64_t spc_basis_cap = 0;
+    int32_t *spc_rows = nullptr;    // [2][n]: rows by degree class (long, medium, short), nodes by component
+    int64_t spc_rows_cap = 0;
+    int4 *spc_chunks = nullptr;     // deflation chunks
+    int64_t spc_chunks_cap = 0;
+    double *spc_part = nullptr;     // per-workgroup (per-wave) partial sums
+    int64_t spc_part_cap = 0;
+    double *spc_small = nullptr;    // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
+    int64_t spc_small_cap = 0;
+
     dcr::DevResult *dres = nullptr;  // device
     dcr::DevResult *hres = nullptr;  // pinned host
 

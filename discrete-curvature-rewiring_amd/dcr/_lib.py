@@ -20,6 +20,18 @@ _i32p = ctypes.POINTER(_i32)
 _i64p = ctypes.POINTER(_i64)
 _f64p = ctypes.POINTER(_f64)
 
+
+class SpectralOpts(ctypes.Structure):
+    """dcr_spectral_opts of include/dcr.h."""
+    _fields_ = [('tol', _f64), ('max_steps', _i64), ('max_basis', _i64), ('seed', ctypes.c_uint64)]
+
+
+class SpectralResult(ctypes.Structure):
+    """dcr_spectral_result of include/dcr.h."""
+    _fields_ = [('lambda1', _f64), ('residual', _f64), ('steps', _i64), ('restarts', _i64), ('components', _i64),
+                ('converged', ctypes.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -60,6 +72,8 @@ SIGNATURES = {
     'dcr_cheeger_philox_counts': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, _i64p]),
     'dcr_cheeger_philox_values': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, ctypes.c_int, _f64p]),
     'dcr_cheeger_philox_members': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, _vp]),
+    'dcr_connected_components': (ctypes.c_int, [_vp, _i32p, _i64p]),
+    'dcr_spectral_gap': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.POINTER(SpectralResult), _f64p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -2,6 +2,8 @@
 ``networkx.Graph`` the reference's curvature / SDRF code uses
 (rewiring/sdrf_no_cuda.py:20-68, curvature/bfc_naive.py:7-52)."""
 import ctypes
+import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -29,6 +31,10 @@ def _as_numpy_edge_index(edge_index):
 
 
 CHEEGER_DEFINITIONS = {'reference': 0, 'conductance': 1}
+
+# what DcrGraph.spectral_gap returns; ``vector`` is None unless it was asked for
+SpectralGap = namedtuple('SpectralGap', ['lambda1', 'residual', 'steps', 'restarts', 'components', 'converged', 'vector'],
+                         defaults=[None])
 
 
 def pack_members(members, num_nodes):
@@ -314,6 +320,30 @@ class DcrGraph:
         out = np.empty((self.num_nodes, max(int(words), 0)), dtype=np.uint64)
         check(lib().dcr_cheeger_philox_members(self._h, int(seed), int(first), int(words), out.ctypes.data))
         return out
+
+    # ---- spectral gap (experiment/cheeger_bounds.py) -------------------------------------------------------------------
+    def connected_components(self):
+        """(count, labels int32 ``[n]``): the label of a node is the smallest node id of its component; an isolated node is
+        a component.  Computed on the device over the live adjacency."""
+        labels = np.empty(self.num_nodes, dtype=np.int32)
+        count = ctypes.c_int64()
+        check(lib().dcr_connected_components(self._h, labels.ctypes.data_as(_lib._i32p), ctypes.byref(count)))
+        return count.value, labels
+
+    def spectral_gap(self, tol=1e-10, max_steps=20000, max_basis=None, seed=0, return_vector=False):
+        """The smallest eigenvalue of the normalised Laplacian above its null space (cheeger_bounds.py:13-16 as it is meant:
+        the (c+1)-th smallest with c components), by deflated Lanczos on the device (csrc/dcr_spectral.hip).  Returns a
+        ``SpectralGap``; ``converged`` says that the true residual of the returned pair is <= ``tol`` (a ``RuntimeWarning``
+        when it is not).  ``ValueError`` on a graph without edges.  ``vector``: the unit eigenvector in node order."""
+        opts = _lib.SpectralOpts(float(tol), int(max_steps), 0 if max_basis is None else int(max_basis), int(seed))
+        res = _lib.SpectralResult()
+        vec = np.empty(self.num_nodes, dtype=np.float64) if return_vector else None
+        check(lib().dcr_spectral_gap(self._h, ctypes.byref(opts), ctypes.byref(res),
+                                     vec.ctypes.data_as(_lib._f64p) if return_vector else None))
+        if not res.converged:
+            warnings.warn(f'spectral_gap: residual {res.residual:.3e} above tol {float(tol):.3e} after {res.steps} steps',
+                          RuntimeWarning, stacklevel=2)
+        return SpectralGap(res.lambda1, res.residual, res.steps, res.restarts, res.components, bool(res.converged), vec)
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

@@ -187,6 +187,35 @@ int dcr_cheeger_philox_counts(dcr_graph *g, uint64_t seed, int64_t first, int64_
 int dcr_cheeger_philox_values(dcr_graph *g, uint64_t seed, int64_t first, int64_t B, int definition, double *out_values);
 int dcr_cheeger_philox_members(dcr_graph *g, uint64_t seed, int64_t first, int64_t W, uint64_t *out_members);
 
+/* ---- spectral gap and Cheeger bounds: experiment/cheeger_bounds.py:11-21 ------------------------------------------------
+ * The reference brackets the Cheeger constant by lambda_1 / 2 <= h <= sqrt(2 lambda_1), lambda_1 the smallest eigenvalue of
+ * the normalised Laplacian L = I - D^-1/2 A D^-1/2 above its null space (:13-19, from a dense eigh).  With c connected
+ * components (an isolated node is one; its row of L is zero, as networkx has it) the null space of L has dimension exactly
+ * c, so lambda_1 is the (c+1)-th smallest eigenvalue.  The calls below compute c and lambda_1 on the live graph
+ * (csrc/dcr_spectral.hip: Lanczos with full reorthogonalisation on I + D^-1/2 A D^-1/2 with the null space deflated in
+ * closed form); both are read-only on the graph and leave the curvature buffer alone.  All arithmetic is fp64 and every
+ * reduction has a fixed order: the same seed on the same graph returns the same bits.
+ *   dcr_connected_components  out_labels: host int32 [num_nodes], the smallest node id of each node's component; out_count: c
+ *   dcr_spectral_gap          opts NULL = defaults: tol 1e-10, max_steps 20000, max_basis 0 = min of 256 columns and
+ *                             4 GiB / 8 num_nodes, at least 16; seed 0: the start vector is Philox-4x32-10 of counter
+ *                             {node, restart} under key seed, csrc/dcr_philox.h.
+ *                             out->converged: the TRUE residual |L y - lambda_1 y|_2 of the returned unit vector, recomputed
+ *                             with a mat-vec of its own, is <= tol; out->residual is that norm.  steps counts mat-vecs and
+ *                             never exceeds max_steps; when they run out the call still returns DCR_OK, with converged = 0
+ *                             and the last checked value, which is never below the true lambda_1.
+ *                             out_vector, host double [num_nodes] or NULL: that eigenvector of L in node order, the Fiedler
+ *                             vector in D^1/2 scaling.
+ *                             max_basis 1 is taken as 2 (one column could only restart from itself).  The basis, max_basis
+ *                             x num_nodes doubles, is allocated for the call and freed before it returns; O(num_nodes)
+ *                             work buffers stay on the handle until dcr_graph_destroy.
+ * A graph without edges has no positive eigenvalue: DCR_EINVAL, where the reference raises IndexError.  Null g or out, tol
+ * negative or NaN, max_steps < 1, max_basis < 0: DCR_EINVAL. */
+typedef struct { double tol; int64_t max_steps; int64_t max_basis; uint64_t seed; } dcr_spectral_opts;
+typedef struct { double lambda1, residual; int64_t steps, restarts, components; int converged; } dcr_spectral_result;
+int dcr_connected_components(dcr_graph *g, int32_t *out_labels /* host [n] */, int64_t *out_count);
+int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts /* NULL = defaults */,
+                     dcr_spectral_result *out, double *out_vector /* host [n] or NULL */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
