@@ -348,6 +348,18 @@ struct dcr_graph {
     double *spc_small = nullptr;    // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
     int64_t spc_small_cap = 0;
 
+    // sweep cut (dcr_sweep.hip), grown on demand: all O(n)
+    uint64_t *swp_keys = nullptr;   // [2][n] sort keys, ping and pong
+    int64_t swp_keys_cap = 0;
+    int32_t *swp_idx = nullptr;     // [7][n]: node ids ping and pong, rank, the three difference arrays (in, lo, hi), rows by degree class
+    int64_t swp_idx_cap = 0;
+    int32_t *swp_table = nullptr;   // [256][tiles] digit counts of a sort pass, then the scans' per-block sums and offsets
+    int64_t swp_table_cap = 0;
+    double *swp_f64 = nullptr;      // [2][n]: the score, the profile
+    int64_t swp_f64_cap = 0;
+    unsigned *swp_ctl = nullptr;    // tickets, NaN flag, the [8][256] digit histogram of the keys, the result block, arg-min partials
+    int64_t swp_ctl_cap = 0;
+
     dcr::DevResult *dres = nullptr;  // device
     dcr::DevResult *hres = nullptr;  // pinned host
 
@@ -404,6 +416,20 @@ int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental);
 bool h2_can_take(const dcr_graph *g, int curv_type, bool incremental);
 int launch_curvature_pass_h2(dcr_graph *g);
 bool h2_grow_pools(dcr_graph *g);
+
+// dcr_spectral.hip
+struct RowClasses {
+    int n_long, n_mid, n_short;
+};
+// rows by degree class as k_spec_matvec takes them: above 2,048 a workgroup a row, above 32 a wave a row, the rest eight lanes a row
+void classify_rows(const std::vector<int2> &info, std::vector<int32_t> &rows, RowClasses *rc);
+struct SpectralKept {  // what spectral_solve leaves in device memory: the unit Ritz vector y, the scale s = 1 / sqrt(deg), the row list
+    const double *y, *s;
+    const int32_t *rows;
+    RowClasses rc;
+};
+int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept);
+void spectral_release_basis(dcr_graph *g);  // synchronises the stream and frees the Lanczos basis (y with it)
 
 template <typename T>
 int dev_alloc(T **p, int64_t count) {

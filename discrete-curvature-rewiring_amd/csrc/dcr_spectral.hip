@@ -403,6 +403,32 @@ static int spectral_components(dcr_graph *g, std::vector<int32_t> &labels) {
     return DCR_OK;
 }
 
+// rows: the long rows (degree above SP_LONG_DEG), then the medium ones, then the short ones (up to SP_SHORT_DEG), each by node id
+void classify_rows(const std::vector<int2> &info, std::vector<int32_t> &rows, RowClasses *rc) {
+    const int64_t n = (int64_t)info.size();
+    rows.resize((size_t)n);
+    int64_t nl = 0, nm = 0, ns = 0;
+    for (int64_t v = 0; v < n; ++v) {
+        const int d = info[(size_t)v].y;
+        (d > SP_LONG_DEG ? nl : d > SP_SHORT_DEG ? nm : ns)++;
+    }
+    int64_t pl = 0, pm = nl, ps = nl + nm;
+    for (int64_t v = 0; v < n; ++v) {
+        const int d = info[(size_t)v].y;
+        rows[(size_t)(d > SP_LONG_DEG ? pl : d > SP_SHORT_DEG ? pm : ps)++] = (int32_t)v;
+    }
+    rc->n_long = (int)nl;
+    rc->n_mid = (int)nm;
+    rc->n_short = (int)ns;
+}
+
+void spectral_release_basis(dcr_graph *g) {
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    if (g->spc_basis) (void)hipFree(g->spc_basis);
+    g->spc_basis = nullptr;
+    g->spc_basis_cap = 0;
+}
+
 struct SpecRun {
     dcr_graph *g;
     int64_t n;
@@ -458,27 +484,9 @@ struct SpecRun {
     }
 };
 
-}  // namespace dcr
-
-using namespace dcr;
-
-extern "C" {
-
-int dcr_connected_components(dcr_graph *g, int32_t *out_labels, int64_t *out_count) {
-    if (!g || !out_labels || !out_count) DCR_FAIL(DCR_EINVAL, "null argument");
-    DCR_HIP(hipSetDevice(g->device));
-    std::vector<int32_t> labels;
-    DCR_TRY(spectral_components(g, labels));
-    int64_t c = 0;
-    for (int64_t v = 0; v < g->n; ++v) {
-        out_labels[v] = labels[(size_t)v];
-        c += labels[(size_t)v] == v;
-    }
-    *out_count = c;
-    return DCR_OK;
-}
-
-int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, double *out_vector) {
+// The whole of dcr_spectral_gap but for the download of the vector: the accepted Ritz vector stays in column 0 of the basis, which
+// stays allocated until spectral_release_basis.
+int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept) {
     if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
     dcr_spectral_opts o = {1e-10, 20000, 0, 0};
     if (opts) o = *opts;
@@ -539,25 +547,15 @@ int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_r
     }
     R.n_chunks = (int)chunks.size();
     // rows by degree class
-    std::vector<int32_t> rows((size_t)n);
-    {
-        int64_t nl = 0, nm = 0, ns = 0;
-        for (int64_t v = 0; v < n; ++v) {
-            const int d = info[(size_t)v].y;
-            (d > SP_LONG_DEG ? nl : d > SP_SHORT_DEG ? nm : ns)++;
-        }
-        int64_t pl = 0, pm = nl, ps = nl + nm;
-        for (int64_t v = 0; v < n; ++v) {
-            const int d = info[(size_t)v].y;
-            rows[(size_t)(d > SP_LONG_DEG ? pl : d > SP_SHORT_DEG ? pm : ps)++] = (int32_t)v;
-        }
-        R.n_long = (int)nl;
-        R.n_mid = (int)nm;
-        R.n_short = (int)ns;
-        R.nb_long = (int)nl;
-        R.nb_mid = (int)((nm + 3) / 4);
-        R.nb_mv = R.nb_long + R.nb_mid + (int)((ns + 31) / 32);
-    }
+    std::vector<int32_t> rows;
+    RowClasses rc;
+    classify_rows(info, rows, &rc);
+    R.n_long = rc.n_long;
+    R.n_mid = rc.n_mid;
+    R.n_short = rc.n_short;
+    R.nb_long = rc.n_long;
+    R.nb_mid = (rc.n_mid + 3) / 4;
+    R.nb_mv = R.nb_long + R.nb_mid + (rc.n_short + 31) / 32;
     // basis capacity
     const int64_t by_memory = ((int64_t)4 << 30) / (8 * n);
     int64_t m = o.max_basis > 0 ? std::min(o.max_basis, std::max<int64_t>(by_memory, 16)) : std::max<int64_t>(std::min<int64_t>(256, by_memory), 16);
@@ -647,15 +645,11 @@ int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_r
             break;
         }
     }
-    if (out_vector) {
-        DCR_HIP(hipMemcpyAsync(out_vector, R.col(0), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-        DCR_HIP(hipStreamSynchronize(g->stream));
-    }
-    // an occasional analysis call: the basis (up to 4 GiB) does not stay on the handle; the O(n) buffers do
     DCR_HIP(hipStreamSynchronize(g->stream));
-    (void)hipFree(g->spc_basis);
-    g->spc_basis = nullptr;
-    g->spc_basis_cap = 0;
+    kept->y = R.col(0);
+    kept->s = R.s;
+    kept->rows = R.rows;
+    kept->rc = rc;
     out->lambda1 = 2.0 - theta;
     out->residual = residual;
     out->steps = total;
@@ -663,6 +657,42 @@ int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_r
     out->components = components;
     out->converged = converged ? 1 : 0;
     return DCR_OK;
+}
+
+}  // namespace dcr
+
+using namespace dcr;
+
+extern "C" {
+
+int dcr_connected_components(dcr_graph *g, int32_t *out_labels, int64_t *out_count) {
+    if (!g || !out_labels || !out_count) DCR_FAIL(DCR_EINVAL, "null argument");
+    DCR_HIP(hipSetDevice(g->device));
+    std::vector<int32_t> labels;
+    DCR_TRY(spectral_components(g, labels));
+    int64_t c = 0;
+    for (int64_t v = 0; v < g->n; ++v) {
+        out_labels[v] = labels[(size_t)v];
+        c += labels[(size_t)v] == v;
+    }
+    *out_count = c;
+    return DCR_OK;
+}
+
+int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, double *out_vector) {
+    SpectralKept kept;
+    int rc = spectral_solve(g, opts, out, &kept);
+    if (rc == DCR_OK && out_vector) {
+        hipError_t e = hipMemcpyAsync(out_vector, kept.y, sizeof(double) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+        if (e != hipSuccess) {
+            set_error(std::string("spectral gap: the vector did not come back: ") + hipGetErrorString(e));
+            rc = DCR_EHIP;
+        }
+    }
+    // an occasional analysis call: the basis (up to 4 GiB) does not stay on the handle; the O(n) buffers do
+    if (g) spectral_release_basis(g);
+    return rc;
 }
 
 }  // extern "C"

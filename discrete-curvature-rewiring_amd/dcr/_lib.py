@@ -32,6 +32,11 @@ class SpectralResult(ctypes.Structure):
                 ('converged', ctypes.c_int)]
 
 
+class SweepResult(ctypes.Structure):
+    """dcr_sweep_result of include/dcr.h (``size`` is the best k)."""
+    _fields_ = [('value', _f64), ('size', _i64), ('n_in', _i64), ('n_lo', _i64), ('n_hi', _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -74,6 +79,9 @@ SIGNATURES = {
     'dcr_cheeger_philox_members': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _i64, _vp]),
     'dcr_connected_components': (ctypes.c_int, [_vp, _i32p, _i64p]),
     'dcr_spectral_gap': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.POINTER(SpectralResult), _f64p]),
+    'dcr_sweep_cut': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, ctypes.POINTER(SweepResult), _i32p, _f64p]),
+    'dcr_fiedler_sweep': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.c_int, ctypes.POINTER(SpectralResult),
+                                         ctypes.POINTER(SweepResult), _i32p, _f64p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -36,6 +36,10 @@ CHEEGER_DEFINITIONS = {'reference': 0, 'conductance': 1}
 SpectralGap = namedtuple('SpectralGap', ['lambda1', 'residual', 'steps', 'restarts', 'components', 'converged', 'vector'],
                          defaults=[None])
 
+# what DcrGraph.sweep_cut returns: the best prefix S_size of the order, its value, counts = int64 [4] (in, lo, hi, out);
+# ``order`` / ``profile`` are None unless asked for
+SweepCut = namedtuple('SweepCut', ['value', 'size', 'counts', 'order', 'profile'])
+
 
 def pack_members(members, num_nodes):
     """(uint64 words [n, W], number of subsets) from bool ``[B, n]`` or from the packed words themselves."""
@@ -344,6 +348,46 @@ class DcrGraph:
             warnings.warn(f'spectral_gap: residual {res.residual:.3e} above tol {float(tol):.3e} after {res.steps} steps',
                           RuntimeWarning, stacklevel=2)
         return SpectralGap(res.lambda1, res.residual, res.steps, res.restarts, res.components, bool(res.converged), vec)
+
+    # ---- sweep cut (csrc/dcr_sweep.hip) ----------------------------------------------------------------------------------
+    def _sweep_result(self, res, order, profile):
+        counts3 = np.array([[res.n_in, res.n_lo, res.n_hi]], dtype=np.int64)
+        return SweepCut(res.value, int(res.size), _with_outside(counts3, self.number_of_edges())[0], order, profile)
+
+    def sweep_cut(self, score, definition='conductance', return_order=True, return_profile=False):
+        """The best prefix of the nodes ordered ascending by ``(score, node id)`` (``-0.0 == +0.0``; ``np.lexsort((ids,
+        np.where(score == 0, 0.0, score)))``): S_k = the first k nodes, k = 1 .. n - 1, valued by ``definition`` as in
+        ``cheeger_philox_values``; the smallest value and the smallest k that has it.  Sorted, counted and minimised on the
+        device over the live adjacency, read-only on the graph.  Returns a ``SweepCut``; ``order`` int32 ``[n]`` (the node at
+        each position), ``profile`` float64 ``[n - 1]`` (the value of every prefix).  ``ValueError`` on a NaN, a score of
+        the wrong length or fewer than two nodes."""
+        x = np.ascontiguousarray(np.asarray(score, dtype=np.float64))
+        if x.ndim != 1 or x.shape[0] != self.num_nodes:
+            raise ValueError(f'score must have shape [{self.num_nodes}]')
+        res = _lib.SweepResult()
+        order = np.empty(self.num_nodes, dtype=np.int32) if return_order else None
+        profile = np.empty(max(self.num_nodes - 1, 0), dtype=np.float64) if return_profile else None
+        check(lib().dcr_sweep_cut(self._h, x.ctypes.data_as(_lib._f64p), CHEEGER_DEFINITIONS[definition], ctypes.byref(res),
+                                  order.ctypes.data_as(_lib._i32p) if return_order else None,
+                                  profile.ctypes.data_as(_lib._f64p) if return_profile else None))
+        return self._sweep_result(res, order, profile)
+
+    def fiedler_sweep(self, definition='conductance', tol=1e-10, max_steps=20000, max_basis=None, seed=0):
+        """``spectral_gap`` and the sweep of its eigenvector in D^-1/2 scaling in one call, the vector never leaving the device:
+        ``(SpectralGap, SweepCut, score)``, ``score`` float64 ``[n]`` the numbers that were ordered.  With ``'conductance'``
+        ``lambda1 / 2 <= h <= SweepCut.value <= sqrt(2 lambda1)``: the set ``order[:size]`` certifies the upper bound.  The
+        same ``RuntimeWarning`` as ``spectral_gap`` when the solver did not converge."""
+        opts = _lib.SpectralOpts(float(tol), int(max_steps), 0 if max_basis is None else int(max_basis), int(seed))
+        gap, res = _lib.SpectralResult(), _lib.SweepResult()
+        order = np.empty(self.num_nodes, dtype=np.int32)
+        score = np.empty(self.num_nodes, dtype=np.float64)
+        check(lib().dcr_fiedler_sweep(self._h, ctypes.byref(opts), CHEEGER_DEFINITIONS[definition], ctypes.byref(gap),
+                                      ctypes.byref(res), order.ctypes.data_as(_lib._i32p), score.ctypes.data_as(_lib._f64p)))
+        if not gap.converged:
+            warnings.warn(f'fiedler_sweep: residual {gap.residual:.3e} above tol {float(tol):.3e} after {gap.steps} steps',
+                          RuntimeWarning, stacklevel=2)
+        return (SpectralGap(gap.lambda1, gap.residual, gap.steps, gap.restarts, gap.components, bool(gap.converged), None),
+                self._sweep_result(res, order, None), score)
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

@@ -20,6 +20,12 @@ noise values come out <= 0 the strings are the reference's own (``tests/golden/c
 of its graphs which case it is, ``reference_sound``).  A graph without edges has no positive eigenvalue: ``ValueError`` here,
 ``IndexError`` in the reference.
 
+``cheeger_sweep(data)`` is the certificate for that bracket, and has no counterpart in the reference.  The bracket is two numbers; the
+constructive half of Cheeger's inequality gives a set: order the nodes by the eigenvector of lambda_1 in D^-1/2 scaling, take the
+prefix of that order with the smallest conductance, and ``lambda_1 / 2 <= h <= conductance <= sqrt(2 lambda_1)``.  Eigenvector,
+sort, edge counts of every prefix and the arg-min stay on the device (``DcrGraph.fiedler_sweep``, csrc/dcr_sweep.hip); neither the
+vector nor the edge list comes back to the host.
+
 No dataset loop and no pickles here: the reference's ``__main__`` (:24-39) reads edge lists saved by earlier runs.
 """
 import math
@@ -50,3 +56,30 @@ def format_bounds(left, right):
 def cheeger_bounds(data):
     left, right, _ = cheeger_bounds_values(data)
     return format_bounds(left, right)
+
+
+def cheeger_sweep(data, definition='conductance', **solver):
+    """``(value, members, lambda1)``: the best sweep cut of the Fiedler order, ``members`` a bool ``[n]`` array holding the side of
+    smaller volume, and the spectral gap.  ``'conductance'``: (lo + hi) / min(vol S, vol V - S), for which ``lambda1 / 2 <= value <=
+    sqrt(2 lambda1)``.  ``'reference'``: compute_cheeger.py's own ratio, lo / min(2 in, 2 out); it is not symmetric in the
+    orientation of the order (``lo`` counts only the edges whose SMALLER endpoint is inside), so both x and -x are swept and the
+    smaller value is returned.
+    :param data: a ``Data``, or a live ``DcrGraph``.
+    :param solver: keyword arguments of ``DcrGraph.spectral_gap`` (``tol``, ``max_steps``, ``max_basis``, ``seed``).
+    """
+    import numpy as np
+    unknown = set(solver) - {'tol', 'max_steps', 'max_basis', 'seed'}
+    if unknown:
+        raise TypeError(f'unknown solver arguments: {sorted(unknown)}')
+    G = _graph(data)
+    gap, cut, score = G.fiedler_sweep(definition=definition, **solver)
+    if definition == 'reference':
+        other = G.sweep_cut(-score, definition=definition)
+        if other.value < cut.value:
+            cut = other
+    members = np.zeros(G.number_of_nodes(), dtype=bool)
+    members[cut.order[:cut.size]] = True
+    n_in, _, _, n_out = (int(c) for c in cut.counts)
+    if n_in > n_out:   # vol S - vol (V - S) = 2 (in - out) under either definition
+        members = ~members
+    return cut.value, members, gap.lambda1

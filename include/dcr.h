@@ -216,6 +216,33 @@ int dcr_connected_components(dcr_graph *g, int32_t *out_labels /* host [n] */, i
 int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts /* NULL = defaults */,
                      dcr_spectral_result *out, double *out_vector /* host [n] or NULL */);
 
+/* ---- sweep cut: the constructive half of Cheeger's inequality (csrc/dcr_sweep.hip; no counterpart in the reference) ------
+ * The nodes are ordered ascending by (score, node id): -0.0 and +0.0 are the same score, +-inf are ordinary values, i.e.
+ * np.lexsort((ids, np.where(score == 0, 0.0, score))).  S_k is the first k nodes of that order, k = 1 .. num_nodes - 1.  With
+ * in / lo / hi / out of S_k counted as above (each undirected edge a < b once), the value of S_k is, by `definition`, one of the
+ * two ratios of dcr_cheeger_philox_values: 0: lo / min(2 in, 2 out); 1: (lo + hi) / min(2 in + lo + hi, 2 out + lo + hi); +inf
+ * where the smaller volume is 0; one IEEE float64 division of exact integers.  The result is the smallest value and, among
+ * equal values, the smallest k (numpy's argmin of the profile; k = 1 when every value is +inf).  Sort, counts and arg-min run on
+ * the device over the live adjacency (a hand-written stable LSD radix sort on an order-preserving uint64 image of the score,
+ * integer difference arrays and prefix sums); the calls are READ-ONLY on the graph as the Cheeger and spectral calls are, run on
+ * the graph's stream and are synchronous on return.  Counts are int32 on the device: fewer than 2^31 live adjacency slots.
+ * O(num_nodes) work buffers stay on the handle until dcr_graph_destroy.
+ *   dcr_sweep_cut      score: host double [num_nodes].  out_order, host int32 [num_nodes] or NULL: the node at each position;
+ *                      out_profile, host double [num_nodes - 1] or NULL: the value of S_1 .. S_{n-1}.  A NaN in the score is
+ *                      DCR_EINVAL, found on the host before any device call.
+ *   dcr_fiedler_sweep  runs the solver of dcr_spectral_gap (same opts, same out_gap bits), keeps the eigenvector y on the
+ *                      device, forms the score x = s ⊙ y with the solver's own s = 1 / sqrt(deg) (0 at degree 0) -- the Fiedler
+ *                      vector in D^-1/2 scaling -- and sweeps it with no host round trip of the vector.  out_score, host
+ *                      double [num_nodes] or NULL: the score that was swept.  With `definition` 1 the result satisfies
+ *                      lambda_1 / 2 <= h <= value <= sqrt(2 lambda_1).  A graph without edges: DCR_EINVAL, as dcr_spectral_gap.
+ * Null g, out (or out_gap), score; a definition outside {0, 1}; num_nodes < 2: DCR_EINVAL. */
+typedef struct { double value; int64_t size, in, lo, hi; } dcr_sweep_result;   /* size = best k */
+int dcr_sweep_cut(dcr_graph *g, const double *score /* host [n] */, int definition, dcr_sweep_result *out,
+                  int32_t *out_order /* host [n] or NULL */, double *out_profile /* host [n-1] or NULL */);
+int dcr_fiedler_sweep(dcr_graph *g, const dcr_spectral_opts *opts, int definition,
+                      dcr_spectral_result *out_gap, dcr_sweep_result *out,
+                      int32_t *out_order, double *out_score /* host [n] or NULL */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
