@@ -511,7 +511,7 @@ int dcr_graph_destroy(dcr_graph *g) {
                         g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
                         g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists, g->chg_members, g->chg_counts, g->chg_values,
                         g->spc_label, g->spc_ctl, g->spc_vec, g->spc_basis, g->spc_rows, g->spc_chunks, g->spc_part, g->spc_small,
-                        g->swp_keys, g->swp_idx, g->swp_table, g->swp_f64, g->swp_ctl};
+                        g->swp_keys, g->swp_idx, g->swp_table, g->swp_f64, g->swp_ctl, g->res_vec, g->res_rows, g->res_part, g->res_ctl};
     for (void *p : dev_ptrs)
         if (p) (void)hipFree(p);
     for (int b = 0; b < NBINS; ++b)

@@ -192,6 +192,35 @@ __device__ inline bool last_arriver(T *ticket, T arrivals) {
     return last;
 }
 
+// ---- deterministic fp64 reductions (dcr_spectral.hip, dcr_resistance.hip): no floating-point atomics; per-workgroup partials go
+// through the L2 (st_agent), the last arriver closes them in index order (ld_agent) ----------------------------------------
+__device__ inline double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// butterfly: every lane ends with the same bits (a + b == b + a)
+__device__ inline double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// 256 threads; the four wave sums are added in wave order.  sh is free again on return.
+__device__ inline double block_sum(double x, double *sh) {
+    x = wave_sum(x);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return r;
+}
+
+// sum of other workgroups' partials part[0 .. count): thread t takes t, t + 256, ... in order, then block_sum
+__device__ inline double close_partials(const double *part, int64_t count, double *sh) {
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < count; i += 256) acc += ld_agent(part + i);
+    return block_sum(acc, sh);
+}
+
 struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in device memory
     int32_t x, y, dx, dy;
     int32_t T, s1, s2;
@@ -348,6 +377,16 @@ struct dcr_graph {
     double *spc_small = nullptr;    // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
     int64_t spc_small_cap = 0;
 
+    // effective resistance (dcr_resistance.hip), grown on demand: O(n B), B the columns of a batch
+    double *res_vec = nullptr;      // z, p, r, y, q as [n][B] each, then s [n]
+    int64_t res_vec_cap = 0;
+    int32_t *res_rows = nullptr;    // [n] rows by degree class
+    int64_t res_rows_cap = 0;
+    double *res_part = nullptr;     // per-workgroup partial sums, B per workgroup (2 B in the closing mat-vec)
+    int64_t res_part_cap = 0;
+    unsigned char *res_ctl = nullptr;  // the batch's control block (ResCtl of dcr_resistance.hip)
+    int64_t res_ctl_cap = 0;
+
     // sweep cut (dcr_sweep.hip), grown on demand: all O(n)
     uint64_t *swp_keys = nullptr;   // [2][n] sort keys, ping and pong
     int64_t swp_keys_cap = 0;
@@ -418,6 +457,9 @@ int launch_curvature_pass_h2(dcr_graph *g);
 bool h2_grow_pools(dcr_graph *g);
 
 // dcr_spectral.hip
+constexpr int SP_SHORT_DEG = 32;    // rows up to this degree: a lane group a row
+constexpr int SP_LONG_DEG = 2048;   // rows above this degree: a workgroup a row
+constexpr int SP_CHECK_EVERY = 8;   // solver steps between host synchronisations
 struct RowClasses {
     int n_long, n_mid, n_short;
 };
@@ -428,6 +470,8 @@ struct SpectralKept {  // what spectral_solve leaves in device memory: the unit 
     const int32_t *rows;
     RowClasses rc;
 };
+int spectral_components(dcr_graph *g, std::vector<int32_t> &labels);  // labels (smallest node id of the component) into g->spc_label and onto the host
+void spectral_scale(dcr_graph *g, double *s);  // launches s = 1 / sqrt(deg), 0 at degree 0, on the graph's stream
 int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept);
 void spectral_release_basis(dcr_graph *g);  // synchronises the stream and frees the Lanczos basis (y with it)
 

@@ -36,39 +36,9 @@
 
 namespace dcr {
 
-constexpr int SP_SHORT_DEG = 32;    // rows up to this degree: eight lanes a row
-constexpr int SP_LONG_DEG = 2048;   // rows above this degree: a workgroup a row
 constexpr int SP_WAVE_ELEMS = 512;  // elements of w a wave of k_spec_gs_coef keeps in registers
 constexpr int SP_CHUNK = 1024;      // nodes per deflation chunk
-constexpr int SP_CHECK_EVERY = 8;   // Lanczos steps between host synchronisations
 constexpr double SP_BREAKDOWN = 0x1p-40;
-
-__device__ inline double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// butterfly: every lane ends with the same bits (a + b == b + a)
-__device__ inline double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// 256 threads; the four wave sums are added in wave order.  sh is free again on return.
-__device__ inline double block_sum(double x, double *sh) {
-    x = wave_sum(x);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-
-// sum of other workgroups' partials part[0 .. count): thread t takes t, t + 256, ... in order, then block_sum
-__device__ inline double close_partials(const double *part, int64_t count, double *sh) {
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += 256) acc += ld_agent(part + i);
-    return block_sum(acc, sh);
-}
 
 // ---- connected components --------------------------------------------------------------------------------------------------------
 __device__ inline int32_t cc_find(const int32_t *label, int32_t x) {
@@ -379,7 +349,7 @@ static bool top_ritz(const double *alpha, const double *beta, int k, bool full, 
 static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // labels (smallest node id of the component) into g->spc_label, and onto the host
-static int spectral_components(dcr_graph *g, std::vector<int32_t> &labels) {
+int spectral_components(dcr_graph *g, std::vector<int32_t> &labels) {
     const int64_t n = g->n;
     labels.resize((size_t)n);
     if (n == 0) return DCR_OK;
@@ -420,6 +390,10 @@ void classify_rows(const std::vector<int2> &info, std::vector<int32_t> &rows, Ro
     rc->n_long = (int)nl;
     rc->n_mid = (int)nm;
     rc->n_short = (int)ns;
+}
+
+void spectral_scale(dcr_graph *g, double *s) {
+    hipLaunchKernelGGL(k_spec_scale, dim3(blocks_of(g->n)), dim3(256), 0, g->stream, g->rowinfo, s, g->n);
 }
 
 void spectral_release_basis(dcr_graph *g) {
@@ -590,7 +564,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
     if (!order.empty())
         DCR_HIP(hipMemcpyAsync(R.order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, g->stream));
     DCR_HIP(hipMemcpyAsync(g->spc_chunks, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
-    hipLaunchKernelGGL(k_spec_scale, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, R.s, n);
+    spectral_scale(g, R.s);
     hipLaunchKernelGGL(k_spec_start, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, R.w, n, (uint64_t)0, o.seed);
     R.first_column();
     DCR_HIP(hipGetLastError());

@@ -37,6 +37,11 @@ class SweepResult(ctypes.Structure):
     _fields_ = [('value', _f64), ('size', _i64), ('n_in', _i64), ('n_lo', _i64), ('n_hi', _i64)]
 
 
+class ResistanceOpts(ctypes.Structure):
+    """dcr_resistance_opts of include/dcr.h."""
+    _fields_ = [('tol', _f64), ('max_steps', _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -82,6 +87,7 @@ SIGNATURES = {
     'dcr_sweep_cut': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, ctypes.POINTER(SweepResult), _i32p, _f64p]),
     'dcr_fiedler_sweep': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.c_int, ctypes.POINTER(SpectralResult),
                                          ctypes.POINTER(SweepResult), _i32p, _f64p]),
+    'dcr_effective_resistance': (ctypes.c_int, [_vp, _i32p, _i32p, _i64, ctypes.POINTER(ResistanceOpts), _f64p, _f64p, _i32p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -41,6 +41,10 @@ SpectralGap = namedtuple('SpectralGap', ['lambda1', 'residual', 'steps', 'restar
 SweepCut = namedtuple('SweepCut', ['value', 'size', 'counts', 'order', 'profile'])
 
 
+# pairs of one batch of DcrGraph.effective_resistance: DCR_RES_B of csrc/dcr_resistance.hip
+RESISTANCE_BATCH = 16
+
+
 def pack_members(members, num_nodes):
     """(uint64 words [n, W], number of subsets) from bool ``[B, n]`` or from the packed words themselves."""
     m = np.asarray(members)
@@ -388,6 +392,50 @@ class DcrGraph:
                           RuntimeWarning, stacklevel=2)
         return (SpectralGap(gap.lambda1, gap.residual, gap.steps, gap.restarts, gap.components, bool(gap.converged), None),
                 self._sweep_result(res, order, None), score)
+
+    # ---- effective resistance (csrc/dcr_resistance.hip) -------------------------------------------------------------------
+    def effective_resistance(self, pairs, tol=1e-10, max_steps=20000, return_info=False):
+        """Effective resistance R(u, v) = (e_u - e_v)^T L^+ (e_u - e_v), L = D - A, of each pair of ``pairs`` (array-like
+        ``[P, 2]``) on the live graph, as float64 ``[P]``: ``RESISTANCE_BATCH`` conjugate-gradient solves at a time on the device,
+        read-only on the graph.  The value is the LOWER bound ``2 c^T y - y^T L' y`` of include/dcr.h: never above R (whatever
+        ``max_steps``), and within ``residual ** 2 / lambda_1`` of it.  0.0 for u == v and inf across components, both decided
+        without a solve.  ``return_info``: also a dict of ``residual`` (float64, the true ``|c - L' y|``), ``steps`` (int32) and
+        ``converged`` (bool: ``residual <= tol |c|``, ``|c|^2 = 1 / deg u + 1 / deg v``; True where no solve was needed).
+        ``RuntimeWarning`` when a pair did not converge; ``ValueError`` on an endpoint outside the graph."""
+        pr = np.asarray(pairs)
+        if pr.size == 0:
+            pr = pr.reshape(0, 2)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError('pairs must have shape [P, 2]')
+        if pr.size and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+            raise ValueError('pair endpoint outside 0 .. num_nodes - 1')
+        u = np.ascontiguousarray(pr[:, 0], dtype=np.int32)
+        v = np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+        P = u.shape[0]
+        lower, residual = np.empty(P, dtype=np.float64), np.empty(P, dtype=np.float64)
+        steps = np.empty(P, dtype=np.int32)
+        opts = _lib.ResistanceOpts(float(tol), int(max_steps))
+        check(lib().dcr_effective_resistance(self._h, u.ctypes.data_as(_lib._i32p), v.ctypes.data_as(_lib._i32p), P, ctypes.byref(opts),
+                                             lower.ctypes.data_as(_lib._f64p), residual.ctypes.data_as(_lib._f64p),
+                                             steps.ctypes.data_as(_lib._i32p)))
+        converged = np.ones(P, dtype=bool)
+        solved = np.flatnonzero(np.isfinite(lower) & (u != v))
+        if solved.size:
+            nodes = np.unique(np.concatenate([u[solved], v[solved]]))
+            deg = np.zeros(self.num_nodes, dtype=np.float64)
+            if nodes.size <= 64:
+                deg[nodes] = [self.degree(int(x)) for x in nodes]
+            else:
+                deg = np.bincount(np.concatenate(self.edges()), minlength=self.num_nodes).astype(np.float64)
+            cnorm = np.sqrt(1.0 / deg[u[solved]] + 1.0 / deg[v[solved]])
+            converged[solved] = residual[solved] <= float(tol) * cnorm
+        if not converged.all():
+            worst = residual[~converged].max()
+            warnings.warn(f'effective_resistance: {int((~converged).sum())} of {P} pairs above tol {float(tol):.3e} after '
+                          f'{int(max_steps)} steps (largest residual {worst:.3e})', RuntimeWarning, stacklevel=2)
+        if return_info:
+            return lower, {'residual': residual, 'steps': steps, 'converged': converged}
+        return lower
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

@@ -243,6 +243,34 @@ int dcr_fiedler_sweep(dcr_graph *g, const dcr_spectral_opts *opts, int definitio
                       dcr_spectral_result *out_gap, dcr_sweep_result *out,
                       int32_t *out_order, double *out_score /* host [n] or NULL */);
 
+/* ---- effective resistance of node pairs (csrc/dcr_resistance.hip; no counterpart in the reference) ------------------------
+ * R(u, v) = (e_u - e_v)^T L^+ (e_u - e_v), L = D - A the combinatorial Laplacian of the live graph: the commute time between u
+ * and v divided by 2 E.  Solved in the normalised operator of the spectral calls: with L' = I - D^-1/2 A D^-1/2 and
+ * c = s_u e_u - s_v e_v, s = 1 / sqrt(deg), R = c^T y* where L' y* = c, by conjugate gradients from y = 0 (Jacobi-preconditioned
+ * CG on L), 8 or 16 pairs at a time as independent columns of one multi-column mat-vec over the live adjacency.
+ *   out_lower     host double [P]: 2 c^T y - y^T L' y for the y the iteration ended with.  For ANY y this is a LOWER bound:
+ *                 R - out_lower = (y* - y)^T L' (y* - y) >= 0, also when the solve was cut short by max_steps, and
+ *                 R - out_lower <= out_residual^2 / lambda_1, lambda_1 the spectral gap of dcr_spectral_gap (of the whole graph: it
+ *                 is the smallest over the components with an edge).  Computed with a mat-vec of its own, not from the recurrences.
+ *   out_residual  host double [P]: the true residual |c - L' y|_2 from that same mat-vec.  A pair has converged when it is
+ *                 <= tol |c|_2, |c|_2^2 = 1 / deg u + 1 / deg v.
+ *   out_steps     host int32 [P] or NULL: CG steps the pair's column took.  A column stops, on the device, in the step where the
+ *                 recurrence's |r| <= tol |c|, or where p^T L' p is not a positive finite number.
+ * Decided from the connected components before any solve: u == v gives 0 (residual 0, steps 0); u and v in different
+ * components, an isolated node included, give +inf (residual 0, steps 0).
+ * opts NULL = defaults: tol 1e-10, max_steps 20000.  A pair that ran out of steps is still DCR_OK; its residual says so.
+ * All arithmetic is fp64 without floating-point atomics and every reduction has a fixed order in which the columns of a batch
+ * do not meet: a pair's three outputs are the same bits whatever else is in the call and wherever in it the pair stands.
+ * READ-ONLY on the graph as the Cheeger and spectral calls are, runs on the graph's stream and is synchronous on return; work
+ * buffers of O(16 num_nodes) doubles stay on the handle until dcr_graph_destroy.
+ * Null g, u, v, out_lower or out_residual; P < 0; an endpoint outside 0 .. num_nodes - 1; tol negative or NaN; max_steps < 1:
+ * DCR_EINVAL before any device call.  P == 0: DCR_OK, nothing written. */
+typedef struct { double tol; int64_t max_steps; } dcr_resistance_opts;
+int dcr_effective_resistance(dcr_graph *g, const int32_t *u, const int32_t *v, int64_t P,
+                             const dcr_resistance_opts *opts /* NULL = defaults */,
+                             double *out_lower /* host [P] */, double *out_residual /* host [P] */,
+                             int32_t *out_steps /* host [P] or NULL */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
