@@ -18,7 +18,7 @@
 // Both take every undirected edge at the slot where col > row, as the curvature array does, and skip the slack of the rows.
 #include <cstdlib>
 
-#include "dcr_internal.h"
+#include "dcr_analysis.h"
 #include "dcr_philox.h"
 
 namespace dcr {
@@ -192,17 +192,11 @@ __global__ void __launch_bounds__(256) k_cheeger_draw(uint64_t *mem, int64_t n, 
 }
 
 // ---- counts -> ratios ---------------------------------------------------------------------------------------------------------
-// definition 0: compute_cheeger.py:40-45, lo / min(2 in, 2 out); 1: (lo + hi) / min(2 in + lo + hi, 2 out + lo + hi).  inf where
-// the smaller volume is zero.  One IEEE float64 division of two integers below 2^53.
 __global__ void __launch_bounds__(256) k_cheeger_values(const unsigned long long *counts, int64_t n_sub, int64_t B, int64_t n_edges,
                                                          int definition, double *out) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= B) return;
-    const int64_t in = (int64_t)counts[j], lo = (int64_t)counts[n_sub + j], hi = (int64_t)counts[2 * n_sub + j];
-    const int64_t outside = n_edges - in - lo - hi;
-    const int64_t cut = definition ? lo + hi : lo, extra = definition ? lo + hi : 0;
-    const int64_t va = 2 * in + extra, vb = 2 * outside + extra, m = va < vb ? va : vb;
-    out[j] = m == 0 ? __builtin_inf() : (double)cut / (double)m;
+    out[j] = cheeger_ratio((int64_t)counts[j], (int64_t)counts[n_sub + j], (int64_t)counts[2 * n_sub + j], n_edges, definition);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
@@ -213,9 +207,10 @@ static bool cheeger_use_lane() {
 
 static int cheeger_buffers(dcr_graph *g, int64_t W) {
     DCR_HIP(hipSetDevice(g->device));
-    DCR_TRY(dev_regrow(&g->chg_members, &g->chg_members_cap, g->n * W));
-    DCR_TRY(dev_regrow(&g->chg_counts, &g->chg_counts_cap, 3 * 64 * W));
-    DCR_TRY(dev_regrow(&g->chg_values, &g->chg_values_cap, 64 * W));
+    AnalysisState &A = analysis_of(g);
+    DCR_TRY(dev_regrow(&A.chg_members, &A.chg_members_cap, g->n * W));
+    DCR_TRY(dev_regrow(&A.chg_counts, &A.chg_counts_cap, 3 * 64 * W));
+    DCR_TRY(dev_regrow(&A.chg_values, &A.chg_values_cap, 64 * W));
     return DCR_OK;
 }
 
@@ -230,13 +225,13 @@ static void launch_sliced(dcr_graph *g, int W) {
     const int64_t chunk = per_round * rounds;
     const unsigned gx = (unsigned)((g->cap_total + chunk - 1) / chunk);
     hipLaunchKernelGGL(k_cheeger_sliced<WL>, dim3(gx, (unsigned)groups), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                       g->cap_total, g->chg_members, W, (int)rounds, g->chg_counts, (int64_t)64 * W);
+                       g->cap_total, g->analysis->chg_members, W, (int)rounds, g->analysis->chg_counts, (int64_t)64 * W);
 }
 
-// counts of the subsets in g->chg_members [n][W] -> g->chg_counts [3][64 W], on the graph's stream (no synchronisation)
+// counts of the subsets in chg_members [n][W] -> chg_counts [3][64 W] (after cheeger_buffers), on the graph's stream (no synchronisation)
 static int cheeger_run(dcr_graph *g, int W) {
     const int64_t n_sub = (int64_t)64 * W;
-    DCR_HIP(hipMemsetAsync(g->chg_counts, 0, sizeof(unsigned long long) * 3 * (size_t)n_sub, g->stream));
+    DCR_HIP(hipMemsetAsync(g->analysis->chg_counts, 0, sizeof(unsigned long long) * 3 * (size_t)n_sub, g->stream));
     if (g->cap_total <= 0 || g->n <= 0) return DCR_OK;
     if (cheeger_use_lane()) {
         int64_t per = g->cap_total * W / (8 * (g->num_cu > 0 ? g->num_cu : 256)) + 1;
@@ -244,7 +239,7 @@ static int cheeger_run(dcr_graph *g, int W) {
         if (per < 512) per = 512;
         const unsigned gx = (unsigned)((g->cap_total + per - 1) / per);
         hipLaunchKernelGGL(k_cheeger_lane, dim3(gx, (unsigned)W), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                           g->cap_total, g->chg_members, W, per, g->chg_counts, n_sub);
+                           g->cap_total, g->analysis->chg_members, W, per, g->analysis->chg_counts, n_sub);
     } else if (W >= 16) {
         launch_sliced<16>(g, W);
     } else if (W > 4) {
@@ -263,7 +258,7 @@ static int cheeger_run(dcr_graph *g, int W) {
 static int cheeger_draw(dcr_graph *g, uint64_t seed, int64_t first, int W) {
     const int64_t total = g->n * W;
     if (total <= 0) return DCR_OK;
-    hipLaunchKernelGGL(k_cheeger_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g->stream, g->chg_members, g->n, W,
+    hipLaunchKernelGGL(k_cheeger_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_members, g->n, W,
                        first / 64, seed);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
@@ -272,7 +267,7 @@ static int cheeger_draw(dcr_graph *g, uint64_t seed, int64_t first, int W) {
 // counts [3][n_sub] on the device -> out [B][3] on the host
 static int cheeger_fetch_counts(dcr_graph *g, int64_t n_sub, int64_t B, int64_t *out) {
     std::vector<unsigned long long> h((size_t)(3 * n_sub));
-    DCR_HIP(hipMemcpyAsync(h.data(), g->chg_counts, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(h.data(), g->analysis->chg_counts, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     for (int64_t j = 0; j < B; ++j)
         for (int c = 0; c < 3; ++c) out[3 * j + c] = (int64_t)h[(size_t)(c * n_sub + j)];
@@ -299,7 +294,7 @@ int dcr_cheeger_counts(dcr_graph *g, const uint64_t *members, int64_t W, int64_t
     if (W <= 0 || W > CHEEGER_MAX_WORDS) DCR_FAIL(DCR_EINVAL, "W out of range");
     DCR_TRY(cheeger_buffers(g, W));
     if (g->n > 0)
-        DCR_HIP(hipMemcpyAsync(g->chg_members, members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(g->analysis->chg_members, members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyHostToDevice, g->stream));
     DCR_TRY(cheeger_run(g, (int)W));
     return cheeger_fetch_counts(g, 64 * W, 64 * W, out_counts);
 }
@@ -311,7 +306,7 @@ int dcr_cheeger_philox_members(dcr_graph *g, uint64_t seed, int64_t first, int64
     DCR_TRY(cheeger_buffers(g, W));
     DCR_TRY(cheeger_draw(g, seed, first, (int)W));
     if (g->n > 0)
-        DCR_HIP(hipMemcpyAsync(out_members, g->chg_members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(out_members, g->analysis->chg_members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
@@ -334,10 +329,10 @@ int dcr_cheeger_philox_values(dcr_graph *g, uint64_t seed, int64_t first, int64_
     DCR_TRY(cheeger_buffers(g, W));
     DCR_TRY(cheeger_draw(g, seed, first, (int)W));
     DCR_TRY(cheeger_run(g, (int)W));
-    hipLaunchKernelGGL(k_cheeger_values, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g->stream, g->chg_counts, 64 * W, B,
-                       g->n_edges, definition, g->chg_values);
+    hipLaunchKernelGGL(k_cheeger_values, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_counts, 64 * W, B,
+                       g->n_edges, definition, g->analysis->chg_values);
     DCR_HIP(hipGetLastError());
-    DCR_HIP(hipMemcpyAsync(out_values, g->chg_values, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_values, g->analysis->chg_values, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }

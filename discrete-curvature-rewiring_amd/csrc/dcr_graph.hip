@@ -509,11 +509,10 @@ int dcr_graph_destroy(dcr_graph *g) {
                         g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_queues, g->giant_list,
                         g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight,
                         g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
-                        g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists, g->chg_members, g->chg_counts, g->chg_values,
-                        g->spc_label, g->spc_ctl, g->spc_vec, g->spc_basis, g->spc_rows, g->spc_chunks, g->spc_part, g->spc_small,
-                        g->swp_keys, g->swp_idx, g->swp_table, g->swp_f64, g->swp_ctl, g->res_vec, g->res_rows, g->res_part, g->res_ctl};
+                        g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists};
     for (void *p : dev_ptrs)
         if (p) (void)hipFree(p);
+    analysis_destroy(g);
     for (int b = 0; b < NBINS; ++b)
         if (g->work[b]) (void)hipFree(g->work[b]);
     if (g->hres) (void)hipHostFree(g->hres);

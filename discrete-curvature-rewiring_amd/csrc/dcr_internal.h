@@ -192,35 +192,6 @@ __device__ inline bool last_arriver(T *ticket, T arrivals) {
     return last;
 }
 
-// ---- deterministic fp64 reductions (dcr_spectral.hip, dcr_resistance.hip): no floating-point atomics; per-workgroup partials go
-// through the L2 (st_agent), the last arriver closes them in index order (ld_agent) ----------------------------------------
-__device__ inline double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// butterfly: every lane ends with the same bits (a + b == b + a)
-__device__ inline double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// 256 threads; the four wave sums are added in wave order.  sh is free again on return.
-__device__ inline double block_sum(double x, double *sh) {
-    x = wave_sum(x);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-
-// sum of other workgroups' partials part[0 .. count): thread t takes t, t + 256, ... in order, then block_sum
-__device__ inline double close_partials(const double *part, int64_t count, double *sh) {
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += 256) acc += ld_agent(part + i);
-    return block_sum(acc, sh);
-}
-
 struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in device memory
     int32_t x, y, dx, dy;
     int32_t T, s1, s2;
@@ -233,6 +204,8 @@ struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in
     int32_t done_draw;   // the same for k_draw_partial (the last one picks)
     int32_t pad_;
 };
+
+struct AnalysisState;  // dcr_analysis.h
 
 }  // namespace dcr
 
@@ -351,53 +324,7 @@ struct dcr_graph {
     dcr::ImpStats *imp_stats = nullptr;
     double *draw_bsum = nullptr;  // device-side draw: partial sums of exp(tau * improvement)
 
-    // Monte-Carlo Cheeger estimate (dcr_cheeger.hip), grown on demand: membership words [n][W], counts [3][64 W], ratios [64 W]
-    uint64_t *chg_members = nullptr;
-    int64_t chg_members_cap = 0;
-    unsigned long long *chg_counts = nullptr;
-    int64_t chg_counts_cap = 0;
-    double *chg_values = nullptr;
-    int64_t chg_values_cap = 0;
-
-    // spectral gap and connected components (dcr_spectral.hip), grown on demand
-    int32_t *spc_label = nullptr;   // [n] smallest node id of the node's component
-    int64_t spc_label_cap = 0;
-    unsigned *spc_ctl = nullptr;    // {a sweep of the components changed a label, reduction ticket, -, -}
-    int64_t spc_ctl_cap = 0;
-    double *spc_vec = nullptr;      // [4][n]: scale s, null-space weights k, z = s ⊙ v of the newest column, work vector w
-    int64_t spc_vec_cap = 0;
-    double *spc_basis = nullptr;    // [columns][n] Lanczos basis
-    int64_t spc_basis_cap = 0;
-    int32_t *spc_rows = nullptr;    // [2][n]: rows by degree class (long, medium, short), nodes by component
-    int64_t spc_rows_cap = 0;
-    int4 *spc_chunks = nullptr;     // deflation chunks
-    int64_t spc_chunks_cap = 0;
-    double *spc_part = nullptr;     // per-workgroup (per-wave) partial sums
-    int64_t spc_part_cap = 0;
-    double *spc_small = nullptr;    // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
-    int64_t spc_small_cap = 0;
-
-    // effective resistance (dcr_resistance.hip), grown on demand: O(n B), B the columns of a batch
-    double *res_vec = nullptr;      // z, p, r, y, q as [n][B] each, then s [n]
-    int64_t res_vec_cap = 0;
-    int32_t *res_rows = nullptr;    // [n] rows by degree class
-    int64_t res_rows_cap = 0;
-    double *res_part = nullptr;     // per-workgroup partial sums, B per workgroup (2 B in the closing mat-vec)
-    int64_t res_part_cap = 0;
-    unsigned char *res_ctl = nullptr;  // the batch's control block (ResCtl of dcr_resistance.hip)
-    int64_t res_ctl_cap = 0;
-
-    // sweep cut (dcr_sweep.hip), grown on demand: all O(n)
-    uint64_t *swp_keys = nullptr;   // [2][n] sort keys, ping and pong
-    int64_t swp_keys_cap = 0;
-    int32_t *swp_idx = nullptr;     // [7][n]: node ids ping and pong, rank, the three difference arrays (in, lo, hi), rows by degree class
-    int64_t swp_idx_cap = 0;
-    int32_t *swp_table = nullptr;   // [256][tiles] digit counts of a sort pass, then the scans' per-block sums and offsets
-    int64_t swp_table_cap = 0;
-    double *swp_f64 = nullptr;      // [2][n]: the score, the profile
-    int64_t swp_f64_cap = 0;
-    unsigned *swp_ctl = nullptr;    // tickets, NaN flag, the [8][256] digit histogram of the keys, the result block, arg-min partials
-    int64_t swp_ctl_cap = 0;
+    dcr::AnalysisState *analysis = nullptr;  // every buffer of the graph-analysis calls (dcr_analysis.h), created on first use
 
     dcr::DevResult *dres = nullptr;  // device
     dcr::DevResult *hres = nullptr;  // pinned host
@@ -422,8 +349,6 @@ struct dcr_graph {
 namespace dcr {
 
 // dcr_graph.hip
-int device_exclusive_scan(dcr_graph *g, const int32_t *in, int32_t *out, int64_t n, int64_t *total_out);
-int ensure_scan(dcr_graph *g, int64_t n);
 int relayout(dcr_graph *g);
 int sync_result(dcr_graph *g);  // D2H of DevResult + stream sync
 void launch_add_edge(dcr_graph *g, int32_t u, int32_t v);          // u < 0: no-op that clears add_status
@@ -456,24 +381,8 @@ bool h2_can_take(const dcr_graph *g, int curv_type, bool incremental);
 int launch_curvature_pass_h2(dcr_graph *g);
 bool h2_grow_pools(dcr_graph *g);
 
-// dcr_spectral.hip
-constexpr int SP_SHORT_DEG = 32;    // rows up to this degree: a lane group a row
-constexpr int SP_LONG_DEG = 2048;   // rows above this degree: a workgroup a row
-constexpr int SP_CHECK_EVERY = 8;   // solver steps between host synchronisations
-struct RowClasses {
-    int n_long, n_mid, n_short;
-};
-// rows by degree class as k_spec_matvec takes them: above 2,048 a workgroup a row, above 32 a wave a row, the rest eight lanes a row
-void classify_rows(const std::vector<int2> &info, std::vector<int32_t> &rows, RowClasses *rc);
-struct SpectralKept {  // what spectral_solve leaves in device memory: the unit Ritz vector y, the scale s = 1 / sqrt(deg), the row list
-    const double *y, *s;
-    const int32_t *rows;
-    RowClasses rc;
-};
-int spectral_components(dcr_graph *g, std::vector<int32_t> &labels);  // labels (smallest node id of the component) into g->spc_label and onto the host
-void spectral_scale(dcr_graph *g, double *s);  // launches s = 1 / sqrt(deg), 0 at degree 0, on the graph's stream
-int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept);
-void spectral_release_basis(dcr_graph *g);  // synchronises the stream and frees the Lanczos basis (y with it)
+// dcr_analysis.hip
+void analysis_destroy(dcr_graph *g);  // frees g->analysis and what it holds
 
 template <typename T>
 int dev_alloc(T **p, int64_t count) {

@@ -19,7 +19,7 @@
 //
 // Kernels (all fp64, no floating-point atomics: per-workgroup partials through the L2, closed in index order by the last arriver):
 //   k_res_start      r = p = c, z = s ⊙ p, y = 0 for all columns; |c|^2 per column
-//   k_res_matvec<0>  q = 𝓛 p = p - s ⊙ (A z) for all columns in one sweep of the rows, in the three degree classes of k_spec_matvec
+//   k_res_matvec<0>  q = 𝓛 p = p - s ⊙ (A z) for all columns in one sweep of the rows, through walk_rows in the three degree classes
 //                    (<= 32: 32 lanes a row, 64 rows a workgroup; <= 2048: a wave a row; above: a workgroup a row, those first); the
 //                    per-column partials of p^T q; the last arriver sets alpha = |r|^2 / p^T q or freezes the column
 //   k_res_update     y += alpha p, r -= alpha q, partials of the new |r|^2; the last arriver sets beta, counts the step and freezes
@@ -31,7 +31,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "dcr_internal.h"
+#include "dcr_analysis.h"
 
 #ifndef DCR_RES_B
 #define DCR_RES_B 16  // columns of a batch: 8 or 16 (DESIGN §4.8 has the timings of both)
@@ -43,6 +43,7 @@ constexpr int RES_B = DCR_RES_B;
 constexpr int RES_CP = RES_B / 2;        // lanes across a node: two columns each
 constexpr int RES_SHORT_LANES = 32;      // lanes of a short row's group
 constexpr int RES_SHORT_ROWS = 64;       // short rows a workgroup takes: 8 groups x 8 turns
+using ResRows = RowGeom<RES_SHORT_LANES, RES_SHORT_ROWS / 8, RES_CP>;
 constexpr int RES_UPDATE_BLOCKS = 1024;  // most workgroups of the element-wise kernels with a reduction
 static_assert(RES_B == 8 || RES_B == 16, "a batch has 8 or 16 columns");
 
@@ -67,31 +68,9 @@ __device__ inline void st2(double *base, int64_t node, int cp, double2 x) { *rei
 // the entry of c = s_u e_u - s_v e_v at `node` for the column of pair (u, v)
 __device__ inline double c_entry(int32_t node, int32_t u, int32_t v, double s_node) { return node == u ? s_node : node == v ? -s_node : 0.0; }
 
-// x summed over the lanes of the wave that hold the same column pair (lane % RES_CP): a butterfly, the same bits in each of them
-__device__ inline double2 cols_wave_sum(double2 x) {
-#pragma unroll
-    for (int off = 32; off >= RES_CP; off >>= 1) {
-        x.x += __shfl_xor(x.x, off);
-        x.y += __shfl_xor(x.y, off);
-    }
-    return x;
-}
-
-// 256 threads: the same over the workgroup, the four wave sums added in wave order.  sh: 4 RES_CP entries, free again on return.
-__device__ inline double2 cols_block_sum(double2 x, double2 *sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cp = lane % RES_CP;
-    x = cols_wave_sum(x);
-    if (lane < RES_CP) sh[wave * RES_CP + lane] = x;
-    __syncthreads();
-    double2 r = sh[cp];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        r.x += sh[w * RES_CP + cp].x;
-        r.y += sh[w * RES_CP + cp].y;
-    }
-    __syncthreads();
-    return r;
-}
+// x summed per column pair (lane % RES_CP) over the workgroup: butterflies over the offsets 32 .. RES_CP, then the four wave sums
+// in wave order.  sh: 4 RES_CP entries, free again on return.
+__device__ inline double2 cols_block_sum(double2 x, double2 *sh) { return block_sum<RES_CP>(x, sh); }
 
 // partials part[workgroup][RES_B] of `count` workgroups: thread t adds those of workgroups t / RES_CP, + 256 / RES_CP, ... for its
 // column pair in order, then cols_block_sum
@@ -137,14 +116,12 @@ __global__ void __launch_bounds__(256) k_res_start(const double *__restrict__ s,
 
 // ---- mat-vec ---------------------------------------------------------------------------------------------------------------------
 // MODE 0: x = p, q = 𝓛 p stored, partials of p^T q.  MODE 1: x = y, w = 𝓛 y not stored, partials of y^T w and, behind them, of |c - w|^2.
-// rows: the long rows, then the medium ones, then the short ones; workgroups in the same order.
 template <int MODE>
-__global__ void __launch_bounds__(256) k_res_matvec(const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
-                                                     const int32_t *__restrict__ rows, int n_long, int n_mid, int n_short, int nb_long,
-                                                     int nb_mid, const double *__restrict__ x, const double *__restrict__ z,
+__global__ void __launch_bounds__(256) k_res_matvec(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
+                                                     const double *__restrict__ x, const double *__restrict__ z,
                                                      const double *__restrict__ s, double *__restrict__ q, ResCtl *ctl, double *part) {
     __shared__ double2 sh[4 * RES_CP];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, cp = lane % RES_CP;
+    const int t = threadIdx.x, cp = t % RES_CP;
     const int b = blockIdx.x;
     int32_t u0 = -1, v0 = -1, u1 = -1, v1 = -1;
     if (MODE == 1) {
@@ -154,70 +131,31 @@ __global__ void __launch_bounds__(256) k_res_matvec(const int2 *__restrict__ row
         v1 = ctl->v[2 * cp + 1];
     }
     double2 dot = make_double2(0.0, 0.0), dev = make_double2(0.0, 0.0);
-    // the row's entry of 𝓛 x from acc = (A z)_row, by the RES_CP lanes that own the row
-    auto finish = [&](int32_t row, int deg, double2 acc) {
-        const double2 xu = ld2(x, row, cp);
-        const double su = s[row];
-        double2 w;
-        w.x = deg > 0 ? xu.x - su * acc.x : 0.0;
-        w.y = deg > 0 ? xu.y - su * acc.y : 0.0;
-        dot.x += xu.x * w.x;
-        dot.y += xu.y * w.y;
-        if (MODE == 0) {
-            st2(q, row, cp, w);
-        } else {
-            const double e0 = c_entry(row, u0, v0, su) - w.x, e1 = c_entry(row, u1, v1, su) - w.y;
-            dev.x += e0 * e0;
-            dev.y += e1 * e1;
-        }
-    };
-    if (b < nb_long) {
-        const int32_t row = rows[b];
-        const int2 ri = rowinfo[row];
-        double2 acc = make_double2(0.0, 0.0);
-        for (int j = t / RES_CP; j < ri.y; j += 256 / RES_CP) {
+    walk_rows<ResRows>(plan, rowinfo, sh, [=](auto scope, int32_t row, int2 ri, double2 &xw, double2 &ee) {
+        double2 acc = make_double2(0.0, 0.0);  // (A z)_row
+        for (int j = scope.first(); j < ri.y; j += scope.stride) {
             const double2 zv = ld2(z, col[ri.x + j], cp);
             acc.x += zv.x;
             acc.y += zv.y;
         }
-        acc = cols_block_sum(acc, sh);
-        if (t < RES_CP) finish(row, ri.y, acc);
-    } else if (b < nb_long + nb_mid) {
-        const int i = (b - nb_long) * 4 + wave;
-        if (i < n_mid) {
-            const int32_t row = rows[n_long + i];
-            const int2 ri = rowinfo[row];
-            double2 acc = make_double2(0.0, 0.0);
-            for (int j = lane / RES_CP; j < ri.y; j += 64 / RES_CP) {
-                const double2 zv = ld2(z, col[ri.x + j], cp);
-                acc.x += zv.x;
-                acc.y += zv.y;
-            }
-            acc = cols_wave_sum(acc);
-            if (lane < RES_CP) finish(row, ri.y, acc);
+        acc = scope.sum(acc);
+        if (!scope.owner()) return;
+        // the row's entry of 𝓛 x, by the RES_CP lanes that own the row
+        const double2 xu = ld2(x, row, cp);
+        const double su = s[row];
+        double2 w;
+        w.x = ri.y > 0 ? xu.x - su * acc.x : 0.0;
+        w.y = ri.y > 0 ? xu.y - su * acc.y : 0.0;
+        xw.x += xu.x * w.x;
+        xw.y += xu.y * w.y;
+        if (MODE == 0) {
+            st2(q, row, cp, w);
+        } else {
+            const double e0 = c_entry(row, u0, v0, su) - w.x, e1 = c_entry(row, u1, v1, su) - w.y;
+            ee.x += e0 * e0;
+            ee.y += e1 * e1;
         }
-    } else {
-        const int sub = t & (RES_SHORT_LANES - 1), grp = t / RES_SHORT_LANES;  // 8 groups
-        const int first = (b - nb_long - nb_mid) * RES_SHORT_ROWS;
-        for (int turn = 0; turn < RES_SHORT_ROWS / 8; ++turn) {
-            const int i = first + turn * 8 + grp;
-            const bool ok = i < n_short;
-            const int32_t row = ok ? rows[n_long + n_mid + i] : 0;
-            const int2 ri = ok ? rowinfo[row] : make_int2(0, 0);
-            double2 acc = make_double2(0.0, 0.0);
-            for (int j = sub / RES_CP; j < ri.y; j += RES_SHORT_LANES / RES_CP) {
-                const double2 zv = ld2(z, col[ri.x + j], cp);
-                acc.x += zv.x;
-                acc.y += zv.y;
-            }
-#pragma unroll
-            for (int off = RES_SHORT_LANES / 2; off >= RES_CP; off >>= 1) {
-                acc.x += __shfl_xor(acc.x, off);
-                acc.y += __shfl_xor(acc.y, off);
-            }
-            if (ok && sub < RES_CP) finish(row, ri.y, acc);
-        }
-    }
+    }, dot, dev);
     dot = cols_block_sum(dot, sh);
     if (t < RES_CP) cols_store_partial(part, b, dot);
     if (MODE == 1) {
@@ -340,26 +278,22 @@ __global__ void __launch_bounds__(256) k_res_scale_y(int64_t n, const double *__
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
-static int resistance_batches(dcr_graph *g, const std::vector<int2> &info, const int32_t *u, const int32_t *v,
-                              const std::vector<int64_t> &todo, const dcr_resistance_opts &o, double *out_lower, double *out_residual,
-                              int32_t *out_steps) {
+static int resistance_batches(dcr_graph *g, const int32_t *u, const int32_t *v, const std::vector<int64_t> &todo,
+                              const dcr_resistance_opts &o, double *out_lower, double *out_residual, int32_t *out_steps) {
     const int64_t n = g->n;
-    std::vector<int32_t> rows;
-    RowClasses rc;
-    classify_rows(info, rows, &rc);
-    const int nb_long = rc.n_long, nb_mid = (rc.n_mid + 3) / 4;
-    const int nb_mv = nb_long + nb_mid + (rc.n_short + RES_SHORT_ROWS - 1) / RES_SHORT_ROWS;
-    const int nb_el = (int)std::min<int64_t>(RES_UPDATE_BLOCKS, (n * RES_CP + 255) / 256);
+    RowPlan plan;
+    DCR_TRY(build_row_plan(g, &plan, nullptr));
+    const int nb_mv = (int)row_grid<ResRows>(plan);
+    const int nb_el = (int)std::min<int64_t>(RES_UPDATE_BLOCKS, blocks_of(n * RES_CP));
 
-    DCR_TRY(dev_regrow(&g->res_vec, &g->res_vec_cap, n + 5 * n * RES_B));
-    DCR_TRY(dev_regrow(&g->res_rows, &g->res_rows_cap, n));
-    DCR_TRY(dev_regrow(&g->res_part, &g->res_part_cap, (int64_t)RES_B * std::max(2 * nb_mv, nb_el)));
-    DCR_TRY(dev_regrow(&g->res_ctl, &g->res_ctl_cap, (int64_t)sizeof(ResCtl)));
-    double *z = g->res_vec, *p = z + n * RES_B, *r = p + n * RES_B, *y = r + n * RES_B, *q = y + n * RES_B;  // 16-byte aligned each
+    AnalysisState &A = analysis_of(g);
+    DCR_TRY(dev_regrow(&A.res_vec, &A.res_vec_cap, n + 5 * n * RES_B));
+    DCR_TRY(dev_regrow(&A.res_part, &A.res_part_cap, (int64_t)RES_B * std::max(2 * nb_mv, nb_el)));
+    DCR_TRY(dev_regrow(&A.res_ctl, &A.res_ctl_cap, (int64_t)sizeof(ResCtl)));
+    double *z = A.res_vec, *p = z + n * RES_B, *r = p + n * RES_B, *y = r + n * RES_B, *q = y + n * RES_B;  // 16-byte aligned each
     double *s = q + n * RES_B;
-    ResCtl *ctl = reinterpret_cast<ResCtl *>(g->res_ctl);
-    DCR_HIP(hipMemcpyAsync(g->res_rows, rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
-    spectral_scale(g, s);
+    ResCtl *ctl = reinterpret_cast<ResCtl *>(A.res_ctl);
+    inv_sqrt_degree(g, s);
     DCR_HIP(hipGetLastError());
 
     ResCtl h;
@@ -378,9 +312,9 @@ static int resistance_batches(dcr_graph *g, const std::vector<int2> &info, const
         DCR_HIP(hipStreamSynchronize(g->stream));  // h is reused below
         hipLaunchKernelGGL(k_res_start, dim3((unsigned)nb_el), dim3(256), 0, g->stream, s, n, ctl, z, p, r, y);
         for (int64_t step = 0; step < o.max_steps; ++step) {
-            hipLaunchKernelGGL(k_res_matvec<0>, dim3((unsigned)nb_mv), dim3(256), 0, g->stream, g->rowinfo, g->col, g->res_rows, rc.n_long,
-                               rc.n_mid, rc.n_short, nb_long, nb_mid, p, z, s, q, ctl, g->res_part);
-            hipLaunchKernelGGL(k_res_update, dim3((unsigned)nb_el), dim3(256), 0, g->stream, n, ctl, p, q, y, r, g->res_part);
+            hipLaunchKernelGGL(k_res_matvec<0>, dim3((unsigned)nb_mv), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, p, z, s, q, ctl,
+                               A.res_part);
+            hipLaunchKernelGGL(k_res_update, dim3((unsigned)nb_el), dim3(256), 0, g->stream, n, ctl, p, q, y, r, A.res_part);
             hipLaunchKernelGGL(k_res_direction, dim3((unsigned)nb_el), dim3(256), 0, g->stream, n, ctl, s, r, p, z);
             if ((step + 1) % SP_CHECK_EVERY != 0 && step + 1 != o.max_steps) continue;
             DCR_HIP(hipGetLastError());
@@ -389,8 +323,8 @@ static int resistance_batches(dcr_graph *g, const std::vector<int2> &info, const
             if (h.active == 0) break;
         }
         hipLaunchKernelGGL(k_res_scale_y, dim3((unsigned)nb_el), dim3(256), 0, g->stream, n, s, y, z);
-        hipLaunchKernelGGL(k_res_matvec<1>, dim3((unsigned)nb_mv), dim3(256), 0, g->stream, g->rowinfo, g->col, g->res_rows, rc.n_long,
-                           rc.n_mid, rc.n_short, nb_long, nb_mid, y, z, s, q, ctl, g->res_part);
+        hipLaunchKernelGGL(k_res_matvec<1>, dim3((unsigned)nb_mv), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, y, z, s, q, ctl,
+                           A.res_part);
         DCR_HIP(hipGetLastError());
         DCR_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
@@ -421,11 +355,10 @@ int dcr_effective_resistance(dcr_graph *g, const int32_t *u, const int32_t *v, i
         if (u[i] < 0 || u[i] >= g->n || v[i] < 0 || v[i] >= g->n) DCR_FAIL(DCR_EINVAL, "pair " + std::to_string(i) + ": endpoint outside 0 .. num_nodes - 1");
     if (P == 0) return DCR_OK;
     DCR_HIP(hipSetDevice(g->device));
-    const int64_t n = g->n;
 
     // decided from the components alone: the same node, or no path between the two (an isolated node is its own component)
     std::vector<int32_t> labels;
-    DCR_TRY(spectral_components(g, labels));
+    DCR_TRY(graph_components(g, labels));
     std::vector<int64_t> todo;
     for (int64_t i = 0; i < P; ++i) {
         const bool same = u[i] == v[i];
@@ -438,10 +371,7 @@ int dcr_effective_resistance(dcr_graph *g, const int32_t *u, const int32_t *v, i
         if (out_steps) out_steps[i] = 0;
     }
     if (todo.empty()) return DCR_OK;
-    std::vector<int2> info((size_t)n);
-    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipStreamSynchronize(g->stream));
-    return resistance_batches(g, info, u, v, todo, o, out_lower, out_residual, out_steps);
+    return resistance_batches(g, u, v, todo, o, out_lower, out_residual, out_steps);
 }
 
 }  // extern "C"

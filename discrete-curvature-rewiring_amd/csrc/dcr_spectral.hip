@@ -1,4 +1,4 @@
-// Spectral gap of the normalised Laplacian on the device-resident graph, and the connected components it needs.
+// Spectral gap of the normalised Laplacian on the device-resident graph (the connected components it needs: dcr_analysis.hip).
 //
 // Replaces the dense eigh of the reference's experiment/cheeger_bounds.py:11-21 (normalized_laplacian_matrix, :13; eigh, :15; "the
 // first eigenvalue > 0", :16).  What :16 means is the smallest eigenvalue above the null space of L = I - Â, Â = D^-1/2 A D^-1/2;
@@ -13,10 +13,9 @@
 //
 // Kernels (all fp64, no floating-point atomics: every reduction is per-workgroup partials closed in index order, so the same
 // seed on the same graph returns the same bits):
-//   k_cc_hook / k_cc_compress  min-label hooking + pointer jumping over the live slots; integer only, any schedule, same labels
-//   k_spec_scale, k_spec_start s = 1 / sqrt(deg) from rowinfo; start vector from Philox, counter (node, restart)
-//   k_spec_matvec              w = v + s ⊙ (A z), z = s ⊙ v kept next to v; rows in three degree classes: <= 32 eight lanes a
-//                              row, <= 2048 a wave a row, above that a workgroup a row (those launch first); alpha = v . w
+//   k_spec_start               start vector from Philox, counter (node, restart)
+//   k_spec_matvec              w = v + s ⊙ (A z), z = s ⊙ v kept next to v; rows through walk_rows (dcr_analysis.h): <= 32 eight
+//                              lanes a row, <= 2048 a wave a row, above that a workgroup a row (those launch first); alpha = v . w
 //   k_spec_defl_dot / _apply   w -= sum_C (k_C . w) k_C over chunks of 1024 nodes: one reduction when there is one component,
 //                              the nodes taken through a by-component order otherwise; run before and after Gram-Schmidt, the
 //                              second time with |w|^2 -> beta
@@ -31,7 +30,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "dcr_internal.h"
+#include "dcr_analysis.h"
 #include "dcr_philox.h"
 
 namespace dcr {
@@ -40,53 +39,7 @@ constexpr int SP_WAVE_ELEMS = 512;  // elements of w a wave of k_spec_gs_coef ke
 constexpr int SP_CHUNK = 1024;      // nodes per deflation chunk
 constexpr double SP_BREAKDOWN = 0x1p-40;
 
-// ---- connected components --------------------------------------------------------------------------------------------------------
-__device__ inline int32_t cc_find(const int32_t *label, int32_t x) {
-    for (;;) {  // label[x] <= x always, so this ends at a root
-        const int32_t p = __hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_cc_init(int32_t *label, int64_t n) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v < n) label[v] = (int32_t)v;
-}
-
-// every live slot with col > row: hook the larger root under the smaller.  An atomicMin that lands on a node hooked meanwhile
-// may drop that node's earlier link; the sweeps repeat until one changes nothing, and that last sweep has seen every edge with
-// both ends under one root.
-__global__ void __launch_bounds__(256) k_cc_hook(const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
-                                                  const int32_t *__restrict__ slot_row, int64_t cap_total, int32_t *label, int32_t *changed) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= cap_total) return;
-    const int32_t u = slot_row[s];
-    const int2 ri = rowinfo[u];
-    if (s - ri.x >= (int64_t)ri.y) return;  // slack
-    const int32_t v = col[s];
-    if (v <= u) return;
-    const int32_t ru = cc_find(label, u), rv = cc_find(label, v);
-    if (ru == rv) return;
-    const int32_t hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
-    if (atomicMin(label + hi, lo) > lo) *changed = 1;
-}
-
-__global__ void __launch_bounds__(256) k_cc_compress(int32_t *label, int64_t n) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n) return;
-    const int32_t r = cc_find(label, (int32_t)v);
-    __hip_atomic_store(label + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---- vectors ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_spec_scale(const int2 *__restrict__ rowinfo, double *__restrict__ s, int64_t n) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n) return;
-    const int d = rowinfo[v].y;
-    s[v] = d > 0 ? 1.0 / sqrt((double)d) : 0.0;
-}
-
 // uniform in (-1, 1) from 53 bits of philox4x32_10(node, restart, seed); 0 on isolated nodes
 __global__ void __launch_bounds__(256) k_spec_start(const int2 *__restrict__ rowinfo, double *__restrict__ w, int64_t n, uint64_t restart,
                                                      uint64_t seed) {
@@ -98,59 +51,27 @@ __global__ void __launch_bounds__(256) k_spec_start(const int2 *__restrict__ row
     w[v] = rowinfo[v].y > 0 ? ((double)bits + 0.5) * 0x1p-52 - 1.0 : 0.0;
 }
 
-// rows: the long rows, then the medium ones, then the short ones; workgroups in the same order (the longest work starts first)
-__global__ void __launch_bounds__(256) k_spec_matvec(const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
-                                                      const int32_t *__restrict__ rows, int n_long, int n_mid, int n_short, int nb_long,
-                                                      int nb_mid, const double *__restrict__ v, const double *__restrict__ z,
+using SpecRows = RowGeom<>;  // eight lanes a short row, 32 short rows a workgroup
+
+__global__ void __launch_bounds__(256) k_spec_matvec(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
+                                                      const double *__restrict__ v, const double *__restrict__ z,
                                                       const double *__restrict__ s, double *__restrict__ w, double *part,
                                                       unsigned *ticket, double *alpha_out) {
     __shared__ double sh[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = blockIdx.x;
-    double dot = 0.0;
-    if (b < nb_long) {
-        const int32_t u = rows[b];
-        const int2 ri = rowinfo[u];
+    const int t = threadIdx.x;
+    double dot = 0.0;  // v_u w_u of the row this thread finishes
+    walk_rows<SpecRows>(plan, rowinfo, sh, [=](auto scope, int32_t u, int2 ri, double &vw) {
         double acc = 0.0;
-        for (int j = t; j < ri.y; j += 256) acc += z[col[ri.x + j]];
-        acc = block_sum(acc, sh);
-        if (t == 0) {
+        for (int j = scope.first(); j < ri.y; j += scope.stride) acc += z[col[ri.x + j]];
+        acc = scope.sum(acc);
+        if (scope.owner()) {
             const double vu = v[u], wu = vu + s[u] * acc;
             w[u] = wu;
-            dot = vu * wu;
+            vw = vu * wu;
         }
-    } else if (b < nb_long + nb_mid) {
-        const int i = (b - nb_long) * 4 + wave;
-        if (i < n_mid) {
-            const int32_t u = rows[n_long + i];
-            const int2 ri = rowinfo[u];
-            double acc = 0.0;
-            for (int j = lane; j < ri.y; j += 64) acc += z[col[ri.x + j]];
-            acc = wave_sum(acc);
-            if (lane == 0) {
-                const double vu = v[u], wu = vu + s[u] * acc;
-                w[u] = wu;
-                dot = vu * wu;
-            }
-        }
-    } else {
-        const int i = (b - nb_long - nb_mid) * 32 + (t >> 3), sub = t & 7;
-        const bool ok = i < n_short;
-        const int32_t u = ok ? rows[n_long + n_mid + i] : 0;
-        const int2 ri = ok ? rowinfo[u] : make_int2(0, 0);
-        double acc = 0.0;
-        for (int j = sub; j < ri.y; j += 8) acc += z[col[ri.x + j]];
-        acc += __shfl_xor(acc, 4);
-        acc += __shfl_xor(acc, 2);
-        acc += __shfl_xor(acc, 1);
-        if (ok && sub == 0) {
-            const double vu = v[u], wu = vu + s[u] * acc;
-            w[u] = wu;
-            dot = vu * wu;
-        }
-    }
+    }, dot);
     dot = block_sum(dot, sh);
-    if (t == 0) st_agent(part + b, dot);
+    if (t == 0) st_agent(part + blockIdx.x, dot);
     if (!last_arriver(ticket, (unsigned)gridDim.x)) return;
     const double a = close_partials(part, gridDim.x, sh);
     if (t == 0) {
@@ -345,94 +266,47 @@ static bool top_ritz(const double *alpha, const double *beta, int k, bool full, 
     return true;
 }
 
-// ---- host: components, plan, driver ------------------------------------------------------------------------------------------------
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// labels (smallest node id of the component) into g->spc_label, and onto the host
-int spectral_components(dcr_graph *g, std::vector<int32_t> &labels) {
-    const int64_t n = g->n;
-    labels.resize((size_t)n);
-    if (n == 0) return DCR_OK;
-    DCR_TRY(dev_regrow(&g->spc_label, &g->spc_label_cap, n));
-    DCR_TRY(dev_regrow(&g->spc_ctl, &g->spc_ctl_cap, 4));
-    hipLaunchKernelGGL(k_cc_init, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->spc_label, n);
-    for (int sweep = 0; g->cap_total > 0; ++sweep) {
-        if (sweep > 100000) DCR_FAIL(DCR_ESTATE, "connected components did not settle");
-        DCR_HIP(hipMemsetAsync(g->spc_ctl, 0, 4 * sizeof(int32_t), g->stream));
-        hipLaunchKernelGGL(k_cc_hook, dim3(blocks_of(g->cap_total)), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                           g->cap_total, g->spc_label, (int32_t *)g->spc_ctl);
-        hipLaunchKernelGGL(k_cc_compress, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->spc_label, n);
-        DCR_HIP(hipGetLastError());
-        int32_t changed = 0;
-        DCR_HIP(hipMemcpyAsync(&changed, g->spc_ctl, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-        DCR_HIP(hipStreamSynchronize(g->stream));
-        if (!changed) break;
-    }
-    DCR_HIP(hipMemcpyAsync(labels.data(), g->spc_label, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipStreamSynchronize(g->stream));
-    return DCR_OK;
-}
-
-// rows: the long rows (degree above SP_LONG_DEG), then the medium ones, then the short ones (up to SP_SHORT_DEG), each by node id
-void classify_rows(const std::vector<int2> &info, std::vector<int32_t> &rows, RowClasses *rc) {
-    const int64_t n = (int64_t)info.size();
-    rows.resize((size_t)n);
-    int64_t nl = 0, nm = 0, ns = 0;
-    for (int64_t v = 0; v < n; ++v) {
-        const int d = info[(size_t)v].y;
-        (d > SP_LONG_DEG ? nl : d > SP_SHORT_DEG ? nm : ns)++;
-    }
-    int64_t pl = 0, pm = nl, ps = nl + nm;
-    for (int64_t v = 0; v < n; ++v) {
-        const int d = info[(size_t)v].y;
-        rows[(size_t)(d > SP_LONG_DEG ? pl : d > SP_SHORT_DEG ? pm : ps)++] = (int32_t)v;
-    }
-    rc->n_long = (int)nl;
-    rc->n_mid = (int)nm;
-    rc->n_short = (int)ns;
-}
-
-void spectral_scale(dcr_graph *g, double *s) {
-    hipLaunchKernelGGL(k_spec_scale, dim3(blocks_of(g->n)), dim3(256), 0, g->stream, g->rowinfo, s, g->n);
-}
-
+// ---- host: plan, driver ------------------------------------------------------------------------------------------------------------
 void spectral_release_basis(dcr_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->spc_basis) (void)hipFree(g->spc_basis);
-    g->spc_basis = nullptr;
-    g->spc_basis_cap = 0;
+    AnalysisState *A = g->analysis;
+    if (!A) return;
+    if (A->spc_basis) (void)hipFree(A->spc_basis);
+    A->spc_basis = nullptr;
+    A->spc_basis_cap = 0;
 }
 
 struct SpecRun {
     dcr_graph *g;
+    AnalysisState *A;
     int64_t n;
-    int n_long, n_mid, n_short, nb_long, nb_mid, nb_mv;
+    RowPlan plan;
     int n_chunks, n_waves;
     bool one;
-    double *s, *kd, *z, *w;         // [n] each, in g->spc_vec
-    double *alpha, *beta, *scal, *coef, *ritz;  // in g->spc_small
-    int32_t *rows, *order;
+    double *s, *kd, *z, *w;         // [n] each, in spc_vec
+    double *alpha, *beta, *scal, *coef, *ritz;  // in spc_small
+    int32_t *order;
     unsigned *ticket;
 
-    double *col(int j) const { return g->spc_basis + (int64_t)j * n; }
+    double *col(int j) const { return A->spc_basis + (int64_t)j * n; }
     // w -= sum_C (k_C . w) k_C; with beta_out also *beta_out = |w| afterwards
     void deflate(double *beta_out) const {
         if (one) {
-            hipLaunchKernelGGL(k_spec_defl_dot<true>, dim3(n_chunks), dim3(256), 0, g->stream, g->spc_chunks, order, kd, w, g->spc_part);
-            hipLaunchKernelGGL(k_spec_defl_apply<true>, dim3(n_chunks), dim3(256), 0, g->stream, g->spc_chunks, order, kd, w, g->spc_part,
+            hipLaunchKernelGGL(k_spec_defl_dot<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part);
+            hipLaunchKernelGGL(k_spec_defl_apply<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part,
                                ticket, beta_out);
         } else {
-            hipLaunchKernelGGL(k_spec_defl_dot<false>, dim3(n_chunks), dim3(256), 0, g->stream, g->spc_chunks, order, kd, w, g->spc_part);
-            hipLaunchKernelGGL(k_spec_defl_apply<false>, dim3(n_chunks), dim3(256), 0, g->stream, g->spc_chunks, order, kd, w, g->spc_part,
+            hipLaunchKernelGGL(k_spec_defl_dot<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part);
+            hipLaunchKernelGGL(k_spec_defl_apply<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part,
                                ticket, beta_out);
         }
     }
     // w orthogonal to columns 0 .. jc - 1: classical Gram-Schmidt, twice
     void orthogonalise(int jc) const {
         for (int pass = 0; pass < 2; ++pass) {
-            hipLaunchKernelGGL(k_spec_gs_coef, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, g->stream, g->spc_basis, w, n, jc,
-                               n_waves, g->spc_part, coef, ticket);
-            hipLaunchKernelGGL(k_spec_gs_apply, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->spc_basis, w, n, jc, coef);
+            hipLaunchKernelGGL(k_spec_gs_coef, dim3(blocks_of(n_waves, 4)), dim3(256), 0, g->stream, A->spc_basis, w, n, jc,
+                               n_waves, A->spc_part, coef, ticket);
+            hipLaunchKernelGGL(k_spec_gs_apply, dim3(blocks_of(n)), dim3(256), 0, g->stream, A->spc_basis, w, n, jc, coef);
         }
     }
     void normalise(const double *beta_in, int j) const {
@@ -445,8 +319,8 @@ struct SpecRun {
     }
     // Lanczos step j: alpha[j], beta[j], and column j + 1 when there is room for it
     void step(int j, int m) const {
-        hipLaunchKernelGGL(k_spec_matvec, dim3((unsigned)nb_mv), dim3(256), 0, g->stream, g->rowinfo, g->col, rows, n_long, n_mid, n_short,
-                           nb_long, nb_mid, col(j), z, s, w, g->spc_part, ticket, alpha + j);
+        hipLaunchKernelGGL(k_spec_matvec, dim3(row_grid<SpecRows>(plan)), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, col(j), z, s, w,
+                           A->spc_part, ticket, alpha + j);
         // The deflation comes LAST.  Each column carries a rounding-size component along the k_C; Gram-Schmidt hands w the sum
         // of those, weighted by alpha and beta, and with nothing behind it that component obeys the Lanczos recurrence of an
         // eigenvalue inside the spectrum (P B P k = 0) and doubles per step, while alpha = v . B v goes on treating k as
@@ -460,7 +334,7 @@ struct SpecRun {
 
 // The whole of dcr_spectral_gap but for the download of the vector: the accepted Ritz vector stays in column 0 of the basis, which
 // stays allocated until spectral_release_basis.
-int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept) {
+int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, SpectralKept *kept, RowPlan *plan) {
     if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
     dcr_spectral_opts o = {1e-10, 20000, 0, 0};
     if (opts) o = *opts;
@@ -471,10 +345,9 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
 
     // components, degrees, the null-space vectors
     std::vector<int32_t> labels;
-    DCR_TRY(spectral_components(g, labels));
-    std::vector<int2> info((size_t)n);
-    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipStreamSynchronize(g->stream));
+    DCR_TRY(graph_components(g, labels));
+    std::vector<int2> info;
+    DCR_TRY(build_row_plan(g, plan, &info));
     int64_t components = 0;
     std::vector<int32_t> cidx((size_t)n, -1);  // component with an edge -> its index, by smallest node id
     std::vector<int64_t> vol;
@@ -493,9 +366,12 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
     for (int64_t v = 0; v < n; ++v)
         if (info[(size_t)v].y > 0) kd[(size_t)v] = std::sqrt((double)info[(size_t)v].y) / std::sqrt((double)vol[(size_t)cidx[(size_t)labels[(size_t)v]]]);
 
+    AnalysisState &A = analysis_of(g);
     SpecRun R;
     R.g = g;
+    R.A = &A;
     R.n = n;
+    R.plan = *plan;
     R.one = n_comp == 1;
     // deflation chunks
     std::vector<int4> chunks;
@@ -520,16 +396,6 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
         }
     }
     R.n_chunks = (int)chunks.size();
-    // rows by degree class
-    std::vector<int32_t> rows;
-    RowClasses rc;
-    classify_rows(info, rows, &rc);
-    R.n_long = rc.n_long;
-    R.n_mid = rc.n_mid;
-    R.n_short = rc.n_short;
-    R.nb_long = rc.n_long;
-    R.nb_mid = (rc.n_mid + 3) / 4;
-    R.nb_mv = R.nb_long + R.nb_mid + (rc.n_short + 31) / 32;
     // basis capacity
     const int64_t by_memory = ((int64_t)4 << 30) / (8 * n);
     int64_t m = o.max_basis > 0 ? std::min(o.max_basis, std::max<int64_t>(by_memory, 16)) : std::max<int64_t>(std::min<int64_t>(256, by_memory), 16);
@@ -538,33 +404,31 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
     R.n_waves = (int)((n + SP_WAVE_ELEMS - 1) / SP_WAVE_ELEMS);
 
     // buffers
-    DCR_TRY(dev_regrow(&g->spc_vec, &g->spc_vec_cap, 4 * n));
-    DCR_TRY(dev_regrow(&g->spc_basis, &g->spc_basis_cap, m * n));
-    DCR_TRY(dev_regrow(&g->spc_rows, &g->spc_rows_cap, 2 * n));
-    DCR_TRY(dev_regrow(&g->spc_chunks, &g->spc_chunks_cap, (int64_t)chunks.size()));
-    const int64_t part_need = std::max<int64_t>({(int64_t)R.n_waves * m, (int64_t)R.nb_mv, 2 * (int64_t)R.n_chunks});
-    DCR_TRY(dev_regrow(&g->spc_part, &g->spc_part_cap, part_need));
-    DCR_TRY(dev_regrow(&g->spc_small, &g->spc_small_cap, 4 * m + 8));
-    DCR_TRY(dev_regrow(&g->spc_ctl, &g->spc_ctl_cap, 4));
-    R.s = g->spc_vec;
-    R.kd = g->spc_vec + n;
-    R.z = g->spc_vec + 2 * n;
-    R.w = g->spc_vec + 3 * n;
-    R.alpha = g->spc_small;
-    R.beta = g->spc_small + m;
-    R.scal = g->spc_small + 2 * m;  // 8 scalars
-    R.coef = g->spc_small + 2 * m + 8;
-    R.ritz = g->spc_small + 3 * m + 8;
-    R.rows = g->spc_rows;
-    R.order = g->spc_rows + n;
-    R.ticket = g->spc_ctl + 1;
-    DCR_HIP(hipMemsetAsync(g->spc_ctl, 0, 4 * sizeof(unsigned), g->stream));
+    DCR_TRY(dev_regrow(&A.spc_vec, &A.spc_vec_cap, 4 * n));
+    DCR_TRY(dev_regrow(&A.spc_basis, &A.spc_basis_cap, m * n));
+    DCR_TRY(dev_regrow(&A.spc_rows, &A.spc_rows_cap, n));
+    DCR_TRY(dev_regrow(&A.spc_chunks, &A.spc_chunks_cap, (int64_t)chunks.size()));
+    const int64_t part_need = std::max<int64_t>({(int64_t)R.n_waves * m, (int64_t)row_grid<SpecRows>(*plan), 2 * (int64_t)R.n_chunks});
+    DCR_TRY(dev_regrow(&A.spc_part, &A.spc_part_cap, part_need));
+    DCR_TRY(dev_regrow(&A.spc_small, &A.spc_small_cap, 4 * m + 8));
+    DCR_TRY(dev_regrow(&A.spc_ctl, &A.spc_ctl_cap, 4));
+    R.s = A.spc_vec;
+    R.kd = A.spc_vec + n;
+    R.z = A.spc_vec + 2 * n;
+    R.w = A.spc_vec + 3 * n;
+    R.alpha = A.spc_small;
+    R.beta = A.spc_small + m;
+    R.scal = A.spc_small + 2 * m;  // 8 scalars
+    R.coef = A.spc_small + 2 * m + 8;
+    R.ritz = A.spc_small + 3 * m + 8;
+    R.order = A.spc_rows;
+    R.ticket = A.spc_ctl + 1;
+    DCR_HIP(hipMemsetAsync(A.spc_ctl, 0, 4 * sizeof(unsigned), g->stream));
     DCR_HIP(hipMemcpyAsync(R.kd, kd.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, g->stream));
-    DCR_HIP(hipMemcpyAsync(R.rows, rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
     if (!order.empty())
         DCR_HIP(hipMemcpyAsync(R.order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, g->stream));
-    DCR_HIP(hipMemcpyAsync(g->spc_chunks, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
-    spectral_scale(g, R.s);
+    DCR_HIP(hipMemcpyAsync(A.spc_chunks, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
+    inv_sqrt_degree(g, R.s);
     hipLaunchKernelGGL(k_spec_start, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, R.w, n, (uint64_t)0, o.seed);
     R.first_column();
     DCR_HIP(hipGetLastError());
@@ -581,7 +445,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
             const bool forced = total >= o.max_steps - 1;
             if (!(j == 0 || (j + 1) % SP_CHECK_EVERY == 0 || j + 1 == m || forced)) continue;
             DCR_HIP(hipGetLastError());
-            DCR_HIP(hipMemcpyAsync(ab.data(), g->spc_small, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, g->stream));
+            DCR_HIP(hipMemcpyAsync(ab.data(), A.spc_small, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, g->stream));
             DCR_HIP(hipStreamSynchronize(g->stream));
             const double *alpha = ab.data(), *beta = ab.data() + m;
             if (j == 0) {  // column 0 is a unit vector of the deflated space: its Rayleigh quotient and its true residual
@@ -612,7 +476,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
             if (!top_ritz(alpha, beta, k, true, &th, vec)) DCR_FAIL(DCR_ESTATE, "spectral gap: the tridiagonal QL iteration did not converge");
             DCR_HIP(hipMemcpyAsync(R.ritz, vec.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, g->stream));
             DCR_HIP(hipStreamSynchronize(g->stream));
-            hipLaunchKernelGGL(k_spec_combine, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->spc_basis, R.ritz, n, k, R.w);
+            hipLaunchKernelGGL(k_spec_combine, dim3(blocks_of(n)), dim3(256), 0, g->stream, A.spc_basis, R.ritz, n, k, R.w);
             R.first_column();
             ++restarts;
             last_cycle = breakdown || forced;
@@ -622,8 +486,6 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
     DCR_HIP(hipStreamSynchronize(g->stream));
     kept->y = R.col(0);
     kept->s = R.s;
-    kept->rows = R.rows;
-    kept->rc = rc;
     out->lambda1 = 2.0 - theta;
     out->residual = residual;
     out->steps = total;
@@ -639,23 +501,10 @@ using namespace dcr;
 
 extern "C" {
 
-int dcr_connected_components(dcr_graph *g, int32_t *out_labels, int64_t *out_count) {
-    if (!g || !out_labels || !out_count) DCR_FAIL(DCR_EINVAL, "null argument");
-    DCR_HIP(hipSetDevice(g->device));
-    std::vector<int32_t> labels;
-    DCR_TRY(spectral_components(g, labels));
-    int64_t c = 0;
-    for (int64_t v = 0; v < g->n; ++v) {
-        out_labels[v] = labels[(size_t)v];
-        c += labels[(size_t)v] == v;
-    }
-    *out_count = c;
-    return DCR_OK;
-}
-
 int dcr_spectral_gap(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_result *out, double *out_vector) {
     SpectralKept kept;
-    int rc = spectral_solve(g, opts, out, &kept);
+    RowPlan plan;
+    int rc = spectral_solve(g, opts, out, &kept, &plan);
     if (rc == DCR_OK && out_vector) {
         hipError_t e = hipMemcpyAsync(out_vector, kept.y, sizeof(double) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);

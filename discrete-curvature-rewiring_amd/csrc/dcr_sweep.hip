@@ -1,7 +1,7 @@
 // Sweep cut on the device-resident graph: the constructive half of Cheeger's inequality.
 //
 // Given a score per node, the nodes are ordered ascending by (score, node id) and every prefix S_k of that order, k = 1 .. n - 1, is
-// valued by one of the two ratios of dcr_cheeger.hip (k_cheeger_values); the smallest value and the smallest k that has it are
+// valued by one of the two ratios of k_cheeger_values (cheeger_ratio, dcr_analysis.h); the smallest value and the smallest k that has it are
 // returned.  With the score x = D^-1/2 y, y the eigenvector dcr_spectral.hip accepts for lambda_1, the best prefix is a set with
 // lambda_1 / 2 <= h <= conductance(S_k) <= sqrt(2 lambda_1): a certificate for the bracket of experiment/cheeger_bounds.py.  The
 // reference has no counterpart.  Everything up to the one division per prefix is integer arithmetic, so the result does not depend
@@ -20,7 +20,7 @@
 //                     ballots) and a popcount of the lower lanes on top of the wave's running per-digit offset: a STABLE scatter, so
 //                     ties keep the input's id order through every pass
 //   k_sweep_rank      rank[order[p]] = p
-//   k_sweep_edges     every live slot with col > row, rows in the three degree classes of k_spec_matvec; with p = rank[row],
+//   k_sweep_edges     every live slot with col > row, rows through walk_rows in the three degree classes; with p = rank[row],
 //                     q = rank[col]: p < q: the edge is `lo` for k in [p + 1, q], q < p: `hi` for k in [q + 1, p], `in` from
 //                     k = max(p, q) + 1, as +-1 into three int32 difference arrays indexed by k - 1 (integer atomics); what lands on
 //                     the row's own rank is summed over the row first and added once
@@ -30,7 +30,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "dcr_internal.h"
+#include "dcr_analysis.h"
 
 namespace dcr {
 
@@ -51,12 +51,6 @@ struct SweepDev {
     int32_t pad[2];
 };
 static_assert(sizeof(SweepDev) == 32, "result block is 8 words");
-
-__device__ inline int32_t wave_sum_i32(int32_t x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
 
 __device__ inline int32_t wave_incl_scan(int32_t x, int lane) {
 #pragma unroll
@@ -184,7 +178,7 @@ __global__ void __launch_bounds__(256) k_scan_reduce(const int32_t *__restrict__
     int32_t acc = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) acc += i0 + q < len ? a[i0 + q] : 0;
-    acc = wave_sum_i32(acc);
+    acc = wave_sum(acc);
     if ((t & 63) == 0) sh[t >> 6] = acc;
     __syncthreads();
     if (t == 0) __hip_atomic_store(part + (int64_t)y * nb + blockIdx.x, sh[0] + sh[1] + sh[2] + sh[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -247,68 +241,27 @@ __device__ inline void sweep_row_own(int32_t p, int up, int down, int32_t *d_in,
     }
 }
 
-__global__ void __launch_bounds__(256) k_sweep_edges(const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col, const int32_t *__restrict__ rows,
-                                                      int n_long, int n_mid, int n_short, int nb_long, int nb_mid,
+using SweepRows = RowGeom<>;  // eight lanes a short row, 32 short rows a workgroup
+
+__global__ void __launch_bounds__(256) k_sweep_edges(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
                                                       const int32_t *__restrict__ rank, int32_t *d_in, int32_t *d_lo, int32_t *d_hi) {
-    __shared__ int32_t sh[2][4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = blockIdx.x;
-    int up = 0, down = 0;
-    if (b < nb_long) {
-        const int32_t u = rows[b];
-        const int2 ri = rowinfo[u];
+    __shared__ int32_t sh[4];
+    walk_rows<SweepRows>(plan, rowinfo, sh, [=](auto scope, int32_t u, int2 ri) {
         const int32_t p = rank[u];
-        for (int j = t; j < ri.y; j += 256) {
+        int32_t up = 0, down = 0;
+        for (int j = scope.first(); j < ri.y; j += scope.stride) {
             const int r = sweep_slot(u, p, col[ri.x + j], rank, d_in, d_lo, d_hi);
             up += r == 1;
             down += r == 2;
         }
-        up = wave_sum_i32(up);
-        down = wave_sum_i32(down);
-        if (lane == 0) {
-            sh[0][wave] = up;
-            sh[1][wave] = down;
-        }
-        __syncthreads();
-        if (t == 0) sweep_row_own(p, sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3], sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3], d_in, d_lo, d_hi);
-    } else if (b < nb_long + nb_mid) {
-        const int i = (b - nb_long) * 4 + wave;
-        if (i < n_mid) {
-            const int32_t u = rows[n_long + i];
-            const int2 ri = rowinfo[u];
-            const int32_t p = rank[u];
-            for (int j = lane; j < ri.y; j += 64) {
-            const int r = sweep_slot(u, p, col[ri.x + j], rank, d_in, d_lo, d_hi);
-            up += r == 1;
-            down += r == 2;
-        }
-            up = wave_sum_i32(up);
-            down = wave_sum_i32(down);
-            if (lane == 0) sweep_row_own(p, up, down, d_in, d_lo, d_hi);
-        }
-    } else {
-        const int i = (b - nb_long - nb_mid) * 32 + (t >> 3), sub = t & 7;
-        const bool ok = i < n_short;
-        const int32_t u = ok ? rows[n_long + n_mid + i] : 0;
-        const int2 ri = ok ? rowinfo[u] : make_int2(0, 0);
-        const int32_t p = ok ? rank[u] : 0;
-        for (int j = sub; j < ri.y; j += 8) {
-            const int r = sweep_slot(u, p, col[ri.x + j], rank, d_in, d_lo, d_hi);
-            up += r == 1;
-            down += r == 2;
-        }
-        up += __shfl_xor(up, 4);
-        up += __shfl_xor(up, 2);
-        up += __shfl_xor(up, 1);
-        down += __shfl_xor(down, 4);
-        down += __shfl_xor(down, 2);
-        down += __shfl_xor(down, 1);
-        if (ok && sub == 0) sweep_row_own(p, up, down, d_in, d_lo, d_hi);
-    }
+        up = scope.sum(up);
+        down = scope.sum(down);
+        if (scope.owner()) sweep_row_own(p, up, down, d_in, d_lo, d_hi);
+    });
 }
 
 // ---- values and the arg-min --------------------------------------------------------------------------------------------------------
-// c_*: inclusive prefix sums, element k - 1 = the count of S_k; n1 = n - 1 prefixes.  The two ratios of k_cheeger_values.
+// c_*: inclusive prefix sums, element k - 1 = the count of S_k; n1 = n - 1 prefixes.
 __global__ void __launch_bounds__(256) k_sweep_value(const int32_t *__restrict__ c_in, const int32_t *__restrict__ c_lo, const int32_t *__restrict__ c_hi,
                                                       int64_t n1, int64_t n_edges, int definition, double *__restrict__ profile, Ext *part,
                                                       unsigned *ticket, SweepDev *result) {
@@ -317,11 +270,7 @@ __global__ void __launch_bounds__(256) k_sweep_value(const int32_t *__restrict__
     double bv = 0.0;
     int bs = -1;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n1; i += (int64_t)gridDim.x * 256) {
-        const int64_t in = c_in[i], lo = c_lo[i], hi = c_hi[i];
-        const int64_t outside = n_edges - in - lo - hi;
-        const int64_t cut = definition ? lo + hi : lo, extra = definition ? lo + hi : 0;
-        const int64_t va = 2 * in + extra, vb = 2 * outside + extra, m = va < vb ? va : vb;
-        const double val = m == 0 ? __builtin_inf() : (double)cut / (double)m;
+        const double val = cheeger_ratio(c_in[i], c_lo[i], c_hi[i], n_edges, definition);
         profile[i] = val;
         ext_take(bv, bs, val, (int)i, 0);
     }
@@ -351,13 +300,11 @@ __global__ void __launch_bounds__(256) k_sweep_value(const int32_t *__restrict__
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
-static unsigned sw_blocks(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
-
 struct SweepPlan {
     int64_t n;
     int tile, tiles, nb_table, nb_diff;
     uint64_t *keys[2];
-    int32_t *ids[2], *rank, *diff, *rows, *table, *part, *boff;
+    int32_t *ids[2], *rank, *diff, *table, *part, *boff;
     double *score, *profile;
     unsigned *ctl;
 };
@@ -370,37 +317,37 @@ static int sweep_buffers(dcr_graph *g, SweepPlan *P) {
     P->tile = (int)tile;
     P->tiles = (int)((n + tile - 1) / tile);
     const int64_t table_len = (int64_t)256 * P->tiles;
-    P->nb_table = (int)sw_blocks(table_len, SW_SCAN_BLOCK);
-    P->nb_diff = (int)sw_blocks(n, SW_SCAN_BLOCK);
+    P->nb_table = (int)blocks_of(table_len, SW_SCAN_BLOCK);
+    P->nb_diff = (int)blocks_of(n, SW_SCAN_BLOCK);
     const int64_t nb_most = std::max<int64_t>(P->nb_table, 3 * (int64_t)P->nb_diff);
-    DCR_TRY(dev_regrow(&g->swp_keys, &g->swp_keys_cap, 2 * n));
-    DCR_TRY(dev_regrow(&g->swp_idx, &g->swp_idx_cap, 7 * n));
-    DCR_TRY(dev_regrow(&g->swp_table, &g->swp_table_cap, table_len + 2 * nb_most));
-    DCR_TRY(dev_regrow(&g->swp_f64, &g->swp_f64_cap, 2 * n));
-    DCR_TRY(dev_regrow(&g->swp_ctl, &g->swp_ctl_cap, SW_CTL_WORDS));
-    P->keys[0] = g->swp_keys;
-    P->keys[1] = g->swp_keys + n;
-    P->ids[0] = g->swp_idx;
-    P->ids[1] = g->swp_idx + n;
-    P->rank = g->swp_idx + 2 * n;
-    P->diff = g->swp_idx + 3 * n;
-    P->rows = g->swp_idx + 6 * n;
-    P->table = g->swp_table;
-    P->part = g->swp_table + table_len;
+    AnalysisState &A = analysis_of(g);
+    DCR_TRY(dev_regrow(&A.swp_keys, &A.swp_keys_cap, 2 * n));
+    DCR_TRY(dev_regrow(&A.swp_idx, &A.swp_idx_cap, 6 * n));
+    DCR_TRY(dev_regrow(&A.swp_table, &A.swp_table_cap, table_len + 2 * nb_most));
+    DCR_TRY(dev_regrow(&A.swp_f64, &A.swp_f64_cap, 2 * n));
+    DCR_TRY(dev_regrow(&A.swp_ctl, &A.swp_ctl_cap, SW_CTL_WORDS));
+    P->keys[0] = A.swp_keys;
+    P->keys[1] = A.swp_keys + n;
+    P->ids[0] = A.swp_idx;
+    P->ids[1] = A.swp_idx + n;
+    P->rank = A.swp_idx + 2 * n;
+    P->diff = A.swp_idx + 3 * n;
+    P->table = A.swp_table;
+    P->part = A.swp_table + table_len;
     P->boff = P->part + nb_most;
-    P->score = g->swp_f64;
-    P->profile = g->swp_f64 + n;
-    P->ctl = g->swp_ctl;
+    P->score = A.swp_f64;
+    P->profile = A.swp_f64 + n;
+    P->ctl = A.swp_ctl;
     return DCR_OK;
 }
 
-// the score is in P.score; rows: the graph's rows by degree class (device)
-static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const int32_t *rows, const RowClasses &rc, dcr_sweep_result *out,
-                     int32_t *out_order, double *out_profile) {
+// the score is in P.score; rows: the graph's row plan
+static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const RowPlan &rows, dcr_sweep_result *out, int32_t *out_order,
+                     double *out_profile) {
     const int64_t n = P.n;
     hipStream_t st = g->stream;
     DCR_HIP(hipMemsetAsync(P.ctl, 0, sizeof(unsigned) * SW_CTL_WORDS, st));
-    hipLaunchKernelGGL(k_sweep_keys, dim3(std::min(sw_blocks(n, 256), 1024u)), dim3(256), 0, st, P.score, n, P.keys[0], P.ids[0],
+    hipLaunchKernelGGL(k_sweep_keys, dim3(std::min(blocks_of(n), 1024u)), dim3(256), 0, st, P.score, n, P.keys[0], P.ids[0],
                        P.ctl + SW_CTL_HIST, P.ctl + SW_CTL_NAN);
     DCR_HIP(hipGetLastError());
     std::vector<unsigned> head((size_t)SW_CTL_RESULT);
@@ -412,28 +359,26 @@ static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const int
         bool one_digit = false;
         for (int d = 0; d < 256; ++d) one_digit = one_digit || head[(size_t)(SW_CTL_HIST + pass * 256 + d)] == (unsigned)n;
         if (one_digit) continue;  // the pass would move nothing
-        hipLaunchKernelGGL(k_sweep_hist, dim3(sw_blocks(P.tiles, 4)), dim3(256), 0, st, P.keys[cur], n, 8 * pass, P.tile, P.tiles, P.table);
+        hipLaunchKernelGGL(k_sweep_hist, dim3(blocks_of(P.tiles, 4)), dim3(256), 0, st, P.keys[cur], n, 8 * pass, P.tile, P.tiles, P.table);
         hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)P.nb_table, 1), dim3(256), 0, st, P.table, (int64_t)256 * P.tiles, (int64_t)0,
                            P.nb_table, P.part, P.boff, P.ctl + SW_CTL_TICKETS);
         hipLaunchKernelGGL(k_scan_apply<false>, dim3((unsigned)P.nb_table, 1), dim3(256), 0, st, P.table, (int64_t)256 * P.tiles, (int64_t)0,
                            P.nb_table, P.boff);
-        hipLaunchKernelGGL(k_sweep_scatter, dim3(sw_blocks(P.tiles, 4)), dim3(256), 0, st, P.keys[cur], P.ids[cur], P.keys[cur ^ 1],
+        hipLaunchKernelGGL(k_sweep_scatter, dim3(blocks_of(P.tiles, 4)), dim3(256), 0, st, P.keys[cur], P.ids[cur], P.keys[cur ^ 1],
                            P.ids[cur ^ 1], n, 8 * pass, P.tile, P.tiles, P.table);
         cur ^= 1;
     }
     const int32_t *order = P.ids[cur];
     int32_t *d_in = P.diff, *d_lo = P.diff + n, *d_hi = P.diff + 2 * n;
-    hipLaunchKernelGGL(k_sweep_rank, dim3(sw_blocks(n, 256)), dim3(256), 0, st, order, P.rank, n);
+    hipLaunchKernelGGL(k_sweep_rank, dim3(blocks_of(n)), dim3(256), 0, st, order, P.rank, n);
     DCR_HIP(hipMemsetAsync(P.diff, 0, sizeof(int32_t) * 3 * (size_t)n, st));
-    const int nb_long = rc.n_long, nb_mid = (rc.n_mid + 3) / 4, nb_all = nb_long + nb_mid + (rc.n_short + 31) / 32;
     if (g->n_edges > 0)
-        hipLaunchKernelGGL(k_sweep_edges, dim3((unsigned)nb_all), dim3(256), 0, st, g->rowinfo, g->col, rows, rc.n_long, rc.n_mid, rc.n_short,
-                           nb_long, nb_mid, P.rank, d_in, d_lo, d_hi);
+        hipLaunchKernelGGL(k_sweep_edges, dim3(row_grid<SweepRows>(rows)), dim3(256), 0, st, rows, g->rowinfo, g->col, P.rank, d_in, d_lo, d_hi);
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)P.nb_diff, 3), dim3(256), 0, st, P.diff, n, n, P.nb_diff, P.part, P.boff,
                        P.ctl + SW_CTL_TICKETS);
     hipLaunchKernelGGL(k_scan_apply<true>, dim3((unsigned)P.nb_diff, 3), dim3(256), 0, st, P.diff, n, n, P.nb_diff, P.boff);
     SweepDev *res_dev = (SweepDev *)(P.ctl + SW_CTL_RESULT);
-    hipLaunchKernelGGL(k_sweep_value, dim3(std::min(sw_blocks(n - 1, 256), (unsigned)SW_VALUE_BLOCKS)), dim3(256), 0, st, d_in, d_lo, d_hi, n - 1,
+    hipLaunchKernelGGL(k_sweep_value, dim3(std::min(blocks_of(n - 1), (unsigned)SW_VALUE_BLOCKS)), dim3(256), 0, st, d_in, d_lo, d_hi, n - 1,
                        g->n_edges, definition, P.profile, (Ext *)(P.ctl + SW_CTL_PARTS), P.ctl + SW_CTL_TICKETS + 3, res_dev);
     DCR_HIP(hipGetLastError());
     SweepDev res;
@@ -471,15 +416,10 @@ int dcr_sweep_cut(dcr_graph *g, const double *score, int definition, dcr_sweep_r
     DCR_HIP(hipSetDevice(g->device));
     SweepPlan P;
     DCR_TRY(sweep_buffers(g, &P));
-    std::vector<int2> info((size_t)n);
-    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipStreamSynchronize(g->stream));
-    std::vector<int32_t> rows;
-    RowClasses rc;
-    classify_rows(info, rows, &rc);
-    DCR_HIP(hipMemcpyAsync(P.rows, rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+    RowPlan rows;
+    DCR_TRY(build_row_plan(g, &rows, nullptr));
     DCR_HIP(hipMemcpyAsync(P.score, score, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, g->stream));
-    return sweep_run(g, P, definition, P.rows, rc, out, out_order, out_profile);
+    return sweep_run(g, P, definition, rows, out, out_order, out_profile);
 }
 
 int dcr_fiedler_sweep(dcr_graph *g, const dcr_spectral_opts *opts, int definition, dcr_spectral_result *out_gap, dcr_sweep_result *out,
@@ -487,13 +427,14 @@ int dcr_fiedler_sweep(dcr_graph *g, const dcr_spectral_opts *opts, int definitio
     DCR_TRY(sweep_args(g, definition, out));
     if (!out_gap) DCR_FAIL(DCR_EINVAL, "null argument");
     SpectralKept kept;
-    int rc = spectral_solve(g, opts, out_gap, &kept);
+    RowPlan rows;  // the solver's
+    int rc = spectral_solve(g, opts, out_gap, &kept, &rows);
     if (rc == DCR_OK) {
         SweepPlan P;
         rc = sweep_buffers(g, &P);
         if (rc == DCR_OK) {
-            hipLaunchKernelGGL(k_sweep_score, dim3(sw_blocks(g->n, 256)), dim3(256), 0, g->stream, kept.s, kept.y, P.score, g->n);
-            rc = sweep_run(g, P, definition, kept.rows, kept.rc, out, out_order, nullptr);
+            hipLaunchKernelGGL(k_sweep_score, dim3(blocks_of(g->n)), dim3(256), 0, g->stream, kept.s, kept.y, P.score, g->n);
+            rc = sweep_run(g, P, definition, rows, out, out_order, nullptr);
         }
         if (rc == DCR_OK && out_score) {
             hipError_t e = hipMemcpyAsync(out_score, P.score, sizeof(double) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream);

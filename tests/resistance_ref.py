@@ -112,8 +112,13 @@ class Dense:
 
     @property
     def pinv(self):
+        # np.linalg.pinv(hermitian=True) with the null space cut by its known dimension, one eigenvalue per component, where
+        # numpy cuts at 1e-15 max|w|: with a hub of degree 2,049 a zero eigenvalue came out as -4.9e-12, above that cut-off,
+        # and its reciprocal put 3e-8 into the resistances (tests/test_row_classes_gpu.py has the graph)
         if self._pinv is None:
-            self._pinv = np.linalg.pinv(np.diag(self.deg) - self.a, hermitian=True)
+            w, v = np.linalg.eigh(np.diag(self.deg) - self.a)
+            keep = np.sort(np.argsort(np.abs(w), kind='stable')[self.count:])
+            self._pinv = (v[:, keep] / w[keep]) @ v[:, keep].T
         return self._pinv
 
     def resistance(self, pairs):

@@ -114,6 +114,16 @@ def barbell(m1, m2):
     return _und(left + chain + right, 2 * m1 + m2)
 
 
+def row_classes_graph():
+    """Rows on both sides of both degree limits of the kernels that walk the rows by class (32 and 2,048), in three components:
+    hubs 0..3 of degree 32, 33, 2,048 and 2,049, not adjacent to each other, each joined to the first d of the 2,049 leaves
+    4..2052 (a leaf has degree 1 to 4); the triangle 2053-2054-2055; the isolated node 2056."""
+    hubs = (32, 33, 2048, 2049)
+    pairs = [(h, 4 + i) for h, d in enumerate(hubs) for i in range(d)]
+    t = 4 + max(hubs)
+    return _und(pairs + [(t, t + 1), (t, t + 2), (t + 1, t + 2)], t + 4)
+
+
 def closed_forms():
     """(name, (edge_index, n), lambda_1)"""
     return [
