@@ -124,6 +124,90 @@ def row_classes_graph():
     return _und(pairs + [(t, t + 1), (t, t + 2), (t + 1, t + 2)], t + 4)
 
 
+# ---- the row plan of the analysis kernels, and graphs with planned class counts ------------------------------------------------
+SHORT_DEG = 32     # csrc/dcr_analysis.h: SP_SHORT_DEG, rows up to this degree are short
+LONG_DEG = 2048    # SP_LONG_DEG, rows above this degree are long (tests/test_row_classes_cpu.py reads both out of the source)
+
+
+def row_plan(edge_index, n):
+    """((n_long, n_mid, n_short), rows): what csrc/dcr_analysis.hip::classify_rows makes of the graph; rows holds the long rows,
+    then the medium ones, then the short ones, each by node id."""
+    _, deg = normalised_adjacency(edge_index, n)
+    long_, short = deg > LONG_DEG, deg <= SHORT_DEG
+    classes = [np.flatnonzero(long_), np.flatnonzero(~long_ & ~short), np.flatnonzero(short)]
+    return tuple(int(c.size) for c in classes), np.concatenate(classes).astype(np.int32)
+
+
+def planned_graph(hub_degrees, hub_edges=(), n_short=None, isolated=0, seed=0):
+    """Hubs over shared leaves, as row_classes_graph: hub h has degree hub_degrees[h], of which its edges in hub_edges (pairs of
+    hubs) come first and the rest go to the first leaves, so a leaf has the degree of the number of hubs that reach it.  Then
+    `isolated` nodes, then as many filler nodes as make n_short short rows in all (every hub above SHORT_DEG): filler k hangs off
+    leaf k % leaves.  The node ids are then permuted by Generator(PCG64(seed)), with the last isolated node moved to the highest id,
+    the end of the short list.  Returns (edge_index, n, names): names maps 'hub0', ..., 'leaf_first', 'leaf_last' (the leaf of
+    the smallest degree), 'isolated' (when there is one) to the permuted ids."""
+    H = len(hub_degrees)
+    to_leaves = [d - sum(h in e for e in hub_edges) for h, d in enumerate(hub_degrees)]
+    L = max(to_leaves)
+    assert min(hub_degrees) > SHORT_DEG and min(to_leaves) >= 1 and H < SHORT_DEG
+    fillers = 0 if n_short is None else n_short - L - isolated
+    assert fillers >= 0 and H + 1 + -(-fillers // L) <= SHORT_DEG, 'the leaves must stay short rows'
+    n = H + L + isolated + fillers
+    pairs = [tuple(e) for e in hub_edges]
+    pairs += [(h, H + i) for h, d in enumerate(to_leaves) for i in range(d)]
+    f0 = H + L + isolated
+    pairs += [(f0 + k, H + k % L) for k in range(fillers)]
+    perm = np.random.Generator(np.random.PCG64(seed)).permutation(n)
+    if isolated:
+        last = H + L + isolated - 1
+        at = int(np.flatnonzero(perm == n - 1)[0])
+        perm[at], perm[last] = perm[last], perm[at]
+    ei, _ = _und(perm[np.asarray(pairs, dtype=np.int64)], n)
+    names = {f'hub{h}': int(perm[h]) for h in range(H)}
+    names.update(leaf_first=int(perm[H]), leaf_last=int(perm[H + L - 1]))
+    if isolated:
+        names['isolated'] = int(perm[H + L + isolated - 1])
+    return ei, n, names
+
+
+def plan_family():
+    """(name, edge_index, n) of graphs whose counts of long, medium and short rows sit at and either side of the limits of
+    csrc/dcr_analysis.h::walk_rows and row_grid: a medium workgroup takes 4 rows, a short workgroup 32 (RowGeom<>) or 64 in 8
+    turns of 8 (the resistance geometry).  tests/test_row_classes_cpu.py asserts what each graph is here for.  A graph has a long
+    row only where the plan needs one: the others stay small."""
+    return [(name, ei, n) for name, (ei, n, _) in _plan_family().items()]
+
+
+def plan_nodes(name):
+    """The named nodes of ONE graph of plan_family, as planned_graph returns them; {} for the two that are not hub graphs."""
+    return _plan_family()[name][2]
+
+
+# the graphs of plan_family, for parametrising without building them
+PLAN_NAMES = ('long3_mid9_short63', 'long1_mid0_short0', 'mid1_short7', 'mid4_short8', 'mid5_short9', 'mid8_short1', 'mid34_short0',
+              'mid0_short257')
+_FAMILY = {}
+
+
+def _plan_family():
+    if _FAMILY:
+        return _FAMILY
+    M = LONG_DEG   # a medium row at the limit
+    f = _FAMILY
+    # three long workgroups, three medium ones (the last with one row), a partial last short workgroup in both geometries;
+    # hub0 - hub1 joins two long rows, hub2 - hub3 a long and a medium one
+    f['long3_mid9_short63'] = planned_graph([M + 1, M + 2, 2100, 33, M, 33, 34, 40, 64, 65, 100, 500], [(0, 1), (2, 3)],
+                                            n_short=33 * 64 - 1, isolated=2, seed=1)
+    f['long1_mid0_short0'] = planned_graph([M + 1], n_short=33 * 64, isolated=2, seed=2)     # long rows, no medium rows
+    f['mid1_short7'] = planned_graph([33], n_short=64 + 7, isolated=2, seed=3)
+    f['mid4_short8'] = planned_graph([33, 33, 35, 64], [(0, 1)], n_short=64 + 8, seed=4)
+    f['mid5_short9'] = planned_graph([33, 34, 36, 38, 40], [(1, 4)], n_short=64 + 9, seed=5)
+    f['mid8_short1'] = planned_graph([33, 33, 34, 35, 37, 41, 48, 48], [(0, 7), (2, 3)], n_short=64 + 1, isolated=2, seed=6)
+    f['mid34_short0'] = complete(34) + ({},)     # no short rows at all
+    f['mid0_short257'] = cycle(257) + ({},)      # no long and no medium rows; one row into the next workgroup, wave and turn
+    assert tuple(f) == PLAN_NAMES
+    return f
+
+
 def closed_forms():
     """(name, (edge_index, n), lambda_1)"""
     return [
