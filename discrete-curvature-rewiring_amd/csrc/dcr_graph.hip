@@ -475,9 +475,7 @@ int dcr_graph_create(int device, int64_t n, int64_t m, const int64_t *src, const
     DCR_TRY(dev_alloc(&g->rowcap, n));
     DCR_TRY(alloc_layout(g, tot));
     DCR_TRY(dev_alloc(&g->dres, 1));
-    DCR_TRY(dev_alloc(&g->imp_stats, 1));
-    DCR_HIP(hipMemsetAsync(g->imp_stats, 0xFF, sizeof(*g->imp_stats), g->stream));  // (pos_x_in_y = -1)
-    DCR_TRY(dev_alloc(&g->draw_bsum, 256));
+    DCR_TRY(sdrf_scratch_create(g));
     DCR_TRY(dev_alloc(&g->dirty, n + 4));  // OR-ed through 32-bit words
     DCR_HIP(hipMemsetAsync(g->dirty, 0, (size_t)(n > 0 ? n : 1), g->stream));
     DCR_TRY(dev_alloc(&g->touched, n + 64));
@@ -502,10 +500,7 @@ int dcr_graph_destroy(dcr_graph *g) {
     if (!g) return DCR_OK;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    void *dev_ptrs[] = {g->rowinfo, g->rowcap, g->col, g->slot_row, g->curv, g->red_scratch, g->scan_a, g->scan_b,
-                        g->imp_table, g->imp_posx, g->imp_posy, g->imp_c1, g->imp_c2, g->imp_b, g->imp_c,
-                        g->imp_rowcount, g->imp_rowoff, g->imp_adjbits, g->imp_out, g->imp_ci, g->imp_cj,
-                        g->imp_stats, g->draw_bsum, g->dres, g->dirty, g->nc_units[0], g->nc_units[1], g->nc_units[2],
+    void *dev_ptrs[] = {g->rowinfo, g->rowcap, g->col, g->slot_row, g->curv, g->dres, g->dirty, g->nc_units[0], g->nc_units[1], g->nc_units[2],
                         g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_queues, g->giant_list,
                         g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight,
                         g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
@@ -513,12 +508,10 @@ int dcr_graph_destroy(dcr_graph *g) {
     for (void *p : dev_ptrs)
         if (p) (void)hipFree(p);
     analysis_destroy(g);
+    sdrf_scratch_destroy(g);
     for (int b = 0; b < NBINS; ++b)
         if (g->work[b]) (void)hipFree(g->work[b]);
     if (g->hres) (void)hipHostFree(g->hres);
-    if (g->imp_out_h) (void)hipHostFree(g->imp_out_h);
-    if (g->imp_ci_h) (void)hipHostFree(g->imp_ci_h);
-    if (g->imp_cj_h) (void)hipHostFree(g->imp_cj_h);
     for (int b = 0; b < NBINS - 1; ++b) {
         if (g->side[b]) (void)hipStreamDestroy(g->side[b]);
         if (g->ev_join[b]) (void)hipEventDestroy(g->ev_join[b]);

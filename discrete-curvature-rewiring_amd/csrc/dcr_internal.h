@@ -206,6 +206,7 @@ struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in
 };
 
 struct AnalysisState;  // dcr_analysis.h
+struct SdrfScratch;    // dcr_sdrf.hip
 
 }  // namespace dcr
 
@@ -293,37 +294,14 @@ struct dcr_graph {
     int32_t *work[dcr::NBINS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int64_t work_cap = 0;
 
-    // reductions / scans
-    void *red_scratch = nullptr;  // argext partials
-    // per-block (value, slot) minima and maxima left by the two-hop pass's closing kernel (k_h2_final): the first minimum
-    // after the pass and the stale first maximum of the removal step then need no sweep of their own.  Valid until the next
-    // edit (a removal moves values between slots) or pass.
+    // per-block (value, slot) minima and maxima left by the two-hop pass's closing kernel (k_h2_final) or by the one sweep for
+    // both (launch_argext_both): the first minimum after the pass and the stale first maximum of the removal step then need no
+    // sweep of their own.  Valid until the next edit (a removal moves values between slots) or pass.
     void *ext_part = nullptr;     // Ext[2][EXT_PART_BLOCKS]: minima, then maxima
     int ext_part_n = 0;
     bool ext_part_valid = false;
-    int32_t *scan_a = nullptr, *scan_b = nullptr;
-    int64_t scan_cap = 0;
 
-    // improvement pipeline scratch (grown on demand)
-    int32_t *imp_table = nullptr;  // hash keys
-    int32_t *imp_posx = nullptr, *imp_posy = nullptr;
-    int64_t imp_table_cap = 0;
-    bool imp_table_dirty = true;   // the table is not all-empty (fresh allocation, or a pipeline that did not reach its last kernel)
-    int32_t *imp_c1 = nullptr, *imp_c2 = nullptr;  // per position in row x / row y
-    double *imp_b = nullptr, *imp_c = nullptr;     // class B / C improvements per position
-    int32_t *imp_rowcount = nullptr, *imp_rowoff = nullptr;
-    uint32_t *imp_adjbits = nullptr;               // (dx+1) x words(dy+1)
-    int64_t imp_rows_cap = 0, imp_bits_cap = 0;
-    double *imp_out = nullptr;                     // compacted improvements (device)
-    int32_t *imp_ci = nullptr, *imp_cj = nullptr;
-    int64_t imp_out_cap = 0;
-    double *imp_out_h = nullptr;                   // pinned host mirrors
-    int32_t *imp_ci_h = nullptr, *imp_cj_h = nullptr;
-    int64_t imp_out_h_cap = 0, imp_cand_h_cap = 0;
-    int64_t imp_n = 0;
-    dcr::ImpStats *imp_stats = nullptr;
-    double *draw_bsum = nullptr;  // device-side draw: partial sums of exp(tau * improvement)
-
+    dcr::SdrfScratch *sdrf = nullptr;        // every buffer of the SDRF step (dcr_sdrf.hip), created with the graph
     dcr::AnalysisState *analysis = nullptr;  // every buffer of the graph-analysis calls (dcr_analysis.h), created on first use
 
     dcr::DevResult *dres = nullptr;  // device
@@ -358,6 +336,8 @@ void launch_sdrf_tail(dcr_graph *g, int32_t u, int32_t v, int edit_add, int do_r
 void launch_mark_dirty(dcr_graph *g, int32_t u, int32_t v, int edit);  // flag the edges edit number `edit` can change (>= 3: coarse)
 
 // dcr_sdrf.hip
+int sdrf_scratch_create(dcr_graph *g);    // g->sdrf and the two buffers every iteration needs
+void sdrf_scratch_destroy(dcr_graph *g);  // frees g->sdrf and what it holds
 int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_t st = nullptr);  // st: default the library stream
 // the same from the per-block extrema of the last two-hop pass (g->ext_part_valid), without sweeping the edges again
 int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st = nullptr);

@@ -45,61 +45,14 @@ __device__ inline double bfc_value(int d1, int d2, int T, int s1, int s2, int ga
 // arg-extremum over undirected edges, first in G.edges order (= smallest slot) on ties
 // ---------------------------------------------------------------------------------------------
 // (Ext, ext_better and the reductions live in dcr_internal.h: the two-hop pass's closing kernel leaves per-block extrema too)
-__global__ void __launch_bounds__(256) k_argext_edges(RowView g, int64_t cap_total, const double *curv, int want_max,
-                                                       int excl_u, int excl_v, const DevResult *res, Ext *partial) {
-    __shared__ double shv[4];
-    __shared__ int shs[4];
-    if (excl_u == -2) {  // the edge picked on the device (dcr_sdrf_tail_at)
-        excl_u = res->cand_i;
-        excl_v = res->cand_j;
-    }
-    double best_v = 0.0;
-    int best_s = -1;
-    // four slots per thread and round, their chains of dependent loads (owner row -> row extent -> neighbour ->
-    // value) in flight together; slots are visited in increasing order per thread, so "first" extremum is preserved by
-    // ext_better's (value, slot) order
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 < cap_total; s0 += 4 * stride) {
-        int u[4], v[4];
-        int2 ru[4];
-        bool ok[4];
-        double cv[4];
-        // everything addressed by the slot itself in one round (owner row, neighbour, value: all in bounds for every slot,
-        // slack included), the row extent in a second one
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t s = s0 + q * stride;
-            ok[q] = s < cap_total;
-            u[q] = ok[q] ? g.slot_row[s] : 0;
-            v[q] = ok[q] ? g.col[s] : -1;
-            cv[q] = ok[q] ? curv[s] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ru[q] = ok[q] ? g.rowinfo[u[q]] : make_int2(0, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t s = s0 + q * stride;
-            if (!ok[q] || (int)(s - ru[q].x) >= ru[q].y || v[q] <= u[q] || (u[q] == excl_u && v[q] == excl_v)) continue;
-            ext_take(best_v, best_s, cv[q], (int)s, want_max);
-        }
-    }
-    ext_block_reduce(best_v, best_s, want_max, shv, shs);
-    if (threadIdx.x == 0) partial[blockIdx.x] = ext_make(best_v, best_s);
-}
 
-// both extrema in ONE sweep, left as per-workgroup partials where the two-hop pass's closing kernel leaves its per-wave ones
-// (g->ext_part): after a node-centric or incremental pass the arg-min of the loop (sdrf_no_cuda.py:27) and the stale arg-max of
-// its removal step (:57-61) were two sweeps of 13 us each
-// (round 5: clear_words — the incremental pass's node flags, which nothing reads between the pass and this sweep: their fill
-//  launch rode in front of it before)
-__global__ void __launch_bounds__(256) k_argext_edges_both(RowView g, int64_t cap_total, const double *curv, Ext *part_min, Ext *part_max,
-                                                            unsigned *clear_words, int64_t n_clear_words, DevResult *res) {
-    __shared__ double shv[4];
-    __shared__ int shs[4];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_clear_words; i += (int64_t)gridDim.x * blockDim.x) clear_words[i] = 0u;
-    if (n_clear_words > 0 && blockIdx.x == 0 && threadIdx.x == 0) res->touched_n = 0;   // (the list of flagged nodes goes with the flags)
-    double lo_v = 0.0, hi_v = 0.0;
-    int lo_s = -1, hi_s = -1;
+// Calls body(slot, u, v, value, acc...) for every live slot of this thread that holds an undirected edge (u < v), in increasing
+// slot order: ext_take's "first slot wins" rests on that order.  Four slots per thread and round, their chains of dependent loads
+// (owner row -> row extent; neighbour; value) in flight together: everything addressed by the slot itself in one round (all in
+// bounds for every slot, slack included), the row extent in a second one.  body is a lambda that captures BY VALUE; what it
+// accumulates comes in as reference parameters (as walk_rows of dcr_analysis.h): the running extrema stay in plain registers.
+template <class Body, typename... Acc>
+__device__ __forceinline__ void walk_edge_slots(const RowView &g, int64_t cap_total, const double *curv, Body body, Acc &...acc) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 < cap_total; s0 += 4 * stride) {
         int u[4], v[4];
@@ -120,10 +73,52 @@ __global__ void __launch_bounds__(256) k_argext_edges_both(RowView g, int64_t ca
         for (int q = 0; q < 4; ++q) {
             const int64_t s = s0 + q * stride;
             if (!ok[q] || (int)(s - ru[q].x) >= ru[q].y || v[q] <= u[q]) continue;
-            ext_take(lo_v, lo_s, cv[q], (int)s, 0);
-            ext_take(hi_v, hi_s, cv[q], (int)s, 1);
+            body((int)s, u[q], v[q], cv[q], acc...);
         }
     }
+}
+
+__global__ void __launch_bounds__(256) k_argext_edges(RowView g, int64_t cap_total, const double *curv, int want_max,
+                                                       int excl_u, int excl_v, const DevResult *res, Ext *partial) {
+    __shared__ double shv[4];
+    __shared__ int shs[4];
+    if (excl_u == -2) {  // the edge picked on the device (dcr_sdrf_tail_at)
+        excl_u = res->cand_i;
+        excl_v = res->cand_j;
+    }
+    double best_v = 0.0;
+    int best_s = -1;
+    walk_edge_slots(
+        g, cap_total, curv,
+        [=](int s, int u, int v, double cv, double &bv, int &bs) {
+            if (u == excl_u && v == excl_v) return;
+            ext_take(bv, bs, cv, s, want_max);
+        },
+        best_v, best_s);
+    ext_block_reduce(best_v, best_s, want_max, shv, shs);
+    if (threadIdx.x == 0) partial[blockIdx.x] = ext_make(best_v, best_s);
+}
+
+// both extrema in ONE sweep, left as per-workgroup partials where the two-hop pass's closing kernel leaves its per-wave ones
+// (g->ext_part): after a node-centric or incremental pass the arg-min of the loop (sdrf_no_cuda.py:27) and the stale arg-max of
+// its removal step (:57-61) were two sweeps of 13 us each
+// (clear_words: the incremental pass's node flags, which nothing reads between the pass and this sweep: their fill launch rode
+//  in front of it before)
+__global__ void __launch_bounds__(256) k_argext_edges_both(RowView g, int64_t cap_total, const double *curv, Ext *part_min, Ext *part_max,
+                                                            unsigned *clear_words, int64_t n_clear_words, DevResult *res) {
+    __shared__ double shv[4];
+    __shared__ int shs[4];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_clear_words; i += (int64_t)gridDim.x * blockDim.x) clear_words[i] = 0u;
+    if (n_clear_words > 0 && blockIdx.x == 0 && threadIdx.x == 0) res->touched_n = 0;   // (the list of flagged nodes goes with the flags)
+    double lo_v = 0.0, hi_v = 0.0;
+    int lo_s = -1, hi_s = -1;
+    walk_edge_slots(
+        g, cap_total, curv,
+        [](int s, int, int, double cv, double &lv, int &ls, double &hv, int &hs) {
+            ext_take(lv, ls, cv, s, 0);
+            ext_take(hv, hs, cv, s, 1);
+        },
+        lo_v, lo_s, hi_v, hi_s);
     ext_block_reduce(lo_v, lo_s, 0, shv, shs);
     if (threadIdx.x == 0) part_min[blockIdx.x] = ext_make(lo_v, lo_s);
     __syncthreads();
@@ -131,17 +126,24 @@ __global__ void __launch_bounds__(256) k_argext_edges_both(RowView g, int64_t ca
     if (threadIdx.x == 0) part_max[blockIdx.x] = ext_make(hi_v, hi_s);
 }
 
-// the one-workgroup reduction of the partial extrema into the result block (any workgroup size)
-__device__ inline void argext_final_body(const RowView &g, const Ext *partial, int nparts, int want_max, DevResult *res) {
+// partial[0 .. nparts) reduced to (best_v, best_s) in every thread of ONE workgroup of any size up to 1,024 (16 waves)
+__device__ inline void reduce_partials(const Ext *partial, int nparts, int want_max, double &best_v, int &best_s) {
     __shared__ double shv[16];
     __shared__ int shs[16];
-    double best_v = 0.0;
-    int best_s = -1;
+    best_v = 0.0;
+    best_s = -1;
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
         const Ext e = partial[i];
         ext_take(best_v, best_s, e.val, e.slot, want_max);
     }
     ext_block_reduce(best_v, best_s, want_max, shv, shs);
+}
+
+// the one-workgroup reduction of the partial extrema into the result block
+__device__ inline void argext_final_body(const RowView &g, const Ext *partial, int nparts, int want_max, DevResult *res) {
+    double best_v;
+    int best_s;
+    reduce_partials(partial, nparts, want_max, best_v, best_s);
     if (threadIdx.x == 0) {
         res->ext_val = best_v;
         res->ext_slot = best_s;
@@ -158,10 +160,12 @@ __global__ void __launch_bounds__(1024) k_argext_final(RowView g, const Ext *par
     argext_final_body(g, partial, nparts, want_max, res);
 }
 
-// first maximum of a plain array (np.argmax of the improvements, utils/softmax.py:7)
-__global__ void __launch_bounds__(256) k_argmax_array(const double *a, int64_t n, Ext *partial, int64_t *idx_hi) {
+// first maximum of a plain array (np.argmax of the improvements, utils/softmax.py:7): of a[0 .. n), or of a[0 .. res->n_cand)
+// when res is given (the device-side draw: nothing there needs a host value)
+__global__ void __launch_bounds__(256) k_argmax_array(const double *a, int64_t n, const DevResult *res, Ext *partial) {
     __shared__ double shv[4];
     __shared__ int shs[4];
+    if (res) n = res->n_cand;
     double best_v = 0.0;
     int best_s = -1;
     // indices may exceed int32 only beyond 2^31 candidates, which the row capacity already excludes
@@ -170,74 +174,20 @@ __global__ void __launch_bounds__(256) k_argmax_array(const double *a, int64_t n
     }
     ext_block_reduce(best_v, best_s, 1, shv, shs);
     if (threadIdx.x == 0) partial[blockIdx.x] = ext_make(best_v, best_s);
-    (void)idx_hi;
 }
 
 __global__ void __launch_bounds__(256) k_argmax_final(const Ext *partial, int nparts, DevResult *res) {
-    __shared__ double shv[4];
-    __shared__ int shs[4];
-    double best_v = 0.0;
-    int best_s = -1;
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        const Ext e = partial[i];
-        ext_take(best_v, best_s, e.val, e.slot, 1);
-    }
-    ext_block_reduce(best_v, best_s, 1, shv, shs);
+    double best_v;
+    int best_s;
+    reduce_partials(partial, nparts, 1, best_v, best_s);
     if (threadIdx.x == 0) res->imp_argmax = best_s;
 }
 
-static inline int nparts_threads(int nparts) { return nparts > 1024 ? 1024 : nparts > 256 ? 512 : 256; }  // threads of the one-workgroup reduction
-constexpr int ARGEXT_BLOCKS = 1024;  // (8192 blocks: 92 us instead of 33 on S100k, the per-block reduction dominates)
-
-int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_t st) {
-    if (!st) st = g->stream;
-    g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
-    if (!g->red_scratch) {
-        Ext *p = nullptr;
-        DCR_TRY(dev_alloc(&p, ARGEXT_BLOCKS));
-        g->red_scratch = p;
-    }
-    RowView vw{g->rowinfo, g->col, g->slot_row};
-    int64_t blocks = (g->cap_total + 255) / 256;
-    if (blocks > ARGEXT_BLOCKS) blocks = ARGEXT_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_argext_edges, dim3((unsigned)blocks), dim3(256), 0, st, vw, g->cap_total, g->curv,
-                       want_max, excl_u, excl_v, g->dres, (Ext *)g->red_scratch);
-    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads((int)blocks)), 0, st, vw, (const Ext *)g->red_scratch, (int)blocks,
-                       want_max, g->dres);
-    DCR_HIP(hipGetLastError());
-    return DCR_OK;
-}
-
-// one sweep for both extrema; the partials stay valid until the next edit (as the closing kernel's of the two-hop pass)
-int launch_argext_both(dcr_graph *g, hipStream_t st, bool clear_dirty) {
-    if (!st) st = g->stream;
-    if (!g->ext_part) {
-        Ext *p = nullptr;
-        DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
-        g->ext_part = p;
-    }
-    RowView vw{g->rowinfo, g->col, g->slot_row};
-    int64_t blocks = (g->cap_total + 255) / 256;
-    if (blocks > ARGEXT_BLOCKS) blocks = ARGEXT_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_argext_edges_both, dim3((unsigned)blocks), dim3(256), 0, st, vw, g->cap_total, g->curv, (Ext *)g->ext_part,
-                       (Ext *)g->ext_part + EXT_PART_BLOCKS, reinterpret_cast<unsigned *>(g->dirty),
-                       clear_dirty ? (int64_t)(g->n + 3) / 4 : (int64_t)0, g->dres);   // (the flags hold n + 4 bytes)
-    DCR_HIP(hipGetLastError());
-    g->ext_part_n = (int)blocks;
-    g->ext_part_valid = true;
-    return DCR_OK;
-}
-
-int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st) {
-    if (!st) st = g->stream;
-    g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
-    RowView vw{g->rowinfo, g->col, g->slot_row};
-    const Ext *parts = (const Ext *)g->ext_part + (want_max ? EXT_PART_BLOCKS : 0);
-    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads(g->ext_part_n)), 0, st, vw, parts, g->ext_part_n, want_max, g->dres);
-    DCR_HIP(hipGetLastError());
-    return DCR_OK;
+// the candidate at index idx of the emitted list, as the sorted pair the tail kernels add
+__device__ inline void store_candidate(DevResult *res, const int32_t *ci, const int32_t *cj, int64_t idx) {
+    const int32_t a = ci[idx], b = cj[idx];
+    res->cand_i = a < b ? a : b;
+    res->cand_j = a < b ? b : a;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -754,28 +704,9 @@ __global__ void __launch_bounds__(256) k_imp_emit(RowView g, ImpBuf B, int x, in
     }
 }
 
-template <typename T>
-static int pinned_regrow(T **p, int64_t *cap, int64_t need) {
-    if (need <= *cap) return DCR_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    int64_t nc = need + need / 4 + 1024;
-    void *q = nullptr;
-    hipError_t e = hipHostMalloc(&q, (size_t)nc * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        set_error(std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        return DCR_ENOMEM;
-    }
-    *p = (T *)q;
-    *cap = nc;
-    return DCR_OK;
-}
-
 // the candidate drawn on the host, by index: (k, l) never leaves the device (dcr_sdrf_tail_at)
 __global__ void k_pick_candidate(const int32_t *ci, const int32_t *cj, int64_t index, DevResult *res) {
-    const int32_t a = ci[index], b = cj[index];
-    res->cand_i = a < b ? a : b;
-    res->cand_j = a < b ? b : a;
+    store_candidate(res, ci, cj, index);
     res->draw_status = 0;
 }
 
@@ -792,21 +723,7 @@ __global__ void k_pick_candidate(const int32_t *ci, const int32_t *cj, int64_t i
 constexpr int DRAW_BLOCKS = 256;
 
 // tau = +inf: softmax is one-hot at the first arg-max of the improvements (utils/softmax.py:5-8), so the index np.random.choice
-// returns is that arg-max whatever the uniform (which it still consumes: the caller has taken it).  Candidate count from the
-// result block: nothing here needs a host value.
-__global__ void __launch_bounds__(256) k_argmax_array_dev(const double *a, const DevResult *res, Ext *partial) {
-    __shared__ double shv[4];
-    __shared__ int shs[4];
-    const int64_t n = res->n_cand;
-    double best_v = 0.0;
-    int best_s = -1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        ext_take(best_v, best_s, a[i], (int)i, 1);
-    }
-    ext_block_reduce(best_v, best_s, 1, shv, shs);
-    if (threadIdx.x == 0) partial[blockIdx.x] = ext_make(best_v, best_s);
-}
-
+// returns is that arg-max whatever the uniform (which it still consumes: the caller has taken it).
 __global__ void k_draw_from_argmax(const int32_t *ci, const int32_t *cj, DevResult *res) {
     const int64_t n = res->n_cand, idx = res->imp_argmax;
     if (n <= 0) {
@@ -819,37 +736,32 @@ __global__ void k_draw_from_argmax(const int32_t *ci, const int32_t *cj, DevResu
         res->draw_idx = -1;
         return;
     }
-    const int32_t a = ci[idx], b = cj[idx];
-    res->cand_i = a < b ? a : b;
-    res->cand_j = a < b ? b : a;
+    store_candidate(res, ci, cj, idx);
     res->draw_idx = idx;
     res->draw_status = 0;
 }
 
-__device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *__restrict__ ci, const int32_t *__restrict__ cj,
-                                DevResult *res, double tau, double u, const double *bsum, double margin_scale);
-__device__ void draw_block_sum(const double *__restrict__ imp, const DevResult *res, double tau, double *__restrict__ bsum);
+// The n candidates are cut into DRAW_BLOCKS blocks of L, a block into 256 segments of l: [t0, t1) is segment t of block b
+// (empty behind the end of the block or of the list).
+__device__ inline void draw_segment(int64_t n, int b, int t, int64_t &t0, int64_t &t1) {
+    const int64_t L = (n + DRAW_BLOCKS - 1) / DRAW_BLOCKS, l = (L + 255) / 256;
+    const int64_t b0 = (int64_t)b * L, bend = b0 + L < n ? b0 + L : n;
+    t0 = b0 + (int64_t)t * l;
+    t1 = t0 + l < bend ? t0 + l : bend;
+}
 
-// Block sums of exp(tau * improvement); the LAST block to finish picks the index (round 4: k_draw_pick was a launch of its own).
-__global__ void __launch_bounds__(256) k_draw_partial(const double *__restrict__ imp, const int32_t *__restrict__ ci,
-                                                       const int32_t *__restrict__ cj, DevResult *res, double tau, double u,
-                                                       double *bsum, double margin_scale, ImpStats *st) {
-    draw_block_sum(imp, res, tau, bsum);
-    if (!last_arriver(&st->done_draw, (int)gridDim.x)) return;
-    // (the block sums are read with sc1 loads in draw_pick_block; everything else it reads was written by earlier kernels)
-    draw_pick_block(imp, ci, cj, res, tau, u, bsum, margin_scale);
+// the sum of exp(tau * improvement) over that segment, added in index order
+__device__ inline double draw_segment_sum(const double *__restrict__ imp, int64_t n, double tau, int b, int t) {
+    int64_t t0, t1;
+    draw_segment(n, b, t, t0, t1);
+    double s = 0.0;
+    for (int64_t k = t0; k < t1; ++k) s += exp(imp[k] * tau);
+    return s;
 }
 
 __device__ void draw_block_sum(const double *__restrict__ imp, const DevResult *res, double tau, double *__restrict__ bsum) {
     __shared__ double red[256];
-    const int64_t n = res->n_cand;
-    const int64_t L = (n + DRAW_BLOCKS - 1) / DRAW_BLOCKS, l = (L + 255) / 256;
-    const int64_t b0 = (int64_t)blockIdx.x * L, t0 = b0 + (int64_t)threadIdx.x * l;
-    const int64_t bend = b0 + L < n ? b0 + L : n;
-    const int64_t t1 = t0 + l < bend ? t0 + l : bend;
-    double s = 0.0;
-    for (int64_t k = t0; k < t1; ++k) s += exp(imp[k] * tau);
-    red[threadIdx.x] = s;
+    red[threadIdx.x] = draw_segment_sum(imp, res->n_cand, tau, (int)blockIdx.x, (int)threadIdx.x);
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
         if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
@@ -901,13 +813,7 @@ __device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *_
     const double base = bs == 0 ? 0.0 : pre[bs - 1];
     __syncthreads();
     // inside block bs: the threads' segment sums, then the segment that crosses T is walked element by element
-    const int64_t L = (n + DRAW_BLOCKS - 1) / DRAW_BLOCKS, l = (L + 255) / 256;
-    const int64_t b0 = (int64_t)bs * L, t0 = b0 + (int64_t)t * l;
-    const int64_t bend = b0 + L < n ? b0 + L : n;
-    const int64_t t1 = t0 + l < bend ? t0 + l : bend;
-    double s = 0.0;
-    for (int64_t k = t0; k < t1; ++k) s += exp(imp[k] * tau);
-    pre[t] = s;
+    pre[t] = draw_segment_sum(imp, n, tau, bs, t);
     __syncthreads();
     if (t == 0) {
         const double margin = (double)(n + 1024) * 0x1p-51 * total * margin_scale;
@@ -916,7 +822,8 @@ __device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *_
         double below = 0.0, above = 0.0;
         for (int k = 0; k < 256 && idx < 0; ++k) {
             if (run + pre[k] > T) {
-                const int64_t s0 = b0 + (int64_t)k * l, s1 = s0 + l < bend ? s0 + l : bend;
+                int64_t s0, s1;
+                draw_segment(n, bs, k, s0, s1);
                 for (int64_t q = s0; q < s1; ++q) {
                     const double prev = run;
                     run += exp(imp[q] * tau);
@@ -936,12 +843,161 @@ __device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *_
         res->draw_gap = idx >= 0 ? (above < below || idx == 0 ? above : below) / total : 0.0;
         res->draw_idx = ok ? idx : -1;
         res->draw_status = ok ? 0 : 1;
-        if (ok) {
-            const int32_t a = ci[idx], b = cj[idx];
-            res->cand_i = a < b ? a : b;
-            res->cand_j = a < b ? b : a;
-        }
+        if (ok) store_candidate(res, ci, cj, idx);
     }
+}
+
+// Block sums of exp(tau * improvement); the LAST block to finish picks the index.
+__global__ void __launch_bounds__(256) k_draw_partial(const double *__restrict__ imp, const int32_t *__restrict__ ci,
+                                                       const int32_t *__restrict__ cj, DevResult *res, double tau, double u,
+                                                       double *bsum, double margin_scale, ImpStats *st) {
+    draw_block_sum(imp, res, tau, bsum);
+    if (!last_arriver(&st->done_draw, (int)gridDim.x)) return;
+    // (the block sums are read with sc1 loads in draw_pick_block; everything else it reads was written by earlier kernels)
+    draw_pick_block(imp, ci, cj, res, tau, u, bsum, margin_scale);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side: the scratch of a graph, the launches other translation units call
+// ---------------------------------------------------------------------------------------------
+// Every buffer the SDRF step needs beyond the graph itself: dcr_graph::sdrf, created with the graph (sdrf_scratch_create),
+// grown on demand.  Nothing outside this file looks inside.
+struct SdrfScratch {
+    ImpBuf imp{};                 // the improvement kernels' view: table {keys, posx, posy}[table_cap]; the row arrays c1, c2, clsx,
+    int64_t table_cap = 0;        // clsy, impb, impc, rowcount, rowoff [rows_cap]; adjbits [bits_cap]; st: one ImpStats
+    int64_t rows_cap = 0, bits_cap = 0;
+    bool table_dirty = true;      // the table is not all-empty (fresh allocation, or a pipeline that did not reach its last kernel)
+    double *out = nullptr;        // compacted improvements and their candidate pairs [out_cap]
+    int32_t *ci = nullptr, *cj = nullptr;
+    int64_t out_cap = 0;
+    double *out_h = nullptr;      // pinned host mirrors
+    int32_t *ci_h = nullptr, *cj_h = nullptr;
+    int64_t out_h_cap = 0, cand_h_cap = 0;
+    int64_t n = 0;                // candidates of the last pipeline that was read back
+    Ext *red_scratch = nullptr;   // [ARGEXT_BLOCKS] per-workgroup partial extrema, allocated on first use (red_scratch_of)
+    double *draw_bsum = nullptr;  // [DRAW_BLOCKS] device-side draw: block sums of exp(tau * improvement)
+};
+
+constexpr int ARGEXT_BLOCKS = 1024;  // (8192 blocks: 92 us instead of 33 on S100k, the per-block reduction dominates)
+
+template <typename... T>
+static void dev_release(T **...p) {  // frees each and leaves it null
+    ((*p ? (void)hipFree(*p) : (void)0), ...);
+    ((*p = nullptr), ...);
+}
+
+// Buffers that share one capacity: nothing when need <= *cap; otherwise every one is freed and allocated again with `next`
+// elements.  A failure halfway leaves the whole group empty (null pointers, capacity 0), which the next call and the release
+// both accept.
+template <typename... T>
+static int regrow_group(int64_t *cap, int64_t need, int64_t next, T **...p) {
+    if (need <= *cap) return DCR_OK;
+    *cap = 0;
+    dev_release(p...);
+    int rc = DCR_OK;
+    ((rc = rc == DCR_OK ? dev_alloc(p, next) : rc), ...);
+    if (rc != DCR_OK) {
+        dev_release(p...);
+        return rc;
+    }
+    *cap = next;
+    return DCR_OK;
+}
+
+template <typename T>
+static int pinned_regrow(T **p, int64_t *cap, int64_t need) {
+    if (need <= *cap) return DCR_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    int64_t nc = need + need / 4 + 1024;
+    void *q = nullptr;
+    hipError_t e = hipHostMalloc(&q, (size_t)nc * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        set_error(std::string("hipHostMalloc: ") + hipGetErrorString(e));
+        return DCR_ENOMEM;
+    }
+    *p = (T *)q;
+    *cap = nc;
+    return DCR_OK;
+}
+
+int sdrf_scratch_create(dcr_graph *g) {
+    SdrfScratch *S = g->sdrf = new SdrfScratch();
+    DCR_TRY(dev_alloc(&S->imp.st, 1));
+    DCR_HIP(hipMemsetAsync(S->imp.st, 0xFF, sizeof(ImpStats), g->stream));  // (pos_x_in_y = -1)
+    DCR_TRY(dev_alloc(&S->draw_bsum, DRAW_BLOCKS));
+    return DCR_OK;
+}
+
+void sdrf_scratch_destroy(dcr_graph *g) {
+    SdrfScratch *S = g->sdrf;
+    if (!S) return;
+    ImpBuf &B = S->imp;
+    dev_release(&B.keys, &B.posx, &B.posy, &B.c1, &B.c2, &B.clsx, &B.clsy, &B.impb, &B.impc, &B.rowcount, &B.rowoff, &B.adjbits, &B.st,
+                &S->out, &S->ci, &S->cj, &S->red_scratch, &S->draw_bsum);
+    if (S->out_h) (void)hipHostFree(S->out_h);
+    if (S->ci_h) (void)hipHostFree(S->ci_h);
+    if (S->cj_h) (void)hipHostFree(S->cj_h);
+    delete S;
+    g->sdrf = nullptr;
+}
+
+static int red_scratch_of(dcr_graph *g, Ext **out) {  // allocated on first use
+    SdrfScratch &S = *g->sdrf;
+    if (!S.red_scratch) DCR_TRY(dev_alloc(&S.red_scratch, ARGEXT_BLOCKS));
+    *out = S.red_scratch;
+    return DCR_OK;
+}
+
+static inline int nparts_threads(int nparts) { return nparts > 1024 ? 1024 : nparts > 256 ? 512 : 256; }  // threads of the one-workgroup reduction
+
+static inline unsigned argext_blocks(int64_t cap_total) {  // workgroups of an edge sweep
+    const int64_t blocks = (cap_total + 255) / 256;
+    return (unsigned)(blocks > ARGEXT_BLOCKS ? ARGEXT_BLOCKS : blocks < 1 ? 1 : blocks);
+}
+
+int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_t st) {
+    if (!st) st = g->stream;
+    g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
+    Ext *partial = nullptr;
+    DCR_TRY(red_scratch_of(g, &partial));
+    RowView vw{g->rowinfo, g->col, g->slot_row};
+    const unsigned blocks = argext_blocks(g->cap_total);
+    hipLaunchKernelGGL(k_argext_edges, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv, want_max, excl_u, excl_v, g->dres,
+                       partial);
+    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads((int)blocks)), 0, st, vw, (const Ext *)partial, (int)blocks,
+                       want_max, g->dres);
+    DCR_HIP(hipGetLastError());
+    return DCR_OK;
+}
+
+// one sweep for both extrema; the partials stay valid until the next edit (as the closing kernel's of the two-hop pass)
+int launch_argext_both(dcr_graph *g, hipStream_t st, bool clear_dirty) {
+    if (!st) st = g->stream;
+    if (!g->ext_part) {
+        Ext *p = nullptr;
+        DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
+        g->ext_part = p;
+    }
+    RowView vw{g->rowinfo, g->col, g->slot_row};
+    const unsigned blocks = argext_blocks(g->cap_total);
+    hipLaunchKernelGGL(k_argext_edges_both, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv, (Ext *)g->ext_part,
+                       (Ext *)g->ext_part + EXT_PART_BLOCKS, reinterpret_cast<unsigned *>(g->dirty),
+                       clear_dirty ? (int64_t)(g->n + 3) / 4 : (int64_t)0, g->dres);   // (the flags hold n + 4 bytes)
+    DCR_HIP(hipGetLastError());
+    g->ext_part_n = (int)blocks;
+    g->ext_part_valid = true;
+    return DCR_OK;
+}
+
+int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st) {
+    if (!st) st = g->stream;
+    g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
+    RowView vw{g->rowinfo, g->col, g->slot_row};
+    const Ext *parts = (const Ext *)g->ext_part + (want_max ? EXT_PART_BLOCKS : 0);
+    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads(g->ext_part_n)), 0, st, vw, parts, g->ext_part_n, want_max, g->dres);
+    DCR_HIP(hipGetLastError());
+    return DCR_OK;
 }
 
 }  // namespace dcr
@@ -949,7 +1005,7 @@ __device__ void draw_pick_block(const double *__restrict__ imp, const int32_t *_
 using namespace dcr;
 
 // the improvement pipeline of one edge (x, y), enqueued on the library stream: candidates and their improvements end up in
-// g->imp_out / imp_ci / imp_cj, their number in the result block (n_cand); *upper_out = the bound (dx + 1)(dy + 1) on it
+// the scratch's out / ci / cj, their number in the result block (n_cand); *upper_out = the bound (dx + 1)(dy + 1) on it
 // amax_from_parts: the stale arg-max of the removal step reduced from the pass's partial maxima by one more workgroup of the
 // first launch (the caller has checked g->ext_part_valid and sets g->amax_valid)
 static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_t *upper_out, bool amax_from_parts = false) {
@@ -975,70 +1031,27 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
     const int64_t upper = (int64_t)(dx + 1) * (dy + 1);
     if (upper > INT32_MAX) DCR_FAIL(DCR_ECAPACITY, "more than 2^31 candidate pairs");
 
-    // scratch
-    if (ts > g->imp_table_cap) {
-        for (int32_t **p : {&g->imp_table, &g->imp_posx, &g->imp_posy}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-            DCR_TRY(dev_alloc(p, ts));
-        }
-        g->imp_table_cap = ts;
-        g->imp_table_dirty = true;
-    }
+    // scratch: the table exactly as large as asked for; the row arrays and the output doubled (a re-allocation is a device
+    // synchronisation + two driver calls, ~0.3 ms — a few of them inside a 20-iteration measurement are 1-2 % of it)
+    SdrfScratch &S = *g->sdrf;
+    ImpBuf &B = S.imp;
+    if (ts > S.table_cap) S.table_dirty = true;
+    DCR_TRY(regrow_group(&S.table_cap, ts, ts, &B.keys, &B.posx, &B.posy));
     const int64_t rows_need = (int64_t)(dx > dy ? dx : dy) + 2;
-    if (rows_need > g->imp_rows_cap) {
-        const int64_t nc = 2 * rows_need + 64;
-        for (int32_t **p : {&g->imp_c1, &g->imp_c2, &g->imp_rowcount, &g->imp_rowoff, &g->scan_a, &g->scan_b}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-            DCR_TRY(dev_alloc(p, nc));
-        }
-        for (double **p : {&g->imp_b, &g->imp_c}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-            DCR_TRY(dev_alloc(p, nc));
-        }
-        g->imp_rows_cap = nc;
-    }
-    if ((int64_t)rows * words > g->imp_bits_cap) DCR_TRY(dev_regrow(&g->imp_adjbits, &g->imp_bits_cap, 2 * (int64_t)rows * words));
-    if (upper > g->imp_out_cap) {
-        if (g->imp_out) (void)hipFree(g->imp_out);
-        if (g->imp_ci) (void)hipFree(g->imp_ci);
-        if (g->imp_cj) (void)hipFree(g->imp_cj);
-        g->imp_out = nullptr;
-        g->imp_ci = g->imp_cj = nullptr;
-        const int64_t nc = 2 * upper + 1024;   // (doubling: a re-allocation is a device synchronisation + two driver calls, ~0.3 ms —
-                                               //  a few of them inside a 20-iteration measurement are 1-2 % of it)
-        DCR_TRY(dev_alloc(&g->imp_out, nc));
-        DCR_TRY(dev_alloc(&g->imp_ci, nc));
-        DCR_TRY(dev_alloc(&g->imp_cj, nc));
-        g->imp_out_cap = nc;
-    }
-
-    ImpBuf B;
-    B.keys = g->imp_table;
-    B.posx = g->imp_posx;
-    B.posy = g->imp_posy;
-    B.c1 = g->imp_c1;
-    B.c2 = g->imp_c2;
-    B.clsx = g->scan_a;
-    B.clsy = g->scan_b;
-    B.impb = g->imp_b;
-    B.impc = g->imp_c;
-    B.rowcount = g->imp_rowcount;
-    B.rowoff = g->imp_rowoff;
-    B.adjbits = g->imp_adjbits;
-    B.st = g->imp_stats;
+    DCR_TRY(regrow_group(&S.rows_cap, rows_need, 2 * rows_need + 64, &B.c1, &B.c2, &B.rowcount, &B.rowoff, &B.clsx, &B.clsy, &B.impb,
+                         &B.impc));
+    if ((int64_t)rows * words > S.bits_cap) DCR_TRY(dev_regrow(&B.adjbits, &S.bits_cap, 2 * (int64_t)rows * words));
+    DCR_TRY(regrow_group(&S.out_cap, upper, 2 * upper + 1024, &S.out, &S.ci, &S.cj));
     RowView vw{g->rowinfo, g->col, g->slot_row};
 
-    // Five launches (round 4; eleven before): insert both rows | per candidate row: classes, 4-cycle counters, admissibility
-    // bitmap, and the stage's closing statistics + scan by its last workgroup | classes B and C | emit (and leave the table
-    // empty) | the draw (its caller).  The table is only cleared here when the previous pipeline did not leave it empty.
-    if (g->imp_table_dirty) {
-        const unsigned blocks = (unsigned)((g->imp_table_cap + 255) / 256 > 1024 ? 1024 : (g->imp_table_cap + 255) / 256);
-        hipLaunchKernelGGL(k_imp_clear, dim3(blocks ? blocks : 1), dim3(256), 0, g->stream, B, g->imp_table_cap);
+    // Five launches: insert both rows | per candidate row: classes, 4-cycle counters, admissibility bitmap, and the stage's
+    // closing statistics + scan by its last workgroup | classes B and C | emit (and leave the table empty) | the draw (its
+    // caller).  The table is only cleared here when the previous pipeline did not leave it empty.
+    if (S.table_dirty) {
+        const unsigned blocks = (unsigned)((S.table_cap + 255) / 256 > 1024 ? 1024 : (S.table_cap + 255) / 256);
+        hipLaunchKernelGGL(k_imp_clear, dim3(blocks ? blocks : 1), dim3(256), 0, g->stream, B, S.table_cap);
     }
-    g->imp_table_dirty = true;  // (until k_imp_emit below has been enqueued)
+    S.table_dirty = true;  // (until k_imp_emit below has been enqueued)
     const int gi = (dx + dy + 255) / 256 > 0 ? (dx + dy + 255) / 256 : 1;
     const Ext *amax_parts = amax_from_parts ? (const Ext *)g->ext_part + EXT_PART_BLOCKS : nullptr;
     hipLaunchKernelGGL(k_imp_insert, dim3(gi + (amax_parts ? 1 : 0)), dim3(256), 0, g->stream, vw, B, x, y, mask, amax_parts,
@@ -1047,12 +1060,32 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
                        g->dres);
     if (dx + dy > 0)
         hipLaunchKernelGGL(k_imp_bc, dim3(dx + dy), dim3(256), 0, g->stream, vw, B, x, y, mask, curv_type);
-    hipLaunchKernelGGL(k_imp_emit, dim3(rows), dim3(256), 0, g->stream, vw, B, x, y, words, curv_type, g->imp_out,
-                       g->imp_ci, g->imp_cj, ts);
-    g->imp_table_dirty = false;
+    hipLaunchKernelGGL(k_imp_emit, dim3(rows), dim3(256), 0, g->stream, vw, B, x, y, words, curv_type, S.out, S.ci, S.cj, ts);
+    S.table_dirty = false;
     DCR_HIP(hipGetLastError());
     *upper_out = upper;
     return DCR_OK;
+}
+
+static int check_edge_args(const dcr_graph *g, int32_t x, int32_t y, int curv_type) {
+    if (x < 0 || y < 0 || x >= g->n || y >= g->n || x == y) DCR_FAIL(DCR_EINVAL, "bad node ids");
+    if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
+    return DCR_OK;
+}
+
+// the candidate drawn on the host goes into the result block by its index: the tail then adds the pair (-2, -2)
+static int pick_candidate(dcr_graph *g, int64_t cand_index) {
+    if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
+    if (cand_index < 0 || cand_index >= g->sdrf->n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
+    DCR_HIP(hipSetDevice(g->device));
+    hipLaunchKernelGGL(k_pick_candidate, dim3(1), dim3(1), 0, g->stream, g->sdrf->ci, g->sdrf->cj, cand_index, g->dres);
+    return DCR_OK;
+}
+
+static void fill_added(const dcr_graph *g, int32_t out_added[2]) {  // after a synchronisation: the pair the tail added
+    if (!out_added) return;
+    out_added[0] = g->hres->cand_i;
+    out_added[1] = g->hres->cand_j;
 }
 
 extern "C" {
@@ -1079,31 +1112,31 @@ int dcr_argext(dcr_graph *g, int want_max, int32_t excl_u, int32_t excl_v, int32
 int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want_candidates, int64_t *n_out,
                      const double **out_improvement, const int32_t **out_ci, const int32_t **out_cj) {
     if (!g || !n_out) DCR_FAIL(DCR_EINVAL, "null argument");
-    if (x < 0 || y < 0 || x >= g->n || y >= g->n || x == y) DCR_FAIL(DCR_EINVAL, "bad node ids");
-    if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
+    DCR_TRY(check_edge_args(g, x, y, curv_type));
     DCR_HIP(hipSetDevice(g->device));
+    SdrfScratch &S = *g->sdrf;
     int64_t upper = 0;
     DCR_TRY(imp_enqueue(g, x, y, curv_type, &upper));
     // one host sync: the result block and the values go out together; the candidate count is not known yet, so the
     // copy is sized by its upper bound (dx+1)(dy+1), which the real count nearly reaches on a sparse graph
     if (upper > 0 && out_improvement) {
-        DCR_TRY(pinned_regrow(&g->imp_out_h, &g->imp_out_h_cap, upper));
-        DCR_HIP(hipMemcpyAsync(g->imp_out_h, g->imp_out, sizeof(double) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        DCR_TRY(pinned_regrow(&S.out_h, &S.out_h_cap, upper));
+        DCR_HIP(hipMemcpyAsync(S.out_h, S.out, sizeof(double) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
     }
     if (upper > 0 && want_candidates) {
-        if (upper > g->imp_cand_h_cap) {
-            int64_t c1 = g->imp_cand_h_cap, c2 = g->imp_cand_h_cap;
-            DCR_TRY(pinned_regrow(&g->imp_ci_h, &c1, upper));
-            DCR_TRY(pinned_regrow(&g->imp_cj_h, &c2, upper));
-            g->imp_cand_h_cap = c1 < c2 ? c1 : c2;
+        if (upper > S.cand_h_cap) {
+            int64_t c1 = S.cand_h_cap, c2 = S.cand_h_cap;
+            DCR_TRY(pinned_regrow(&S.ci_h, &c1, upper));
+            DCR_TRY(pinned_regrow(&S.cj_h, &c2, upper));
+            S.cand_h_cap = c1 < c2 ? c1 : c2;
         }
-        DCR_HIP(hipMemcpyAsync(g->imp_ci_h, g->imp_ci, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
-        DCR_HIP(hipMemcpyAsync(g->imp_cj_h, g->imp_cj, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(S.ci_h, S.ci, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(S.cj_h, S.cj, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
     }
     DCR_TRY(sync_result(g));
     const int64_t n = g->hres->n_cand;
     if (n < 0 || n > upper) DCR_FAIL(DCR_ESTATE, "candidate count outside its bound");
-    g->imp_n = n;
+    S.n = n;
     *n_out = n;
     // The removal step looks for the highest STALE curvature (sdrf_no_cuda.py:57-61), which does not depend on the edge
     // about to be drawn (that one is excluded there only because it has no stale value): compute it now, while the host
@@ -1113,27 +1146,23 @@ int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want
         else DCR_TRY(launch_argext(g, 1, -1, -1));
         g->amax_valid = true;
     }
-    if (out_improvement) *out_improvement = n > 0 ? g->imp_out_h : nullptr;
-    if (out_ci) *out_ci = (n > 0 && want_candidates) ? g->imp_ci_h : nullptr;
-    if (out_cj) *out_cj = (n > 0 && want_candidates) ? g->imp_cj_h : nullptr;
+    if (out_improvement) *out_improvement = n > 0 ? S.out_h : nullptr;
+    if (out_ci) *out_ci = (n > 0 && want_candidates) ? S.ci_h : nullptr;
+    if (out_cj) *out_cj = (n > 0 && want_candidates) ? S.cj_h : nullptr;
     return DCR_OK;
 }
 
 int dcr_improvements_argmax(dcr_graph *g, int64_t *out_index) {
     if (!g || !out_index) DCR_FAIL(DCR_EINVAL, "null argument");
-    if (g->imp_n <= 0) DCR_FAIL(DCR_ESTATE, "no candidates from the last dcr_improvements call");
+    const int64_t n = g->sdrf->n;
+    if (n <= 0) DCR_FAIL(DCR_ESTATE, "no candidates from the last dcr_improvements call");
     DCR_HIP(hipSetDevice(g->device));
-    if (!g->red_scratch) {
-        Ext *p = nullptr;
-        DCR_TRY(dev_alloc(&p, ARGEXT_BLOCKS));
-        g->red_scratch = p;
-    }
-    int64_t blocks = (g->imp_n + 255) / 256;
-    if (blocks > ARGEXT_BLOCKS) blocks = ARGEXT_BLOCKS;
-    hipLaunchKernelGGL(k_argmax_array, dim3((unsigned)blocks), dim3(256), 0, g->stream, g->imp_out, g->imp_n,
-                       (Ext *)g->red_scratch, (int64_t *)nullptr);
-    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)g->red_scratch, (int)blocks,
-                       g->dres);
+    Ext *partial = nullptr;
+    DCR_TRY(red_scratch_of(g, &partial));
+    const int64_t blocks = (n + 255) / 256 > ARGEXT_BLOCKS ? ARGEXT_BLOCKS : (n + 255) / 256;
+    hipLaunchKernelGGL(k_argmax_array, dim3((unsigned)blocks), dim3(256), 0, g->stream, g->sdrf->out, n, (const DevResult *)nullptr,
+                       partial);
+    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, (int)blocks, g->dres);
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
     *out_index = g->hres->imp_argmax;
@@ -1142,17 +1171,20 @@ int dcr_improvements_argmax(dcr_graph *g, int64_t *out_index) {
 
 int dcr_candidate_at(dcr_graph *g, int64_t index, int32_t *out_i, int32_t *out_j) {
     if (!g || !out_i || !out_j) DCR_FAIL(DCR_EINVAL, "null argument");
-    if (index < 0 || index >= g->imp_n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
+    if (index < 0 || index >= g->sdrf->n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
     DCR_HIP(hipSetDevice(g->device));
-    DCR_HIP(hipMemcpyAsync(out_i, g->imp_ci + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipMemcpyAsync(out_j, g->imp_cj + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_i, g->sdrf->ci + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_j, g->sdrf->cj + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
 
-// The tail of an iteration in two halves, so that the NEXT iteration's curvature pass can be enqueued behind it without a
-// host round trip in between (dcr_sdrf_tail_at_pass_argmin): enqueue (add, dirty flags, stale arg-max, conditional remove)
-// and finish (read the result block after some later synchronisation).
+}  // extern "C"
+
+// The tail of an iteration: prepare (argument checks, host bookkeeping), enqueue (add, dirty flags, stale arg-max, conditional
+// remove), then — after some synchronisation has brought the result block over — finish (edge count, degree bound, outputs).
+// run_tail holds the three together; with a TailPass the synchronisation is the NEXT iteration's curvature pass and first
+// minimum, enqueued right behind the edit without a host round trip in between.
 struct TailCall {
     int32_t add_k, add_l;
     int do_remove;
@@ -1161,10 +1193,16 @@ struct TailCall {
     int edit_add, edit_rem;
 };
 
+struct TailPass {  // arguments of dcr_curvature_pass_argmin
+    int curv_type, incremental;
+    int32_t *out_u, *out_v;
+    double *out_val;
+};
+
 static int tail_prepare(dcr_graph *g, int32_t add_k, int32_t add_l, int do_remove, double removal_bound, TailCall *tc) {
     if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
     if (do_remove && !g->curv_valid) DCR_FAIL(DCR_ESTATE, "removal needs a curvature pass first");
-    tc->adding = add_k >= 0 || add_k == -2;  // -2: the pair k_pick_candidate left in the result block
+    tc->adding = add_k >= 0 || add_k == -2;  // -2: the pair k_pick_candidate or the device-side draw left in the result block
     if (add_k >= 0) {
         if (add_l < 0 || add_k >= g->n || add_l >= g->n || add_k == add_l) DCR_FAIL(DCR_EINVAL, "bad edge to add");
         if (add_k > add_l) {
@@ -1205,8 +1243,9 @@ static int tail_enqueue(dcr_graph *g, const TailCall &tc, bool first_attempt) {
     return DCR_OK;
 }
 
-// after a synchronisation that brought the result block over: host-side bookkeeping and outputs
-static void tail_finish(dcr_graph *g, const TailCall &tc, int32_t out_removed[2], double *out_max_val, bool max_val_known) {
+// after a synchronisation that brought the result block over: host-side bookkeeping and outputs (out_max_val: the stale
+// maximum, for the callers whose result block still holds it — a pass behind the tail overwrites the ext fields)
+static void tail_finish(dcr_graph *g, const TailCall &tc, int32_t out_removed[2], double *out_max_val) {
     if (tc.adding && g->hres->add_status == 0) {
         g->n_edges++;
         g->max_deg_bound++;
@@ -1216,7 +1255,7 @@ static void tail_finish(dcr_graph *g, const TailCall &tc, int32_t out_removed[2]
         ru = g->hres->removed_u;
         rv = g->hres->removed_v;
         if (ru >= 0) g->n_edges--;
-        if (out_max_val) *out_max_val = (max_val_known && g->hres->ext_slot >= 0) ? g->hres->ext_val : 0.0;
+        if (out_max_val) *out_max_val = g->hres->ext_slot >= 0 ? g->hres->ext_val : 0.0;
     }
     if (out_removed) {
         out_removed[0] = ru;
@@ -1224,78 +1263,69 @@ static void tail_finish(dcr_graph *g, const TailCall &tc, int32_t out_removed[2]
     }
 }
 
-static int sdrf_tail_impl(dcr_graph *g, int32_t add_k, int32_t add_l, int do_remove, double removal_bound,
-                          int32_t out_removed[2], double *out_max_val) {
-    TailCall tc;
-    DCR_TRY(tail_prepare(g, add_k, add_l, do_remove, removal_bound, &tc));
+// Enqueue, synchronise (pass: through the next curvature pass and its first minimum), finish.  A row overflow of the add —
+// rare: rows carry slack — is seen only after the synchronisation; nothing was edited then (the removal is skipped when the add
+// overflows): the rows are laid out again and the tail replayed once, the pass with it.  add_status == 3 (the device-side draw
+// left nothing to add: nothing was edited) skips the bookkeeping; it cannot occur behind k_pick_candidate or an explicit pair,
+// which never leave a draw status other than 0, so the one check serves every caller.
+static int run_tail(dcr_graph *g, const TailCall &tc, const TailPass *pass, int32_t out_removed[2], double *out_max_val) {
     for (int attempt = 0; attempt < 2; ++attempt) {
         DCR_TRY(tail_enqueue(g, tc, attempt == 0));
-        DCR_TRY(sync_result(g));
-        if (g->hres->add_status != 1) break;
+        int rc = DCR_OK;
+        if (pass) {
+            // the pass sizes its launches by this upper bound (which class kernels run at all): count the pending add in, on the
+            // replay too — relayout() has just reset the bound to the exact maximum BEFORE the add
+            g->max_deg_bound++;
+            rc = dcr_curvature_pass_argmin(g, pass->curv_type, pass->incremental, pass->out_u, pass->out_v, pass->out_val);  // synchronises
+            g->max_deg_bound--;  // (tail_finish counts it once the add is known to have happened)
+        } else {
+            DCR_TRY(sync_result(g));
+        }
+        if (g->hres->add_status != 1) {
+            if (rc == DCR_OK) break;
+            // the edit did happen on the device (the result block is from a completed synchronisation unless the failure was
+            // the HIP call itself): keep the host's edge count and degree bound in step before reporting
+            if (rc != DCR_EHIP && g->hres->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
+            return rc;
+        }
         if (attempt == 1) DCR_FAIL(DCR_ECAPACITY, "row still full after relayout");
         DCR_TRY(relayout(g));
     }
-    tail_finish(g, tc, out_removed, out_max_val, true);
+    if (g->hres->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
     return DCR_OK;
+}
+
+extern "C" {
+
+int dcr_sdrf_tail(dcr_graph *g, int32_t add_k, int32_t add_l, int do_remove, double removal_bound,
+                  int32_t out_removed[2], double *out_max_val) {
+    TailCall tc;
+    DCR_TRY(tail_prepare(g, add_k, add_l, do_remove, removal_bound, &tc));
+    return run_tail(g, tc, nullptr, out_removed, out_max_val);
 }
 
 int dcr_sdrf_tail_at(dcr_graph *g, int64_t cand_index, int do_remove, double removal_bound, int32_t out_added[2],
                      int32_t out_removed[2], double *out_max_val) {
-    if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
-    if (cand_index < 0 || cand_index >= g->imp_n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
-    DCR_HIP(hipSetDevice(g->device));
-    hipLaunchKernelGGL(k_pick_candidate, dim3(1), dim3(1), 0, g->stream, g->imp_ci, g->imp_cj, cand_index, g->dres);
-    DCR_TRY(sdrf_tail_impl(g, -2, -2, do_remove, removal_bound, out_removed, out_max_val));
-    if (out_added) {
-        out_added[0] = g->hres->cand_i;
-        out_added[1] = g->hres->cand_j;
-    }
+    DCR_TRY(pick_candidate(g, cand_index));
+    TailCall tc;
+    DCR_TRY(tail_prepare(g, -2, -2, do_remove, removal_bound, &tc));
+    DCR_TRY(run_tail(g, tc, nullptr, out_removed, out_max_val));
+    fill_added(g, out_added);
     return DCR_OK;
-}
-
-int dcr_sdrf_tail(dcr_graph *g, int32_t add_k, int32_t add_l, int do_remove, double removal_bound,
-                  int32_t out_removed[2], double *out_max_val) {
-    return sdrf_tail_impl(g, add_k, add_l, do_remove, removal_bound, out_removed, out_max_val);
 }
 
 // Tail of iteration i and the head of iteration i + 1 in one call with ONE host synchronisation: add the drawn
 // candidate, conditional removal (sdrf_no_cuda.py:51,56-66), then the curvature pass of the next iteration and its first
-// minimum (:24,:27).  The pass is enqueued right behind the edit; the result block carries the tail's outcome and the
-// arg-min over together.  (A row overflow of the add — rare: rows carry slack — is seen only then: the rows are laid out
-// again, the tail replayed and the pass redone.)
+// minimum (:24,:27).  The result block carries the tail's outcome and the arg-min over together.
 int dcr_sdrf_tail_at_pass_argmin(dcr_graph *g, int64_t cand_index, int do_remove, double removal_bound, int curv_type,
                                  int incremental, int32_t out_added[2], int32_t out_removed[2], int32_t *out_u, int32_t *out_v,
                                  double *out_val) {
-    if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
-    if (cand_index < 0 || cand_index >= g->imp_n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
-    DCR_HIP(hipSetDevice(g->device));
-    hipLaunchKernelGGL(k_pick_candidate, dim3(1), dim3(1), 0, g->stream, g->imp_ci, g->imp_cj, cand_index, g->dres);
+    DCR_TRY(pick_candidate(g, cand_index));
     TailCall tc;
     DCR_TRY(tail_prepare(g, -2, -2, do_remove, removal_bound, &tc));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        DCR_TRY(tail_enqueue(g, tc, attempt == 0));
-        // the pass below sizes its launches by this upper bound (which class kernels run at all): count the pending add in,
-        // on the replay too — relayout() has just reset the bound to the exact maximum BEFORE the add
-        g->max_deg_bound++;
-        const int rc = dcr_curvature_pass_argmin(g, curv_type, incremental, out_u, out_v, out_val);  // synchronises
-        g->max_deg_bound--;  // (tail_finish counts it once the add is known to have happened)
-        if (g->hres->add_status != 1) {
-            if (rc != DCR_OK) {
-                // the edit did happen on the device (the result block is from a completed synchronisation unless the
-                // failure was the HIP call itself): keep the host's edge count and degree bound in step before reporting
-                if (rc != DCR_EHIP) tail_finish(g, tc, out_removed, nullptr, false);
-                return rc;
-            }
-            break;
-        }
-        if (attempt == 1) DCR_FAIL(DCR_ECAPACITY, "row still full after relayout");
-        DCR_TRY(relayout(g));  // nothing was edited (the removal is skipped when the add overflows): lay out, replay
-    }
-    tail_finish(g, tc, out_removed, nullptr, false);
-    if (out_added) {
-        out_added[0] = g->hres->cand_i;
-        out_added[1] = g->hres->cand_j;
-    }
+    const TailPass pass{curv_type, incremental, out_u, out_v, out_val};
+    DCR_TRY(run_tail(g, tc, &pass, out_removed, nullptr));
+    fill_added(g, out_added);
     return DCR_OK;
 }
 
@@ -1309,13 +1339,13 @@ int dcr_sdrf_iteration_device_draw(dcr_graph *g, int32_t x, int32_t y, int curv_
                                    double removal_bound, int incremental, int *out_status, int64_t *out_n_cand,
                                    int32_t out_added[2], int32_t out_removed[2], int32_t *out_u, int32_t *out_v, double *out_val) {
     if (!g || !out_status || !out_n_cand) DCR_FAIL(DCR_EINVAL, "null argument");
-    if (x < 0 || y < 0 || x >= g->n || y >= g->n || x == y) DCR_FAIL(DCR_EINVAL, "bad node ids");
-    if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
+    DCR_TRY(check_edge_args(g, x, y, curv_type));
     const bool tau_inf = tau > 1.7e308;  // +inf: the first arg-max
     if (!(tau == tau) || tau < -1.7e308 || !(uniform >= 0.0 && uniform < 1.0))
         DCR_FAIL(DCR_EINVAL, "device draw: tau finite or +inf and a uniform in [0, 1) expected");
     if (do_remove && !g->curv_valid) DCR_FAIL(DCR_ESTATE, "removal needs a curvature pass first");
     DCR_HIP(hipSetDevice(g->device));
+    SdrfScratch &S = *g->sdrf;
     // the stale arg-max of the removal step does not depend on the edge about to be drawn (see dcr_improvements), nor on the
     // improvement pipeline: beside it, on a stream of its own (it writes other fields of the result block)
     const bool amax = g->curv_valid && do_remove;
@@ -1338,68 +1368,45 @@ int dcr_sdrf_iteration_device_draw(dcr_graph *g, int32_t x, int32_t y, int curv_
     // (DCR_DRAW_MARGIN_SCALE widens the margin: the tests use it to send draws down the undecided path)
     const double margin_scale = getenv("DCR_DRAW_MARGIN_SCALE") ? atof(getenv("DCR_DRAW_MARGIN_SCALE")) : 1.0;
     if (tau_inf && margin_scale <= 1.0) {
-        if (!g->red_scratch) {
-            Ext *p = nullptr;
-            DCR_TRY(dev_alloc(&p, ARGEXT_BLOCKS));
-            g->red_scratch = p;
-        }
+        Ext *partial = nullptr;
+        DCR_TRY(red_scratch_of(g, &partial));
         // (red_scratch is free again: the stale arg-max beside the pipeline has been joined above)
-        hipLaunchKernelGGL(k_argmax_array_dev, dim3(256), dim3(256), 0, g->stream, g->imp_out, g->dres, (Ext *)g->red_scratch);
-        hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)g->red_scratch, 256, g->dres);
-        hipLaunchKernelGGL(k_draw_from_argmax, dim3(1), dim3(1), 0, g->stream, g->imp_ci, g->imp_cj, g->dres);
+        hipLaunchKernelGGL(k_argmax_array, dim3(256), dim3(256), 0, g->stream, S.out, (int64_t)0, (const DevResult *)g->dres, partial);
+        hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, 256, g->dres);
+        hipLaunchKernelGGL(k_draw_from_argmax, dim3(1), dim3(1), 0, g->stream, S.ci, S.cj, g->dres);
     } else {
-        hipLaunchKernelGGL(k_draw_partial, dim3(DRAW_BLOCKS), dim3(256), 0, g->stream, g->imp_out, g->imp_ci, g->imp_cj, g->dres, tau,
-                           uniform, g->draw_bsum, margin_scale >= 1.0 ? margin_scale : 1.0, g->imp_stats);
+        hipLaunchKernelGGL(k_draw_partial, dim3(DRAW_BLOCKS), dim3(256), 0, g->stream, S.out, S.ci, S.cj, g->dres, tau, uniform,
+                           S.draw_bsum, margin_scale >= 1.0 ? margin_scale : 1.0, S.imp.st);
     }
+    const auto nothing_edited = [&]() {
+        if (out_removed) out_removed[0] = out_removed[1] = -1;
+        if (out_added) out_added[0] = out_added[1] = -1;
+        return DCR_OK;
+    };
     // A host round trip here, without any transfer or host arithmetic: enqueuing the tail and the pass behind a stream that
     // is still working through the small kernels above cost 0.2 ms per iteration more than enqueuing them on an idle one
     // (measured, interleaved in one run: 1.89 against 1.59 ms), and the draw's verdict comes over with it, so an undecided
     // draw costs no wasted pass.
-    // (Round 5: not in front of an INCREMENTAL pass — three launches on this one stream, 0.08 ms: there the round trip costs a
-    //  tenth of the iteration and saves nothing; an undecided draw makes the tail a no-op (it reads the verdict in the result
-    //  block), the pass then finds nothing flagged, and the verdict comes over with the pass's result.)
+    // (Not in front of an INCREMENTAL pass — three launches on this one stream, 0.08 ms: there the round trip costs a tenth of
+    //  the iteration and saves nothing; an undecided draw makes the tail a no-op (it reads the verdict in the result block), the
+    //  pass then finds nothing flagged, and the verdict comes over with the pass's result.)
     if (!incremental) {
         DCR_TRY(sync_result(g));
-        g->imp_n = g->hres->n_cand;
-        *out_n_cand = g->hres->n_cand;
+        S.n = *out_n_cand = g->hres->n_cand;
         *out_status = g->hres->draw_status;
-        if (g->hres->draw_status != 0) {
-            if (out_removed) out_removed[0] = out_removed[1] = -1;
-            if (out_added) out_added[0] = out_added[1] = -1;
-            return DCR_OK;
-        }
+        if (g->hres->draw_status != 0) return nothing_edited();
     }
     TailCall tc;
     DCR_TRY(tail_prepare(g, -2, -2, do_remove, removal_bound, &tc));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        DCR_TRY(tail_enqueue(g, tc, attempt == 0));
-        g->max_deg_bound++;  // (see dcr_sdrf_tail_at_pass_argmin)
-        const int rc = dcr_curvature_pass_argmin(g, curv_type, incremental, out_u, out_v, out_val);  // synchronises
-        g->max_deg_bound--;
-        if (g->hres->add_status != 1) {
-            if (rc != DCR_OK) {
-                if (rc != DCR_EHIP && g->hres->add_status != 3) tail_finish(g, tc, out_removed, nullptr, false);
-                return rc;
-            }
-            break;
-        }
-        if (attempt == 1) DCR_FAIL(DCR_ECAPACITY, "row still full after relayout");
-        DCR_TRY(relayout(g));
-    }
-    g->imp_n = g->hres->n_cand;
-    *out_n_cand = g->hres->n_cand;
+    const TailPass pass{curv_type, incremental, out_u, out_v, out_val};
+    DCR_TRY(run_tail(g, tc, &pass, out_removed, nullptr));
+    S.n = *out_n_cand = g->hres->n_cand;
     *out_status = g->hres->draw_status;
     if (g->hres->draw_status != 0 || g->hres->add_status == 3) {  // nothing was edited; the pass ran on the same graph
         if (g->hres->draw_status == 0) DCR_FAIL(DCR_ESTATE, "device draw: edit skipped without a draw status");
-        if (out_removed) out_removed[0] = out_removed[1] = -1;
-        if (out_added) out_added[0] = out_added[1] = -1;
-        return DCR_OK;
+        return nothing_edited();
     }
-    tail_finish(g, tc, out_removed, nullptr, false);
-    if (out_added) {
-        out_added[0] = g->hres->cand_i;
-        out_added[1] = g->hres->cand_j;
-    }
+    fill_added(g, out_added);
     return DCR_OK;
 }
 
