@@ -725,22 +725,40 @@ static int run_pass(dcr_graph *g, int curv_type, double *bytes_total, bool incre
     return DCR_OK;
 }
 
-int launch_curvature_pass(dcr_graph *g, int curv_type, bool incremental) {
-    g->last_engine = 2;
-    if (h2_can_take(g, curv_type, incremental)) {  // DCR_PASS=h2: full Balanced Forman passes by the two-hop kernels
+// The switches of a pass: DCR_PASS as parsed when the graph was created, the three DCR_NC_FINE* variables as they are now
+// (read per pass: the tests run every route in one process).
+static PassSwitches read_pass_switches(const dcr_graph *g) {
+    const char *fine = getenv("DCR_NC_FINE"), *full = getenv("DCR_NC_FINE_FULL"), *sweep = getenv("DCR_NC_FINE_SWEEP");
+    PassSwitches sw{};
+    sw.pass_impl = g->pass_impl;
+    sw.fine_on = !(fine && atoi(fine) == 0);
+    sw.fine_full_set = full != nullptr;
+    sw.fine_full_slots = full ? atoll(full) : 0;
+    sw.fine_sweep = sweep ? (atoi(sweep) != 0 ? 1 : 0) : -1;
+    return sw;
+}
+
+int launch_curvature_pass(dcr_graph *g, int curv_type, bool incremental, bool node_centric_only) {
+    const PassFacts facts{g->n, g->n_edges, g->cap_total, g->sum_deg2, g->max_deg_bound, g->pending_edits};
+    PassSwitches sw = read_pass_switches(g);
+    if (node_centric_only) sw.pass_impl = 2;
+    const PassPlan plan = plan_pass(facts, sw, curv_type, incremental);
+    switch (plan.route) {
+    case ROUTE_TWO_HOP:
         g->last_engine = 0;
         return launch_curvature_pass_h2(g);
-    }
-    if (curv_type == DCR_CURV_1D || g->pass_impl == 1) {
+    case ROUTE_EDGE_CENTRIC:
         g->last_engine = 1;
         if (curv_type == DCR_CURV_BFC || curv_type == DCR_CURV_1D)
             return run_pass<MODE_BFC>(g, curv_type, nullptr, incremental);
         return run_pass<MODE_TRI>(g, curv_type, nullptr, incremental);
+    case ROUTE_NC_CLASSES:
+    case ROUTE_NC_EDGES:
+        g->last_engine = 2;
+        DCR_TRY(launch_curvature_pass_nc(g, curv_type, incremental, plan.route == ROUTE_NC_EDGES, plan.list_by_rows));
+        break;
     }
-    // node-centric kernels; the edge-centric ones only for edges beyond their degree limits (two hubs with more
-    // than NC_MAXD neighbours each), which cannot exist while the largest degree is within the limit
-    DCR_TRY(launch_curvature_pass_nc(g, curv_type, incremental));
-    if (g->max_deg_bound > NC_MAXD) {
+    if (plan.hub_supplement) {
         if (curv_type == DCR_CURV_BFC) DCR_TRY(run_pass<MODE_BFC>(g, curv_type, nullptr, incremental, true));
         else DCR_TRY(run_pass<MODE_TRI>(g, curv_type, nullptr, incremental, true));
         DCR_TRY(process_hub_edges(g, curv_type, incremental));  // hub-to-small-node edges (dcr_bfc_giant.hip)
@@ -817,11 +835,21 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     }
     g->dirty_tracked = true;
     g->pending_edits = 0;
-    if (g->profile) DCR_HIP(hipEventRecord(g->ev1, g->stream));
-    if (with_argmin) DCR_TRY(argmin_after_pass());
-    DCR_TRY(sync_result(g));
+    // what follows every launch of a pass: its result
+    auto read_result = [&]() -> int {
+        if (g->profile) DCR_HIP(hipEventRecord(g->ev1, g->stream));
+        if (with_argmin) DCR_TRY(argmin_after_pass());
+        DCR_TRY(sync_result(g));
+        if (g->last_engine == 0)
+            for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres->h2_count[c];
+        return DCR_OK;
+    };
+    auto pass_again = [&](bool node_centric_only) -> int {  // the whole pass once more
+        DCR_TRY(launch_curvature_pass(g, curv_type, false, node_centric_only));
+        return read_result();
+    };
+    DCR_TRY(read_result());
     if (g->last_engine == 0) {
-        for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres->h2_count[c];
         for (int again = 0; again < 6 && g->hres->misc[0] == 0; ++again) {
             if (g->hres->h2_status == 3) {
                 // launched without its retry stage, and some node's tables filled up: nothing was written; from now on every
@@ -833,11 +861,7 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
                 break;
             }
             g->ext_part_valid = false;
-            DCR_TRY(launch_curvature_pass(g, curv_type, false));
-            if (g->profile) DCR_HIP(hipEventRecord(g->ev1, g->stream));
-            if (with_argmin) DCR_TRY(argmin_after_pass());
-            DCR_TRY(sync_result(g));
-            for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres->h2_count[c];
+            DCR_TRY(pass_again(false));
         }
         if (g->hres->h2_status != 0) g->ext_part_valid = false;  // (the closing kernel wrote nothing)
         // (advisor, round 4) a two-hop pass that ended with a status may have left its edge set partly patched (k_h2_eset_apply
@@ -846,15 +870,8 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
         if (g->hres->h2_status != 0 && g->hres->misc[0] == 0) {
             // a table of the two-hop pass filled up (keys of a split node hashed unevenly) or a unit list overflowed:
             // nothing it wrote is kept, the node-centric kernels redo the whole pass
-            const int keep = g->pass_impl;
             g->ext_part_valid = false;
-            g->pass_impl = 2;
-            const int rc = launch_curvature_pass(g, curv_type, false);
-            g->pass_impl = keep;
-            DCR_TRY(rc);
-            if (g->profile) DCR_HIP(hipEventRecord(g->ev1, g->stream));
-            if (with_argmin) DCR_TRY(argmin_after_pass());
-            DCR_TRY(sync_result(g));
+            DCR_TRY(pass_again(true));
         }
     }
     if (g->profile) {
@@ -880,6 +897,22 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
 int dcr_pass_engine(dcr_graph *g, int *out) {
     if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
     *out = g->last_engine;
+    return DCR_OK;
+}
+
+int dcr_pass_plan(int64_t n, int64_t n_edges, int64_t cap_total, double sum_deg2, int32_t max_deg_bound, int pending_edits,
+                  int pass_impl, int fine_on, int fine_full_set, int64_t fine_full_slots, int fine_sweep, int curv_type,
+                  int incremental, int *out_route, int *out_list_by_rows, int *out_hub_supplement, double out_ms[3]) {
+    if (!out_route || !out_list_by_rows || !out_hub_supplement || !out_ms) DCR_FAIL(DCR_EINVAL, "null argument");
+    const PassFacts facts{n, n_edges, cap_total, sum_deg2, max_deg_bound, pending_edits};
+    const PassSwitches sw{pass_impl, fine_on != 0, fine_full_set != 0, fine_full_slots, fine_sweep};
+    const PassPlan plan = plan_pass(facts, sw, curv_type, incremental != 0);
+    *out_route = plan.route;
+    *out_list_by_rows = plan.list_by_rows;
+    *out_hub_supplement = plan.hub_supplement;
+    out_ms[0] = plan.t_h2;
+    out_ms[1] = plan.t_nc;
+    out_ms[2] = plan.t_edges;
     return DCR_OK;
 }
 

@@ -68,7 +68,7 @@ constexpr int LONG_ROW = 60;  // longer rows are streamed by a whole wave; short
 
 // ---- node-centric pass: which edges it takes (dcr_bfc_nc.hip) -------------------------------------------------
 constexpr int NC_CLASSES = 5;
-constexpr int NC_MAXD = 8190;       // largest degree whose neighbour table fits the biggest class
+// NC_MAXD (dcr_pass_route.h): largest degree whose neighbour table fits the biggest class
 constexpr int NC_MAXOTHER = 16382;  // largest degree of the other endpoint (15-bit per-slot counters)
 
 // Edges between a hub above every table size and a node of moderate degree are swept from the hub's side with a

@@ -50,8 +50,6 @@ namespace dcr {
 
 constexpr unsigned H2_EMPTY = 0xFFFFFFFFu;
 constexpr unsigned H2_NBR = 0x80000000u;  // on a key of the small classes' EX: member of N(u) (node ids stay below 2^30)
-constexpr int H2_MAXDEG = 5000;           // flagged neighbours live in every partition's table (5,500 keys in the largest class:
-                                          // a hub near the limit is split into many partitions, one workgroup each)
 constexpr int H2_CLASSES = 5;             // 0-2: one wave per node (<= 64 neighbours), 3-4: one workgroup per unit
 constexpr int H2_WB = 4;                  // weight buckets per class (units are laid out heaviest bucket first)
 // third word of an edge's record: the triangle count with the degree of the row's node above it (both below 2^16: H2_MAXDEG).
@@ -1951,35 +1949,6 @@ bool h2_grow_pools(dcr_graph *g) {
     g->h2_want[1] = std::max<int64_t>(g->h2_want[1], 2 * c + 65536);
     g->h2_want[2] = std::max<int64_t>(g->h2_want[2], 2 * p + 65536);
     return true;
-}
-
-// Which engine takes a full Balanced Forman pass (DCR_PASS=h2 / nc force one).  Round 4: two fitted cost models instead of two
-// thresholds from one graph family.  tools/probe_engine_choice.py times both engines on 31 graphs of four families
-// (preferential attachment m = 2 / 5 / 10 / 20 at 2k-500k nodes, uniform random graphs of mean degree 6-20, grids, a dense
-// random graph; profiles/r04_engine_choice.txt) and the pass times (ms, MI355X) are, within 11-15 % on average,
-//     node-centric:  0.127 + 0.438e-6 E + 1.135e-9 E s + 0.201 min(dmax, 400) / 400
-//     two-hop:       0.120 + 1.193e-6 n + 4.498e-9 (sum d^2) (1 + 60 s / n)          (0.190 until round 5)
-//     edge by edge:  0.012 + E (5.0e-6 + 4.2e-9 s)                                   (round 5, csrc/dcr_bfc_nc.hip)
-// with E edges, n nodes, s = sum d^2 / n (the mean size of a 2-hop neighbourhood), dmax the largest degree: the node-centric
-// engine streams about s entries per edge and loses a tenth of a millisecond to the tail of its hub units; the two-hop
-// engine reads sum d^2 entries per pass, pays per node, and slows down as neighbourhoods overlap (s / n: the share of the
-// graph a 2-hop neighbourhood covers — repeated keys, fuller tables, more partitions).  The two-hop engine is taken when
-// its estimate is the lower one, and never for graphs under 3,000 nodes (both engines are launch-bound there and the
-// node-centric one has fewer launches), for s / n above 0.045 (measured 1.5-5 x slower there) or hubs beyond its tables.
-bool h2_can_take(const dcr_graph *g, int curv_type, bool incremental) {
-    if (curv_type != DCR_CURV_BFC || incremental || g->max_deg_bound > H2_MAXDEG || g->cap_total >= (int64_t)1 << 30) return false;
-    if (g->pass_impl == 3) return true;
-    if (g->pass_impl != 0 || g->n < 3000) return false;
-    const double n = (double)g->n, sd2 = g->sum_deg2, s = sd2 / n, share = s / n;
-    if (share > 0.045) return false;
-    // (round 5: the fixed cost of a two-hop pass went from 0.19 to about 0.10 ms with the three-stream layout — re-fitted, kept a
-    //  little above the measurements: on a 500 k-node graph of two edges per node the per-node cost is underestimated — and small
-    //  graphs have a third candidate, a workgroup per edge: nc_edges_full_ms)
-    static const bool edges_on = !(getenv("DCR_NC_FINE") && atoi(getenv("DCR_NC_FINE")) == 0);
-    const double t_nc = nc_class_full_ms(g);
-    const double t_h2 = 0.120 + 1.193e-6 * n + 4.498e-9 * sd2 * (1.0 + 60.0 * share);
-    if (edges_on && nc_edges_full_ms(g) < t_h2) return false;
-    return t_h2 < t_nc;
 }
 
 static int ensure_h2(dcr_graph *g) {

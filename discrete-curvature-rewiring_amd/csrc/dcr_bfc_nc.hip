@@ -1273,7 +1273,7 @@ __global__ void __launch_bounds__(64 * NCF_W) k_nc_fine_edges(View g, const int2
 }
 
 template <int MODE>
-static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental) {
+static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental, bool list_by_rows) {
     if (g->num_cu <= 0) {
         g->num_cu = 256;
         hipDeviceProp_t prop;
@@ -1289,13 +1289,8 @@ static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental) {
     if (!g->nc_queues) DCR_TRY(dev_alloc(&g->nc_queues, 2 * NC_QUEUES * NC_QUEUE_STRIDE));
     View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr, (int32_t)g->n, 1};
     hipLaunchKernelGGL(k_nc_clear, dim3(1), dim3(256), 0, g->stream, g->dres, g->nc_queues, 0, (unsigned *)nullptr, (int64_t)0);
-    // (the sweep over every slot costs 11 us per 2.6 M slots, the rows of the flagged nodes a chain of five dependent reads, 14 us
-    //  whatever the graph's size: S100k 0.203 / 0.208 ms per iteration sweep / rows, S1M 0.540 / 0.452 — by rows from 4 M slots;
-    //  DCR_NC_FINE_SWEEP=1 / 0 forces one: A/B aid)
-    const char *sweep_env = getenv("DCR_NC_FINE_SWEEP");
-    const bool by_rows = sweep_env ? atoi(sweep_env) == 0 : g->cap_total >= 4000000;
     const int64_t blocks = (g->cap_total + 255) / 256;
-    if (incremental && by_rows && g->touched)
+    if (incremental && list_by_rows && g->touched)  // (no list of the flagged nodes: the sweep)
         hipLaunchKernelGGL(k_nc_fine_list_rows, dim3((unsigned)(2 * g->num_cu)), dim3(256), 0, g->stream, vw, curv_type, g->curv, g->touched,
                            (int64_t)g->n, g->dres, g->nc_fine_list, g->nc_fine_cap, &g->dres->nc_count[0]);
     else if (blocks > 0)
@@ -1314,40 +1309,10 @@ static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental) {
     return DCR_OK;
 }
 
-// Estimates of a full Balanced Forman pass, milliseconds on one MI355X (fitted on 31 graphs of four families, tools/probe_engine_choice.py;
-// E edges, s = sum d^2 / n the mean size of a 2-hop neighbourhood, dmax the largest degree): the class kernels of this file (round 4's
-// model, unchanged) and the edge-by-edge kernels — a workgroup per edge costs its chain of dependent reads plus what it streams.
-double nc_class_full_ms(const dcr_graph *g) {
-    const double n = (double)(g->n > 0 ? g->n : 1), E = (double)g->n_edges, s = g->sum_deg2 / n;
-    const double dmax = (double)(g->max_deg_bound < 400 ? g->max_deg_bound : 400);
-    return 0.127 + 0.438e-6 * E + 1.135e-9 * E * s + 0.201 * dmax / 400.0;
-}
-double nc_edges_full_ms(const dcr_graph *g) {
-    const double n = (double)(g->n > 0 ? g->n : 1), E = (double)g->n_edges, s = g->sum_deg2 / n;
-    return 0.012 + E * (5.0e-6 + 4.2e-9 * s);
-}
-
-int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental) {
-    const char *fine_env = getenv("DCR_NC_FINE");   // (read per call: the tests run both routes in one process)
-    const bool fine_on = !(fine_env && atoi(fine_env) == 0);
-    if (incremental && fine_on && g->pending_edits <= DIRTY_EDITS) {
-        if (curv_type == DCR_CURV_BFC) return run_nc_fine<MODE_BFC>(g, curv_type, true);
-        return run_nc_fine<MODE_TRI>(g, curv_type, true);
-    }
-    // A FULL pass of a small graph, edge by edge too: the class kernels are launch-bound there (plans, four persistent grids and
-    // their joins: 0.17-0.4 ms whatever the graph holds), a workgroup per edge is not — Cora's size (5 k edges) 0.19 -> 0.04 ms,
-    // 25 k edges 0.31 -> 0.17, break-even near 50 k edges (profiles/r05_engine_choice.txt).  Taken when its estimate is the
-    // lowest (nc_edges_full_ms against the two models of h2_can_take; automatic engine choice only: DCR_PASS=nc keeps the class
-    // kernels); DCR_NC_FINE_FULL=<slots> forces it for graphs of at most that many adjacency slots (A/B aid).
-    bool full_edges = false;
-    if (!incremental && fine_on) {
-        const char *full_env = getenv("DCR_NC_FINE_FULL");
-        if (full_env) full_edges = g->cap_total <= atoll(full_env);
-        else full_edges = g->pass_impl == 0 && nc_edges_full_ms(g) < nc_class_full_ms(g);
-    }
-    if (full_edges) {
-        if (curv_type == DCR_CURV_BFC) return run_nc_fine<MODE_BFC>(g, curv_type, false);
-        return run_nc_fine<MODE_TRI>(g, curv_type, false);
+int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental, bool edge_by_edge, bool list_by_rows) {
+    if (edge_by_edge) {
+        if (curv_type == DCR_CURV_BFC) return run_nc_fine<MODE_BFC>(g, curv_type, incremental, list_by_rows);
+        return run_nc_fine<MODE_TRI>(g, curv_type, incremental, list_by_rows);
     }
     if (curv_type == DCR_CURV_BFC) return run_nc<MODE_BFC>(g, curv_type, incremental);
     return run_nc<MODE_TRI>(g, curv_type, incremental);

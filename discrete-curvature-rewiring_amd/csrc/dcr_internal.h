@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "dcr.h"
+#include "dcr_pass_route.h"
 
 namespace dcr {
 
@@ -113,7 +114,6 @@ __device__ inline void journal_edit(DevResult *res, int op, int32_t u, int32_t v
     res->edit_n = i + 1;
 }
 constexpr unsigned DIRTY_COARSE = 0x80u, DIRTY_ENDPOINT = 0x40u;
-constexpr int DIRTY_EDITS = 3;
 __device__ __host__ inline bool edge_dirty(unsigned du, unsigned dv) {
     if ((du | dv) & (DIRTY_COARSE | DIRTY_ENDPOINT)) return true;
     return ((((du >> 1) & dv) | ((dv >> 1) & du)) & 0x15u) != 0u;  // some edit has its A bit on one side, its B bit on the other
@@ -342,8 +342,6 @@ int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_
 // the same from the per-block extrema of the last two-hop pass (g->ext_part_valid), without sweeping the edges again
 int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st = nullptr);
 int launch_argext_both(dcr_graph *g, hipStream_t st = nullptr, bool clear_dirty = false);
-double nc_class_full_ms(const dcr_graph *g);   // estimates of a full pass (csrc/dcr_bfc_nc.hip): class kernels / a workgroup per edge
-double nc_edges_full_ms(const dcr_graph *g);
 // reductions of per-workgroup partial results shared by the GCN kernels (csrc/dcr_gemm.hip, csrc/dcr_gcn.hip)
 void launch_slab_reduce(const float *part, float *C, int64_t mn, int N, int64_t ldc, int splits, hipStream_t st);
 void launch_slab_reduce_cols(const float *part, float *C, int64_t mn, int N, int ncols, int64_t ldc, int splits, hipStream_t st);
@@ -352,12 +350,11 @@ int process_giant_edges(dcr_graph *g, int curv_type);  // dcr_bfc_giant.hip; syn
 int process_hub_edges(dcr_graph *g, int curv_type, bool incremental);  // dcr_bfc_giant.hip; syncs once
 int giant_edge(dcr_graph *g, int u, int v, int du, int dv, int64_t slot, int curv_type, bool need_cycles, int64_t *d_out6);  // result in DevResult after the next sync
 
-// dcr_bfc.hip
-int launch_curvature_pass(dcr_graph *g, int curv_type, bool incremental);
-// dcr_bfc_nc.hip
-int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental);
+// dcr_bfc.hip: plans the pass (dcr_pass_route.h) and launches the plan; node_centric_only: planned as under DCR_PASS=nc
+int launch_curvature_pass(dcr_graph *g, int curv_type, bool incremental, bool node_centric_only = false);
+// dcr_bfc_nc.hip: the class kernels, or a workgroup per edge (its edge list from the flagged nodes' rows or from a sweep)
+int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental, bool edge_by_edge, bool list_by_rows);
 // dcr_bfc_h2.hip
-bool h2_can_take(const dcr_graph *g, int curv_type, bool incremental);
 int launch_curvature_pass_h2(dcr_graph *g);
 bool h2_grow_pools(dcr_graph *g);
 

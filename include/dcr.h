@@ -128,6 +128,17 @@ int dcr_sdrf_tail_at(dcr_graph *g, int64_t cand_index, int do_remove, double rem
  * graph is created), 2 node-centric kernels (csrc/dcr_bfc_nc.hip: everything else, or DCR_PASS=nc), 1 edge-centric kernels
  * (DCR_PASS=edge); -1 before the first pass.  All three produce the same bits. */
 int dcr_pass_engine(dcr_graph *g, int *out);
+/* The route a pass with these facts and switches takes (csrc/dcr_pass_route.h: plan_pass, the function every pass calls): no
+ * handle, no environment, no GPU.  Facts: nodes, undirected edges, adjacency slots, sum of squared degrees, upper bound on the
+ * degrees, edits since the last pass.  Switches: pass_impl 0 automatic / 1 edge / 2 nc / 3 h2 (DCR_PASS), fine_on (DCR_NC_FINE),
+ * fine_full_set and fine_full_slots (DCR_NC_FINE_FULL), fine_sweep -1 unset / 0 / 1 (DCR_NC_FINE_SWEEP).  *out_route: 0 two-hop,
+ * 1 edge-centric, 2 node-centric class kernels, 3 node-centric edge by edge (dcr_pass_engine reports 2 for both);
+ * *out_list_by_rows: the edge list of an incremental edge-by-edge pass comes from the flagged nodes' rows, not from a sweep;
+ * *out_hub_supplement: the kernels for hubs above the node-centric tables follow; out_ms: the estimates two-hop, class
+ * kernels, edge by edge. */
+int dcr_pass_plan(int64_t n, int64_t n_edges, int64_t cap_total, double sum_deg2, int32_t max_deg_bound, int pending_edits,
+                  int pass_impl, int fine_on, int fine_full_set, int64_t fine_full_slots, int fine_sweep, int curv_type,
+                  int incremental, int *out_route, int *out_list_by_rows, int *out_hub_supplement, double out_ms[3]);
 
 /* dcr_sdrf_tail_at followed by dcr_curvature_pass_argmin of the NEXT iteration (sdrf_no_cuda.py:51,56-66 then :24,:27) with
  * one host synchronisation instead of two: the pass is enqueued right behind the edit.  Same results as the two calls. */

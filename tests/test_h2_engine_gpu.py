@@ -174,6 +174,30 @@ def test_automatic_engine_choice(monkeypatch):
     assert G.pass_engine() == 'node-centric'
 
 
+def test_edge_by_edge_switch_is_read_per_pass(monkeypatch):
+    """The automatic choice is three-way and its switches are read with every pass: 12 k edges go edge by edge (reported as
+    node-centric: its estimate is below the two-hop one); with DCR_NC_FINE=0 set later in the same process a second graph of
+    the same edges goes to the two-hop kernels.  (Read once per process, the second answer depended on which test had
+    created the first graph.)  Same bits as the C oracle either way."""
+    from dcr import synthetic
+    from dcr.graph import DcrGraph
+    from oracle import c_oracle
+    monkeypatch.delenv('DCR_PASS', raising=False)
+    monkeypatch.delenv('DCR_NC_FINE', raising=False)
+    monkeypatch.delenv('DCR_NC_FINE_FULL', raising=False)
+    ei, n = synthetic.powerlaw_graph(6000, 2, seed=4)
+    ou, ov, oc = c_oracle.CGraph(ei, n).curv_all('bfc', nthreads=8)
+    for fine, engine in ((None, 'node-centric'), ('0', 'two-hop')):
+        if fine is not None:
+            monkeypatch.setenv('DCR_NC_FINE', fine)
+        G = DcrGraph(ei, n)
+        eu, ev, cv = G.curvature_all('bfc')
+        assert G.pass_engine() == engine
+        assert np.array_equal(eu, ou) and np.array_equal(ev, ov)
+        assert np.array_equal(cv.view(np.int64), oc.view(np.int64)), fine
+        G.close()
+
+
 def test_dense_neighbourhoods_are_redone_one_class_up(h2graph):
     """Small dense graph under the forced engine: the wave classes' tables fill up, the nodes go to the retry list and are
     redone by the largest class with worst-case partitions; the pools of the triangle step grow on demand."""

@@ -1,4 +1,4 @@
-"""Which engine the automatic choice (csrc/dcr_bfc_h2.hip: h2_can_take) picks for a full Balanced Forman pass, against both
+"""Which engine the automatic choice (csrc/dcr_pass_route.h: plan_pass) picks for a full Balanced Forman pass, against both
 engines forced, on several graph families (timing only; parity on such families is tests/fuzz_parity.py).
 -> one line per graph: n, E, sum d^2 / n^2, largest degree, node-centric ms, two-hop ms, edge-by-edge ms (graphs up to 400k edges), the
 automatic choice and its time / the best of the three.
