@@ -1,4 +1,5 @@
-// What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip) and the
+// What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
+// dcr_diffusion.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
 // dcr_graph.hip stay as they are.
@@ -186,6 +187,18 @@ struct AnalysisState {
     int64_t swp_f64_cap = 0;
     unsigned *swp_ctl = nullptr;    // tickets, NaN flag, the [8][256] digit histogram of the keys, the result block, arg-min partials
     int64_t swp_ctl_cap = 0;
+
+    // PageRank diffusion (dcr_diffusion.hip): O(n B) for the solve, O(entries kept by one batch) for the selection
+    double *dif_vec = nullptr;      // z, p, r, x, q as [n][B] each, then the scale [n]
+    int64_t dif_vec_cap = 0;
+    double *dif_part = nullptr;     // per-workgroup partial sums, B per workgroup
+    int64_t dif_part_cap = 0;
+    unsigned char *dif_ctl = nullptr;  // the batch's control block (DifCtl of dcr_diffusion.hip)
+    int64_t dif_ctl_cap = 0;
+    int32_t *dif_row = nullptr;     // the node ids a batch keeps, column after column
+    int64_t dif_row_cap = 0;
+    double *dif_val = nullptr;      // their values, then their weights
+    int64_t dif_val_cap = 0;
 
     void release();  // frees every buffer
 };

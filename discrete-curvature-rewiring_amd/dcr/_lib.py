@@ -42,6 +42,11 @@ class ResistanceOpts(ctypes.Structure):
     _fields_ = [('tol', _f64), ('max_steps', _i64)]
 
 
+class DiffusionOpts(ctypes.Structure):
+    """dcr_diffusion_opts of include/dcr.h."""
+    _fields_ = [('alpha', _f64), ('tol', _f64), ('max_steps', _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -91,6 +96,9 @@ SIGNATURES = {
     'dcr_fiedler_sweep': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.c_int, ctypes.POINTER(SpectralResult),
                                          ctypes.POINTER(SweepResult), _i32p, _f64p]),
     'dcr_effective_resistance': (ctypes.c_int, [_vp, _i32p, _i32p, _i64, ctypes.POINTER(ResistanceOpts), _f64p, _f64p, _i32p]),
+    'dcr_ppr_columns': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), _f64p, _f64p, _i32p]),
+    'dcr_diffusion_sparsify': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), ctypes.c_int, _i64, _f64, _i64p, _i64, _i32p,
+                                              _f64p, _f64p, _f64p, _i32p, _i64p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -43,6 +43,8 @@ SweepCut = namedtuple('SweepCut', ['value', 'size', 'counts', 'order', 'profile'
 
 # pairs of one batch of DcrGraph.effective_resistance: DCR_RES_B of csrc/dcr_resistance.hip
 RESISTANCE_BATCH = 16
+# columns of one batch of DcrGraph.ppr and DcrGraph.diffusion: DIF_B of csrc/dcr_diffusion.hip
+DIFFUSION_BATCH = 16
 
 
 def pack_members(members, num_nodes):
@@ -436,6 +438,97 @@ class DcrGraph:
         if return_info:
             return lower, {'residual': residual, 'steps': steps, 'converged': converged}
         return lower
+
+    # ---- PageRank diffusion (csrc/dcr_diffusion.hip) ----------------------------------
+    def _sources(self, sources):
+        src = np.asarray(sources)
+        if src.size == 0:
+            src = src.reshape(0)
+        if src.ndim != 1:
+            raise ValueError('sources must be one-dimensional')
+        if src.size and (src.min() < 0 or src.max() >= self.num_nodes):
+            raise ValueError('source outside 0 .. num_nodes - 1')
+        return np.ascontiguousarray(src, dtype=np.int32)
+
+    @staticmethod
+    def _warn_unconverged(what, converged, residual, tol, max_steps):
+        if not converged.all():
+            warnings.warn(f'{what}: {int((~converged).sum())} of {converged.size} columns above tol {float(tol):.3e} after '
+                          f'{int(max_steps)} steps (largest residual {residual[~converged].max():.3e})', RuntimeWarning, stacklevel=3)
+
+    def ppr(self, sources, alpha=0.15, tol=1e-10, max_steps=20000, return_info=False):
+        """Columns of the personalised-PageRank matrix ``S = alpha (I - (1 - alpha) D~^-1/2 (A + I) D~^-1/2)^-1`` of the live graph
+        (``D~ = D + I``; include/dcr.h has the definition), as float64 ``[len(sources), n]``: row ``i`` is column ``sources[i]``.
+        ``DIFFUSION_BATCH`` conjugate-gradient solves at a time on the device, read-only on the graph.  ``return_info``: also a
+        dict of ``residual`` (float64, the true ``|alpha e_j - M x|``; every entry is within ``residual / alpha`` of S's), ``steps``
+        (int32) and ``converged`` (bool: ``residual <= tol alpha``).  ``RuntimeWarning`` when a column did not converge;
+        ``ValueError`` on a source outside the graph or ``alpha`` outside (0, 1)."""
+        src = self._sources(sources)
+        P = src.shape[0]
+        out = np.empty((P, self.num_nodes), dtype=np.float64)
+        residual, steps = np.empty(P, dtype=np.float64), np.empty(P, dtype=np.int32)
+        opts = _lib.DiffusionOpts(float(alpha), float(tol), int(max_steps))
+        check(lib().dcr_ppr_columns(self._h, src.ctypes.data_as(_lib._i32p), P, ctypes.byref(opts), out.ctypes.data_as(_lib._f64p),
+                                    residual.ctypes.data_as(_lib._f64p), steps.ctypes.data_as(_lib._i32p)))
+        converged = residual <= float(tol) * float(alpha)
+        self._warn_unconverged('ppr', converged, residual, tol, max_steps)
+        if return_info:
+            return out, {'residual': residual, 'steps': steps, 'converged': converged}
+        return out
+
+    def diffusion(self, alpha=0.15, k=None, eps=None, sources=None, return_info=False, tol=1e-10, max_steps=20000):
+        """The sparsified personalised-PageRank matrix of the live graph (DIGL / GDC): per column ``j`` of ``S`` (``ppr``) either
+        the ``k`` largest entries (larger value first, among equal bits the smaller node id first; everything where ``k >= n``)
+        or the entries ``>= eps``, as the reference's ``get_top_k_matrix`` / ``get_clipped_matrix``
+        (utils/adjacency_matrix_ops.py:26-39) select them, divided by the sum of the column's kept entries.  Exactly one of ``k``
+        and ``eps`` must be given.  ``sources``: the columns, default all nodes.  Solve and selection run on the device; no n x n
+        array exists on either side.
+
+        Returns ``(edge_index, weight)``: int64 ``[2, nnz]`` holding ``[i; j]`` and float64 ``[nnz]``, grouped by column in the
+        order of ``sources`` and by ``i`` ascending within a column.  ``return_info``: also a dict of ``value`` (the raw
+        ``S_ij``), ``ptr`` (int64 ``[columns + 1]``), ``residual``, ``steps`` and ``converged`` per column as ``ppr`` has them."""
+        if (k is None) == (eps is None):
+            raise ValueError('exactly one of k and eps must be given')
+        n = self.num_nodes
+        src = None if sources is None else self._sources(sources)
+        P = n if src is None else src.shape[0]
+        opts = _lib.DiffusionOpts(float(alpha), float(tol), int(max_steps))
+        mode = 0 if eps is None else 1
+        if mode == 0 and int(k) < 1:
+            raise ValueError('k must be >= 1')
+        ptr = np.zeros(P + 1, dtype=np.int64)
+        residual, steps = np.empty(P, dtype=np.float64), np.empty(P, dtype=np.int32)
+        # top-k: the size is known.  threshold: a slab of columns at a time into room for all of their entries
+        slab = P if mode == 0 else max(16, min(P, (1 << 23) // max(n, 1)) // 16 * 16)
+        rows, weights, values = [], [], []
+        for first in range(0, P, max(slab, 1)):
+            count = min(slab, P - first)
+            cap = count * (min(int(k), n) if mode == 0 else n)
+            row, weight, value = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.float64)
+            part_ptr = np.zeros(count + 1, dtype=np.int64)
+            nnz = ctypes.c_int64()
+            part_src = np.arange(first, first + count, dtype=np.int32) if src is None else src[first:first + count]
+            whole = src is None and count == n
+            check(lib().dcr_diffusion_sparsify(self._h, None if whole else part_src.ctypes.data_as(_lib._i32p), count, ctypes.byref(opts),
+                                               mode, int(k) if mode == 0 else 0, float(eps) if mode == 1 else 0.0,
+                                               part_ptr.ctypes.data_as(_lib._i64p), cap, row.ctypes.data_as(_lib._i32p),
+                                               weight.ctypes.data_as(_lib._f64p), value.ctypes.data_as(_lib._f64p),
+                                               residual[first:].ctypes.data_as(_lib._f64p), steps[first:].ctypes.data_as(_lib._i32p),
+                                               ctypes.byref(nnz)))
+            ptr[first + 1:first + count + 1] = ptr[first] + part_ptr[1:]
+            rows.append(row[:nnz.value])
+            weights.append(weight[:nnz.value])
+            values.append(value[:nnz.value])
+        row = np.concatenate(rows) if rows else np.empty(0, dtype=np.int32)
+        weight = np.concatenate(weights) if weights else np.empty(0, dtype=np.float64)
+        value = np.concatenate(values) if values else np.empty(0, dtype=np.float64)
+        cols = np.arange(n, dtype=np.int64) if src is None else src.astype(np.int64)
+        edge_index = np.stack([row.astype(np.int64), np.repeat(cols, np.diff(ptr))])
+        converged = residual <= float(tol) * float(alpha)
+        self._warn_unconverged('diffusion', converged, residual, tol, max_steps)
+        if return_info:
+            return edge_index, weight, {'value': value, 'ptr': ptr, 'residual': residual, 'steps': steps, 'converged': converged}
+        return edge_index, weight
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

@@ -282,6 +282,49 @@ int dcr_effective_resistance(dcr_graph *g, const int32_t *u, const int32_t *v, i
                              double *out_lower /* host [P] */, double *out_residual /* host [P] */,
                              int32_t *out_steps /* host [P] or NULL */);
 
+/* ---- PageRank diffusion rewiring, DIGL / GDC (csrc/dcr_diffusion.hip) -------------------------------------------------------
+ * With A~ = A + I, d~ = deg + 1, H = D~^-1/2 A~ D~^-1/2 of the live graph and 0 < alpha < 1:  M = I - (1 - alpha) H, symmetric
+ * positive definite with spectrum in [alpha, 2 - alpha], and S = alpha M^-1, the personalised-PageRank matrix.  Column j of S
+ * solves M x = alpha e_j; S_jj = 1 at an isolated node.  The reference never builds S; utils/adjacency_matrix_ops.py:26-39 holds
+ * the two sparsifiers written for it (get_top_k_matrix, get_clipped_matrix) on dense N x N arrays, restated here per column.
+ * Columns are solved 16 at a time as independent conjugate-gradient iterations from x = 0 in one multi-column mat-vec.
+ *   dcr_ppr_columns         out: host double [P][num_nodes], row i = column sources[i] of S.
+ *   dcr_diffusion_sparsify  per column, mode 0: the k largest entries (all of them where k >= num_nodes); larger value first,
+ *                           among equal bits the smaller node id first.  mode 1: the entries >= eps.  sources NULL stands for all
+ *                           nodes in order, and P must then be num_nodes.  The output is grouped by column in the order of
+ *                           `sources`, within a column by node id ascending:
+ *                             out_ptr     host int64 [P + 1], column i holds entries out_ptr[i] .. out_ptr[i + 1] - 1
+ *                             out_row     host int32 [cap], the node ids
+ *                             out_value   host double [cap], the raw S_ij
+ *                             out_weight  host double [cap], out_value divided by the sum of the column's kept values, the sum
+ *                                         added in node-id order (divided by 1 where that sum is not positive, as the reference
+ *                                         does).  A column with nothing kept has no entries.
+ *                             out_nnz     the number of entries of all columns
+ *                           When cap is smaller than that number the call returns DCR_ECAPACITY with *out_nnz set to the number
+ *                           needed and out_ptr complete; out_row, out_weight and out_value then hold nothing of use (they may be
+ *                           NULL when cap is 0: a counting call).  In mode 0 the number is P min(k, num_nodes) and the call
+ *                           returns before any solve; in mode 1 every column is solved to be counted.
+ *   out_residual  host double [P]: the true residual |alpha e_j - M x|_2 of the returned column, from a mat-vec of its own.  A
+ *                 column has converged when it is <= tol alpha.  |x_i - S_ij| <= out_residual / alpha for every i.
+ *   out_steps     host int32 [P] or NULL: CG steps of the column.  A column stops, on the device, in the step where the
+ *                 recurrence's |r| <= tol alpha, or where p^T M p is not a positive finite number.
+ * opts NULL = defaults: alpha 0.15, tol 1e-10, max_steps 20000.  A column that ran out of steps is still DCR_OK.
+ * All arithmetic is fp64 without floating-point atomics and every reduction has a fixed order in which the columns of a batch
+ * do not meet: a column's outputs are the same bits whatever else is in the call and wherever in it the source stands.
+ * READ-ONLY on the graph, runs on the graph's stream and is synchronous on return; O(16 num_nodes) doubles of work buffers
+ * and the entries one batch keeps stay on the handle until dcr_graph_destroy.  No num_nodes x num_nodes buffer exists.
+ * Null g, out, out_ptr, out_residual, out_nnz (sources too in dcr_ppr_columns); P < 0; a source outside 0 .. num_nodes - 1;
+ * alpha outside (0, 1); tol negative or NaN; max_steps < 1; a mode outside {0, 1}; k < 1 in mode 0; eps NaN in mode 1; cap < 0, or
+ * cap > 0 with a NULL entry array: DCR_EINVAL before any device call.  P == 0: DCR_OK, nothing written. */
+typedef struct { double alpha, tol; int64_t max_steps; } dcr_diffusion_opts;
+int dcr_ppr_columns(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_diffusion_opts *opts /* NULL = defaults */,
+                    double *out /* host [P][n] */, double *out_residual /* host [P] */, int32_t *out_steps /* host [P] or NULL */);
+int dcr_diffusion_sparsify(dcr_graph *g, const int32_t *sources /* NULL = all nodes */, int64_t P,
+                           const dcr_diffusion_opts *opts /* NULL = defaults */, int mode /* 0 top-k, 1 threshold */, int64_t k,
+                           double eps, int64_t *out_ptr /* host [P + 1] */, int64_t cap, int32_t *out_row, double *out_weight,
+                           double *out_value, double *out_residual /* host [P] */, int32_t *out_steps /* host [P] or NULL */,
+                           int64_t *out_nnz);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results

@@ -1,0 +1,88 @@
+"""Dense numpy restatement of what DcrGraph.ppr and DcrGraph.diffusion compute (host only, graphs of a few thousand nodes at most):
+S = alpha (I - (1 - alpha) D~^-1/2 (A + I) D~^-1/2)^-1 with D~ = D + I from ``numpy.linalg.solve``, the two per-column sparsifiers
+with the device's tie-break (larger value first, among equal values the smaller node id first), and the column normalisation with
+the sum taken in node-id order.  Nothing here imports the package under test."""
+import os
+
+import numpy as np
+
+from resistance_ref import EPS, adjacency, barbell, complete, cycle, hub_with_tail, path, random_graph, star, triangle_star_isolated  # noqa: F401
+from spectral_ref import PLAN_NAMES, plan_family, plan_nodes, row_plan  # noqa: F401
+
+ALPHAS = (0.05, 0.15)
+
+
+def operator(edge_index, n, alpha):
+    """M = I - (1 - alpha) H, H = D~^-1/2 (A + I) D~^-1/2."""
+    a = adjacency(edge_index, n) + np.eye(n)
+    s = 1.0 / np.sqrt(a.sum(axis=1))
+    return np.eye(n) - (1.0 - alpha) * (s[:, None] * a * s[None, :])
+
+
+def ppr_matrix(edge_index, n, alpha):
+    """S, dense: column j solves M x = alpha e_j."""
+    return np.linalg.solve(operator(edge_index, n, alpha), alpha * np.eye(n))
+
+
+def ppr_columns(edge_index, n, alpha, sources):
+    """[len(sources), n]: row i is column sources[i] of S, without the other columns."""
+    rhs = np.zeros((n, len(sources)))
+    rhs[np.asarray(sources, dtype=np.int64), np.arange(len(sources))] = alpha
+    return np.linalg.solve(operator(edge_index, n, alpha), rhs).T.copy()
+
+
+def allow(n):
+    """The rounding allowance of the acceptance rule (resistance_ref.allow with entries <= 1): 64 n 2^-52."""
+    return 64.0 * n * EPS
+
+
+def top_k(column, k):
+    """Sorted node ids of the k entries that come first by (larger value, smaller id); all of them where k >= n."""
+    column = np.asarray(column)
+    order = np.lexsort((np.arange(column.size), -column))
+    return np.sort(order[:min(int(k), column.size)])
+
+
+def threshold(column, eps):
+    """Sorted node ids of the entries >= eps."""
+    return np.flatnonzero(np.asarray(column) >= eps)
+
+
+def ordered_sum(values):
+    """The values added one after the other (numpy.sum adds in pairs)."""
+    values = np.asarray(values, dtype=np.float64)
+    return float(np.cumsum(values)[-1]) if values.size else 0.0
+
+
+def normalise(values):
+    """values / their sum in the order given; by 1 where the sum is not positive (as the reference's helpers divide)."""
+    total = ordered_sum(values)
+    return np.asarray(values, dtype=np.float64) / (total if total > 0.0 else 1.0)
+
+
+def sparsify(S, k=None, eps=None, columns=None):
+    """(ptr, row, weight, value) over the columns of S in the layout of DcrGraph.diffusion: grouped by column, by node id within."""
+    assert (k is None) != (eps is None)
+    cols = range(S.shape[1]) if columns is None else columns
+    ptr, rows, weights, values = [0], [], [], []
+    for j in cols:
+        keep = top_k(S[:, j], k) if eps is None else threshold(S[:, j], eps)
+        rows.append(keep)
+        values.append(S[keep, j])
+        weights.append(normalise(S[keep, j]))
+        ptr.append(ptr[-1] + keep.size)
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.empty(0, dtype=dt)   # noqa: E731
+    return np.array(ptr, dtype=np.int64), cat(rows, np.int32), cat(weights, np.float64), cat(values, np.float64)
+
+
+def recorded(golden_dir, fixture, name):
+    """(ptr int64, rows int32, weights) of one helper's result in tests/golden/diffusion_reference.json's array file; name is
+    case['top_k'] or case['clipped']."""
+    with np.load(os.path.join(golden_dir, fixture['arrays']), allow_pickle=False) as z:
+        return z[name + '_ptr'].astype(np.int64), z[name + '_rows'].astype(np.int32), z[name + '_weights']
+
+
+def graphs():
+    """name -> (edge_index, n): the graphs of the value and selection tests; the tie-rich ones are there on purpose."""
+    return {'path8': path(8), 'cycle7': cycle(7), 'star6': star(6), 'barbell20_4': barbell(20, 4), 'random300': random_graph(300, 5),
+            'hub2100': hub_with_tail(2100)}
