@@ -13,12 +13,12 @@ from rewiring.sdrf_cuda_bfc import sdrf_cuda_bfc
 
 
 
-def run(seed=1, seconds=120.0, graphs=None):
+def run(seed=1, seconds=120.0, graphs=None, n_range=(4, 110)):
     rng = np.random.Generator(np.random.PCG64(seed))
     t_end = time.time() + seconds
     n_graphs = n_vals = n_runs = 0
     while time.time() < t_end and (graphs is None or n_graphs < graphs):
-        n = int(rng.integers(4, 110))
+        n = int(rng.integers(n_range[0], n_range[1]))
         p = float(rng.uniform(0.03, 0.4))
         undirected = bool(rng.integers(0, 2))
         m = rng.random((n, n)) < p

@@ -50,3 +50,14 @@ def test_fuzz_bfc_cuda_small_budget():
     import fuzz_bfc_cuda
     graphs, values, runs = fuzz_bfc_cuda.run(seed=7, seconds=120.0, graphs=40)
     assert graphs == 40 and values > 0
+
+
+def test_fuzz_bfc_cuda_beyond_110_nodes():
+    """The same sweep on graphs of 110 to 259 nodes: two to five trips of the dense kernels' 64-wide stride loop, which the
+    default range (4 to 109 nodes) reaches only at its upper end.  G = 4 graphs: with the product side stubbed out the
+    oracle's share of run(seed=2, graphs=G, n_range=(110, 260)) measured 6.9 s at G = 2, 13.0 s at G = 3, 13.6 s at
+    G = 4 and 21.3 s at G = 8 on the CPU (dense draws, p up to 0.4, dominate: the third graph alone costs 6 s), so 4 is
+    the largest count that stays near ten seconds."""
+    import fuzz_bfc_cuda
+    graphs, values, runs = fuzz_bfc_cuda.run(seed=2, seconds=240.0, graphs=4, n_range=(110, 260))
+    assert graphs == 4 and values > 0

@@ -20,7 +20,10 @@ Both files are imported unmodified.  Harness-side glue only:
 
 Only numbers are written: inputs (edge lists, parameters, seeds) and outputs (C, D as float32 hex, traces, edge lists).
 
-Usage:  python tools/make_golden_cuda_compat.py
+Usage:  python tools/make_golden_cuda_compat.py [--wide-only]
+
+A second catalogue (graphs of 65 to 257 nodes from tests/bfc_dense_ref.py, past one trip of the product kernels' 64-wide
+stride loop) goes to tests/golden/bfc_cuda_curvature_wide.json; ``--wide-only`` writes that file alone.
 """
 import json
 import os
@@ -429,6 +432,64 @@ def sdrf_cases():
     return cases
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# second catalogue: graphs above 64 nodes (tests/golden/bfc_cuda_curvature_wide.json)
+# ---------------------------------------------------------------------------------------------------------------------
+WIDE = (('hub_last', 65), ('hub_last', 130), ('hub_last', 257), ('directed_tail', 70), ('directed_tail', 130))
+
+
+def u32hex(t):
+    return [f'{int(v):08x}' for v in np.ascontiguousarray(np.asarray(t, dtype=np.float32)).view(np.uint32).ravel()]
+
+
+def wide_cases():
+    """The families of tests/bfc_dense_ref.py (built by that module's own seeded code) through the reference's two
+    kernels.  Kept small: the pairs, their weights and the values AT the pairs (the rest of C is asserted zero here);
+    float32 bit patterns as 8 hex digits."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import bfc_dense_ref as bd
+    cases = []
+    for family, N in WIDE:
+        directed = family == 'directed_tail'
+        seed = 1000 + N if directed else N                       # bfc_dense_ref.family_graphs' seeding
+        A = bd.directed_tail(N, seed)[0] if directed else bd.hub_last(N, seed)
+        CONTEXT.update(graph=None, array=None)
+        C = ref_cuda.balanced_forman_curvature(torch.from_numpy(A.copy())).numpy()
+        nz = np.nonzero(A)
+        assert not C[A == 0].any()
+        rec = {'family': family, 'num_nodes': N, 'seed': seed, 'directed': directed,
+               'pairs': [[int(t) for t in nz[0]], [int(t) for t in nz[1]]], 'weights': [int(t) for t in A[nz]],
+               'C': u32hex(C[nz]), 'post_delta': []}
+        for x, y in bd.base_queries(A, C, directed):
+            xn, yn = bd.neighbour_lists(A, x, y, directed)
+            D = ref_cuda.balanced_forman_post_delta(torch.from_numpy(A.copy()), x, y, xn, yn).numpy()
+            rec['post_delta'].append({'x': x, 'y': y, 'i_neighbors': xn, 'j_neighbors': yn, 'D': u32hex(D)})
+        cases.append(rec)
+        print('wide', family, N, 'nnz', len(nz[0]), 'post-delta', [len(p['D']) for p in rec['post_delta']], 'mode', MODE)
+    return cases
+
+
+def main_wide():
+    global MODE
+    MODE = 'wide'
+    wide = wide_cases()
+    MODE = 'typed'
+    typed = wide_cases()
+    MODE = 'wide'
+    if json.dumps(wide) != json.dumps(typed):
+        raise SystemExit('bfc_cuda_curvature_wide.json NOT written: the two float32 typing models disagree')
+    path = os.path.join(GOLDEN, 'bfc_cuda_curvature_wide.json')
+    with open(path, 'w') as f:
+        json.dump({'_about': 'outputs of the reference curvature/bfc_cuda.py executed on the CPU through a harness-side numba.cuda '
+                             'stand-in (tools/make_golden_cuda_compat.py --wide-only) on the hub_last / directed_tail graphs of '
+                             'tests/bfc_dense_ref.py; identical under both float32 typing models; C holds the values at the '
+                             'non-zero pairs (row-major), D the whole post-delta matrix; float32 bit patterns as hex',
+                   'cases': wide}, f, separators=(',', ':'))
+    limit = max(os.path.getsize(os.path.join(GOLDEN, n)) for n in os.listdir(GOLDEN) if n != 'bfc_cuda_curvature_wide.json')
+    assert os.path.getsize(path) <= limit, 'larger than the largest fixture'
+    print('wrote bfc_cuda_curvature_wide.json', os.path.getsize(path), 'bytes')
+
+
 def main():
     global MODE
     about = ('outputs of the reference curvature/bfc_cuda.py and rewiring/sdrf_cuda_bfc.py executed on the CPU through a '
@@ -462,4 +523,6 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    if '--wide-only' not in sys.argv[1:]:
+        main()
+    main_wide()
