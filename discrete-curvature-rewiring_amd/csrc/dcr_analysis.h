@@ -1,5 +1,5 @@
 // What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
-// dcr_diffusion.hip) and the
+// dcr_diffusion.hip, dcr_fosr.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
 // dcr_graph.hip stay as they are.
@@ -13,6 +13,7 @@ constexpr int SP_LONG_DEG = 2048;   // rows above this degree: a workgroup a row
 constexpr int SP_CHECK_EVERY = 8;   // solver steps between host synchronisations
 
 inline unsigned blocks_of(int64_t n, int64_t per = 256) { return (unsigned)((n + per - 1) / per); }
+__device__ inline double inv_sqrt_deg(int d) { return d > 0 ? 1.0 / sqrt((double)d) : 0.0; }  // the scale s of a node of degree d
 
 // ---- deterministic reductions: no floating-point atomics; per-workgroup partials go through the L2 (st_agent), the last arriver
 // closes them in index order (ld_agent) -------------------------------------------------------------------------------------------
@@ -200,6 +201,14 @@ struct AnalysisState {
     double *dif_val = nullptr;      // their values, then their weights
     int64_t dif_val_cap = 0;
 
+    // FoSR (dcr_fosr.hip): all O(n)
+    double *fsr_vec = nullptr;      // [4][n]: the iterate x, its projection, s ⊙ projection, z
+    int64_t fsr_vec_cap = 0;
+    double *fsr_part = nullptr;     // per-workgroup partials: sums, or (product, {u, partner}) pairs of the pick
+    int64_t fsr_part_cap = 0;
+    unsigned char *fsr_ctl = nullptr;  // tickets and the result block (FsrCtl of dcr_fosr.hip)
+    int64_t fsr_ctl_cap = 0;
+
     void release();  // frees every buffer
 };
 
@@ -209,6 +218,12 @@ AnalysisState &analysis_of(dcr_graph *g);  // the graph's state, created on firs
 int build_row_plan(dcr_graph *g, RowPlan *plan, std::vector<int2> *info_out);
 int graph_components(dcr_graph *g, std::vector<int32_t> &labels);  // labels (smallest node id of the component) into spc_label and onto the host
 void inv_sqrt_degree(dcr_graph *g, double *s);  // launches s = 1 / sqrt(deg), 0 at degree 0, on the graph's stream
+
+// dcr_sweep.hip: the sweep's order for another call.  *score: the [n] device buffer the caller's kernel fills; sweep_order then
+// sorts it as the sweep cut does (ascending by (score, node id), -0.0 == +0.0) and leaves *order (the node at each position) and
+// *rank (its inverse) on the device.  One host synchronisation; a NaN in the score is DCR_ESTATE.
+int sweep_score_buffer(dcr_graph *g, double **score);
+int sweep_order(dcr_graph *g, const int32_t **order, const int32_t **rank);
 
 // dcr_spectral.hip
 struct SpectralKept {  // what spectral_solve leaves in device memory: the unit Ritz vector y, the scale s = 1 / sqrt(deg)

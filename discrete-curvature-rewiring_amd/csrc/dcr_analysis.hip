@@ -76,8 +76,7 @@ int graph_components(dcr_graph *g, std::vector<int32_t> &labels) {
 __global__ void __launch_bounds__(256) k_inv_sqrt_degree(const int2 *__restrict__ rowinfo, double *__restrict__ s, int64_t n) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= n) return;
-    const int d = rowinfo[v].y;
-    s[v] = d > 0 ? 1.0 / sqrt((double)d) : 0.0;
+    s[v] = inv_sqrt_deg(rowinfo[v].y);
 }
 
 void inv_sqrt_degree(dcr_graph *g, double *s) {
@@ -130,7 +129,7 @@ AnalysisState &analysis_of(dcr_graph *g) {
 void AnalysisState::release() {
     void *ptrs[] = {rows,      chg_members, chg_counts, chg_values, spc_label, spc_ctl,  spc_vec,   spc_basis, spc_rows, spc_chunks,
                     spc_part,  spc_small,   res_vec,    res_part,   res_ctl,   swp_keys, swp_idx,   swp_table, swp_f64,  swp_ctl,
-                    dif_vec,   dif_part,    dif_ctl,    dif_row,    dif_val};
+                    dif_vec,   dif_part,    dif_ctl,    dif_row,    dif_val,   fsr_vec,  fsr_part,  fsr_ctl};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     *this = AnalysisState();

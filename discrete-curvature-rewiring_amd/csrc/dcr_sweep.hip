@@ -341,9 +341,8 @@ static int sweep_buffers(dcr_graph *g, SweepPlan *P) {
     return DCR_OK;
 }
 
-// the score is in P.score; rows: the graph's row plan
-static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const RowPlan &rows, dcr_sweep_result *out, int32_t *out_order,
-                     double *out_profile) {
+// keys, the sort passes and the rank of what is in P.score; *order_out: the node at each position
+static int sweep_sort(dcr_graph *g, const SweepPlan &P, const int32_t **order_out) {
     const int64_t n = P.n;
     hipStream_t st = g->stream;
     DCR_HIP(hipMemsetAsync(P.ctl, 0, sizeof(unsigned) * SW_CTL_WORDS, st));
@@ -368,9 +367,20 @@ static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const Row
                            P.ids[cur ^ 1], n, 8 * pass, P.tile, P.tiles, P.table);
         cur ^= 1;
     }
-    const int32_t *order = P.ids[cur];
+    hipLaunchKernelGGL(k_sweep_rank, dim3(blocks_of(n)), dim3(256), 0, st, P.ids[cur], P.rank, n);
+    DCR_HIP(hipGetLastError());
+    *order_out = P.ids[cur];
+    return DCR_OK;
+}
+
+// the score is in P.score; rows: the graph's row plan
+static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const RowPlan &rows, dcr_sweep_result *out, int32_t *out_order,
+                     double *out_profile) {
+    const int64_t n = P.n;
+    hipStream_t st = g->stream;
+    const int32_t *order;
+    DCR_TRY(sweep_sort(g, P, &order));
     int32_t *d_in = P.diff, *d_lo = P.diff + n, *d_hi = P.diff + 2 * n;
-    hipLaunchKernelGGL(k_sweep_rank, dim3(blocks_of(n)), dim3(256), 0, st, order, P.rank, n);
     DCR_HIP(hipMemsetAsync(P.diff, 0, sizeof(int32_t) * 3 * (size_t)n, st));
     if (g->n_edges > 0)
         hipLaunchKernelGGL(k_sweep_edges, dim3(row_grid<SweepRows>(rows)), dim3(256), 0, st, rows, g->rowinfo, g->col, P.rank, d_in, d_lo, d_hi);
@@ -392,6 +402,21 @@ static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const Row
     out->lo = res.lo;
     out->hi = res.hi;
     return DCR_OK;
+}
+
+// the order alone, for the other analysis calls (dcr_analysis.h): the caller's kernel writes the score, then asks for the sort
+int sweep_score_buffer(dcr_graph *g, double **score) {
+    SweepPlan P;
+    DCR_TRY(sweep_buffers(g, &P));
+    *score = P.score;
+    return DCR_OK;
+}
+
+int sweep_order(dcr_graph *g, const int32_t **order, const int32_t **rank) {
+    SweepPlan P;
+    DCR_TRY(sweep_buffers(g, &P));
+    *rank = P.rank;
+    return sweep_sort(g, P, order);
 }
 
 static int sweep_args(const dcr_graph *g, int definition, const void *out) {

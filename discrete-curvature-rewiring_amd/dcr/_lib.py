@@ -47,6 +47,11 @@ class DiffusionOpts(ctypes.Structure):
     _fields_ = [('alpha', _f64), ('tol', _f64), ('max_steps', _i64)]
 
 
+class FosrOpts(ctypes.Structure):
+    """dcr_fosr_opts of include/dcr.h."""
+    _fields_ = [('num_iterations', _i64), ('initial_power_iters', _i64), ('seed', ctypes.c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -99,6 +104,8 @@ SIGNATURES = {
     'dcr_ppr_columns': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), _f64p, _f64p, _i32p]),
     'dcr_diffusion_sparsify': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), ctypes.c_int, _i64, _f64, _i64p, _i64, _i32p,
                                               _f64p, _f64p, _f64p, _i32p, _i64p]),
+    'dcr_fosr_pick': (ctypes.c_int, [_vp, _f64p, _i32p, _i32p, _f64p, _f64p, ctypes.POINTER(ctypes.c_int)]),
+    'dcr_fosr': (ctypes.c_int, [_vp, ctypes.POINTER(FosrOpts), _f64p, _i32p, _i32p, _i64p, _f64p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

@@ -45,6 +45,8 @@ SweepCut = namedtuple('SweepCut', ['value', 'size', 'counts', 'order', 'profile'
 RESISTANCE_BATCH = 16
 # columns of one batch of DcrGraph.ppr and DcrGraph.diffusion: DIF_B of csrc/dcr_diffusion.hip
 DIFFUSION_BATCH = 16
+# ranks one LDS window of the FoSR pick covers on a row above 2,048 neighbours: FSR_WINDOW of csrc/dcr_fosr.hip
+FOSR_WINDOW = 4096
 
 
 def pack_members(members, num_nodes):
@@ -529,6 +531,47 @@ class DcrGraph:
         if return_info:
             return edge_index, weight, {'value': value, 'ptr': ptr, 'residual': residual, 'steps': steps, 'converged': converged}
         return edge_index, weight
+
+    # ---- FoSR (csrc/dcr_fosr.hip) -------------------------------------------------------
+    def _vector(self, x, what):
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        if x.ndim != 1 or x.shape[0] != self.num_nodes:
+            raise ValueError(f'{what} must have shape [{self.num_nodes}]')
+        return x
+
+    def fosr_pick(self, x, return_y=False):
+        """The edge FoSR would add for the vector ``x`` (float64 ``[n]``): with ``y = x / sqrt(deg + 1)``, the pair ``(u, v)`` of
+        distinct non-adjacent nodes with the smallest ``y[u] * y[v]``, as ``(u, v, product)``; ``None`` where every pair is an edge.
+        include/dcr.h states which of several minimal pairs it is.  Chosen on the device in O(n log n + E), read-only on the
+        graph.  ``return_y``: also the ``y`` that was ordered (then ``(pick or None, y)``).  ``ValueError`` on a NaN, a vector of the
+        wrong length or fewer than two nodes."""
+        x = self._vector(x, 'x')
+        u, v, found, product = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int(), ctypes.c_double()
+        y = np.empty(self.num_nodes, dtype=np.float64) if return_y else None
+        check(lib().dcr_fosr_pick(self._h, x.ctypes.data_as(_lib._f64p), ctypes.byref(u), ctypes.byref(v), ctypes.byref(product),
+                                  y.ctypes.data_as(_lib._f64p) if return_y else None, ctypes.byref(found)))
+        pick = (u.value, v.value, product.value) if found.value else None
+        return (pick, y) if return_y else pick
+
+    def fosr(self, num_iterations, initial_power_iters=50, x0=None, seed=0, return_vector=False):
+        """FoSR, first-order spectral rewiring (Karhadkar et al., ICLR 2023), on the live graph: ``initial_power_iters`` power
+        steps on ``x0`` (default: the Philox vector of ``seed``), then ``num_iterations`` times ``fosr_pick``, ``add_edge`` and one
+        power step with the new degrees.  Returns the added edges in order as int64 ``[2, added]``; ``added`` is smaller than
+        ``num_iterations`` where no free pair was left or the iterate vanished.  ``return_vector``: also the final iterate.
+
+        Unlike the published code, which falls back to an existing edge or a self-loop when every free product is positive,
+        only pairs that are not yet edges are candidates.  MUTATES the graph.  ``ValueError`` on a graph without edges."""
+        x0 = None if x0 is None else self._vector(x0, 'x0')
+        opts = _lib.FosrOpts(int(num_iterations), int(initial_power_iters), int(seed))
+        room = max(int(num_iterations), 1)
+        u, v = np.empty(room, dtype=np.int32), np.empty(room, dtype=np.int32)
+        added = ctypes.c_int64()
+        x = np.empty(self.num_nodes, dtype=np.float64) if return_vector else None
+        check(lib().dcr_fosr(self._h, ctypes.byref(opts), None if x0 is None else x0.ctypes.data_as(_lib._f64p),
+                             u.ctypes.data_as(_lib._i32p), v.ctypes.data_as(_lib._i32p), ctypes.byref(added),
+                             x.ctypes.data_as(_lib._f64p) if return_vector else None))
+        edges = np.stack([u[:added.value], v[:added.value]]).astype(np.int64)
+        return (edges, x) if return_vector else edges
 
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):

@@ -325,6 +325,48 @@ int dcr_diffusion_sparsify(dcr_graph *g, const int32_t *sources /* NULL = all no
                            double *out_value, double *out_residual /* host [P] */, int32_t *out_steps /* host [P] or NULL */,
                            int64_t *out_nnz);
 
+/* ---- FoSR, first-order spectral rewiring (csrc/dcr_fosr.hip; Karhadkar, Banerjee, Montufar, ICLR 2023; no counterpart in the
+ * reference) ------------------------------------------------------------------------------------------------------------------
+ * Adds, one at a time, the edge that raises the spectral gap most to first order.  With deg the current degrees, r = sqrt(deg),
+ * vol = sum deg and s = 1 / sqrt(deg) (0 at degree 0):
+ *   power step on x:   x <- x - (x . r / vol) r;   z <- x + s ⊙ A (s ⊙ x);   x <- z / |z|_2
+ *                      All fp64, no floating-point atomics, every reduction in a fixed order: the same input gives the same bits.
+ *                      Where |z| is 0 or not finite the loop stops there: x stays the iterate before that step, the call is still
+ *                      DCR_OK and reports the edges added so far.
+ *   pick on x:         y_i = x_i / sqrt(deg_i + 1).  The nodes are ordered as the sweep cut orders them: ascending by (y, node id),
+ *                      -0.0 equal to +0.0 (np.lexsort((ids, np.where(y == 0, 0.0, y)))).  For a node u the eligible nodes are those
+ *                      that are neither u nor adjacent to u; partner(u) is the LAST eligible node of the order where y_u < 0 and
+ *                      the FIRST one otherwise (zero included); none where nothing is eligible.  p(u) = fl(y_u y_partner(u)).  The
+ *                      pick is the u with the smallest p(u), among equal values (-0.0 == 0.0) the smallest u, as (u, partner(u)).
+ *                      Rounded multiplication is monotone, so p is the exact minimum of fl(y_u y_v) over all non-adjacent pairs
+ *                      u != v.  It is found in O(n log n + E): partner(u) has rank below deg_u + 2 from its end of the order, a
+ *                      bitmap of that many bits per row; no num_nodes x num_nodes array exists.  (A product 0 x inf is NaN and no
+ *                      candidate.)
+ *   loop:              initial_power_iters power steps; then num_iterations times: pick, add the edge, one power step with the
+ *                      new degrees.  A disconnected graph needs no special case: after the projection the iterate has both
+ *                      signs, components are joined first.
+ * One deliberate difference from the published code: that code zeroes the products of existing edges and of the diagonal and
+ * takes the arg-min of the dense outer product, so when every free product is positive it re-adds an existing edge or adds a
+ * self-loop.  Here only free pairs are candidates; a graph without a free pair gives "none" and the loop stops.
+ *   dcr_fosr_pick  x: host double [num_nodes].  *out_found 0: no free pair (out_u = out_v = -1, out_product 0).  out_y, host
+ *                  double [num_nodes] or NULL: the y that was ordered.  READ-ONLY on the graph as the sweep is.  A NaN in x is
+ *                  DCR_EINVAL, found on the host.
+ *   dcr_fosr       x0: host double [num_nodes], or NULL: x0_v = ((53 bits) + 1/2) 2^-52 - 1, uniform in (-1, 1), the 53 bits being
+ *                  ((r[0] | r[1] << 32) >> 11) of Philox-4x32-10 with counter {v, 0} under key seed (csrc/dcr_philox.h), the
+ *                  construction of the spectral solver's start vector, on every node.  out_u / out_v: host int32
+ *                  [num_iterations], the added edges in order, *out_added of them; out_x, host double [num_nodes] or NULL: the
+ *                  final iterate.  MUTATES the graph: every edge goes through dcr_graph_add_edge, so the incremental flags, the
+ *                  edit journal and the caches behave as for any added edge.  The pick comes back to the host once per iteration
+ *                  (one 56-byte block).  A graph without edges, or a NaN in x0: DCR_EINVAL.
+ * Both run on the graph's stream and are synchronous on return; O(num_nodes) work buffers stay on the handle until
+ * dcr_graph_destroy.  Null g, opts, x or a null output other than out_y / out_x (out_u / out_v may be NULL where num_iterations is
+ * 0); a negative count; num_nodes < 2: DCR_EINVAL before any device call. */
+typedef struct { int64_t num_iterations, initial_power_iters; uint64_t seed; } dcr_fosr_opts;
+int dcr_fosr_pick(dcr_graph *g, const double *x /* host [n] */, int32_t *out_u, int32_t *out_v, double *out_product,
+                  double *out_y /* host [n] or NULL */, int *out_found);
+int dcr_fosr(dcr_graph *g, const dcr_fosr_opts *opts, const double *x0 /* host [n] or NULL */, int32_t *out_u,
+             int32_t *out_v /* host [num_iterations] */, int64_t *out_added, double *out_x /* host [n] or NULL */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
