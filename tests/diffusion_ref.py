@@ -31,6 +31,51 @@ def ppr_columns(edge_index, n, alpha, sources):
     return np.linalg.solve(operator(edge_index, n, alpha), rhs).T.copy()
 
 
+# ---- without a dense matrix: the host certificate of tests/test_diffusion_gpu.py at 33,000 nodes ------------------------------------
+def sparse_operator(edge_index, n, alpha):
+    """(M as scipy CSC in float64, A + I as CSR, s~ = 1 / sqrt(deg + 1))."""
+    import scipy.sparse
+    from spectral_ref import adjacency as sparse_adjacency
+    at = (sparse_adjacency(edge_index, n) + scipy.sparse.identity(n)).tocsr()
+    s = 1.0 / np.sqrt(np.asarray(at.sum(axis=1)).ravel())
+    d = scipy.sparse.diags(s)
+    return (scipy.sparse.identity(n) - (1.0 - alpha) * (d @ at @ d)).tocsc(), at, s
+
+
+def residual_long(at, x, source, alpha):
+    """|alpha e_source - M x|_2 with M x = x - (1 - alpha) s~ (.) ((A + I) (s~ (.) x)) evaluated in np.longdouble from the degrees:
+    no rounded matrix entry takes part."""
+    from spectral_ref import csr_matvec_long
+    L = np.longdouble
+    s = L(1) / np.sqrt(np.asarray(at.sum(axis=1)).ravel().astype(L))
+    x = np.asarray(x, dtype=L)
+    e = -(x - L(1.0 - alpha) * (s * csr_matvec_long(at, s * x)))
+    e[source] += L(alpha)
+    return float(np.sqrt(np.sum(e * e)))
+
+
+def matvec_error(M, x, d_max):
+    """(d_max + 4) 2^-52 | |M| |x| |_2: the forward error of a float64 mat-vec whose longest row adds d_max + 1 products, in the
+    2-norm.  What the residual a device reports may differ by from the residual of the same column computed exactly."""
+    return (d_max + 4) * EPS * float(np.linalg.norm(abs(M) @ np.abs(x)))
+
+
+def residual_long_rounding(M, at, x):
+    """What residual_long's own arithmetic can be off by: row i of its mat-vec adds deg_i + 1 products and takes four more
+    roundings, each within the spacing of np.longdouble: | (deg_i + 4) eps_long (|M| |x|)_i |_2.  2,048 times below matvec_error
+    where np.longdouble has 64 bits of mantissa."""
+    per_row = (at.getnnz(axis=1) - 1 + 4) * float(np.finfo(np.longdouble).eps)
+    return float(np.linalg.norm(per_row * (abs(M) @ np.abs(x))))
+
+
+def lu_columns(M, sources, alpha):
+    """[len(sources), n] from scipy.sparse.linalg.splu."""
+    import scipy.sparse.linalg
+    rhs = np.zeros((M.shape[0], len(sources)))
+    rhs[np.asarray(sources, dtype=np.int64), np.arange(len(sources))] = alpha
+    return scipy.sparse.linalg.splu(M).solve(rhs).T.copy()
+
+
 def allow(n):
     """The rounding allowance of the acceptance rule (resistance_ref.allow with entries <= 1): 64 n 2^-52."""
     return 64.0 * n * EPS

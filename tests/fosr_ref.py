@@ -29,6 +29,29 @@ def power_step(a, deg, x):
     return z / nrm
 
 
+def power_step_long(a, deg, x):
+    """power_step with every operation in np.longdouble; the result in np.longdouble.  What the float64 restatement is compared
+    with to learn its own rounding."""
+    L = np.longdouble
+    d = deg.astype(L)
+    r = np.sqrt(d)
+    s = np.zeros_like(d)
+    s[deg > 0] = L(1) / np.sqrt(d[deg > 0])
+    x = np.asarray(x, dtype=L)
+    x = x - (np.sum(x * r) / d.sum()) * r
+    z = x + s * spectral_ref.csr_matvec_long(a, s * x)
+    return z / np.sqrt(np.sum(z * z))
+
+
+def own_rounding(a, deg, x0, steps):
+    """The largest elementwise difference between `steps` power steps in float64 and the same in np.longdouble: the reference
+    against itself."""
+    x, xl = np.asarray(x0, dtype=np.float64), np.asarray(x0, dtype=np.longdouble)
+    for _ in range(steps):
+        x, xl = power_step(a, deg, x), power_step_long(a, deg, xl)
+    return float(np.abs(x - xl).max())
+
+
 # ---- the pick ------------------------------------------------------------------------------------------------------------------
 def y_of(x, deg):
     return np.asarray(x, dtype=np.float64) / np.sqrt(deg + 1.0)
@@ -51,6 +74,35 @@ def row_products(y, rows):
                 if prod == prod:
                     p[u], partner[u] = prod, v
                 break
+    return p, partner
+
+
+def row_products_fast(y, a):
+    """row_products from the CSR adjacency `a` with array operations.  Counted from its end of the order (the top for y_u < 0), a
+    row of degree d has itself and its neighbours on d + 1 distinct ranks, so the first rank that none of them has is the number of
+    them that sit on the ranks 0, 1, ... without a gap: sorted by (row, rank), the entries whose rank equals their place in the row."""
+    n = y.shape[0]
+    order = order_of(y)
+    rank = np.empty(n, dtype=np.int64)
+    rank[order] = np.arange(n)
+    deg = np.diff(a.indptr).astype(np.int64)
+    top = y < 0
+    row = np.concatenate([np.repeat(np.arange(n), deg), np.arange(n)])          # every neighbour, then the row itself
+    q = rank[np.concatenate([a.indices.astype(np.int64), np.arange(n)])]
+    q = np.where(top[row], n - 1 - q, q)
+    near = q < deg[row] + 2
+    key = np.sort(row[near] * np.int64(n + 1) + q[near])
+    row, q = key // (n + 1), key % (n + 1)
+    start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(row, minlength=n), out=start[1:])
+    free = np.bincount(row[q == np.arange(key.shape[0]) - start[row]], minlength=n)   # the first free rank of every row
+    has = deg < n - 1
+    at = np.where(top, n - 1 - free, free)
+    partner = np.where(has, order[np.where(has, at, 0)], -1)
+    with np.errstate(invalid='ignore'):
+        p = np.where(has, y * y[np.maximum(partner, 0)], np.inf)
+    nan = p != p
+    p[nan], partner[nan] = np.inf, -1
     return p, partner
 
 
@@ -96,6 +148,36 @@ def brute_minimum(y, rows):
 
 
 # ---- the loop ------------------------------------------------------------------------------------------------------------------
+def loop_fast(edge_index, n, num_iterations, initial_power_iters, x0, replay=None):
+    """loop with row_products_fast and a CSR adjacency rebuilt from the edge list at every iteration: no neighbour sets, no
+    Python loop over the nodes.  Also returns the rule's own pick of every iteration: (edges, x, margins, picks)."""
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    a = spectral_ref.adjacency(ei, n)
+    deg = np.diff(a.indptr).astype(np.int64)
+    x = np.asarray(x0, dtype=np.float64).copy()
+    for _ in range(initial_power_iters):
+        x = power_step(a, deg, x)
+        assert x is not None
+    added, margins, picks = [], [], []
+    for it in range(num_iterations):
+        y = y_of(x, deg)
+        p, partner = row_products_fast(y, a)
+        got = pick_of(p, partner)
+        if got is None:
+            break
+        margins.append(margin_of(y, p, partner))
+        picks.append(got)
+        u, v = (int(replay[0][it]), int(replay[1][it])) if replay is not None else got[:2]
+        assert u != v and a[u, v] == 0
+        added.append((u, v))
+        ei = np.concatenate([ei, np.array([[u, v], [v, u]], dtype=np.int64)], axis=1)
+        a = spectral_ref.adjacency(ei, n)
+        deg = np.diff(a.indptr).astype(np.int64)
+        x = power_step(a, deg, x)
+        assert x is not None
+    return np.array(added, dtype=np.int64).reshape(-1, 2).T, x, margins, picks
+
+
 def loop(edge_index, n, num_iterations, initial_power_iters, x0, replay=None):
     """(added edges int64 [2, added], final x, the runner-up margin of every pick).  replay: int [2, k], the picks to take in
     place of the rule's own (the margins are then those of the rule on the replayed state)."""
@@ -213,6 +295,7 @@ LOOP_FIXTURES = [
     ('irregular2500', dict(n=2500, seed=3, isolated=1), 60, 13),
 ]
 LOOP_INITIAL = 5
+LOOP_LARGE_ITERS, LOOP_LARGE_SEED = 10, 14      # the loop on scale_ref.whole_small(): tests/test_fosr_cpu.py asserts its margins
 _LOOPS = {}
 
 

@@ -19,6 +19,17 @@ def adjacency(edge_index, n):
     return a
 
 
+def csr_matvec_long(a, x):
+    """a @ x in np.longdouble for a scipy CSR matrix: the products of a row added from left to right.  (scipy's own product stops
+    at float64.)"""
+    x = np.asarray(x, dtype=np.longdouble)
+    out = np.zeros(a.shape[0], dtype=np.longdouble)
+    if a.nnz:
+        full = np.flatnonzero(np.diff(a.indptr) > 0)     # reduceat returns an element, not 0, for an empty row
+        out[full] = np.add.reduceat(a.data.astype(np.longdouble) * x[a.indices], a.indptr[full])
+    return out
+
+
 def normalised_adjacency(edge_index, n):
     """(Â as scipy CSR, degrees)."""
     a = adjacency(edge_index, n)

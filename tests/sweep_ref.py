@@ -8,11 +8,16 @@ import numpy as np
 Sweep = namedtuple('Sweep', ['value', 'size', 'counts', 'order', 'profile'])
 
 
-def undirected_edges(edge_index):
-    """(a, b) with a < b, each undirected edge once."""
+def undirected_edges(edge_index, num_nodes=None):
+    """(a, b) with a < b, each undirected edge once, by (a, b).  The rows of np.unique(axis=0) are the definition; with num_nodes
+    given (and a * num_nodes + b within int64) the same arrays come from a sort of that key: tests/test_sweep_cpu.py has the
+    equality."""
     ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
     lo, hi = np.minimum(ei[0], ei[1]), np.maximum(ei[0], ei[1])
     keep = lo < hi
+    if num_nodes is not None and 0 < num_nodes < 2 ** 31 and keep.any() and hi.max() < num_nodes:
+        key = np.unique(lo[keep] * np.int64(num_nodes) + hi[keep])
+        return key // num_nodes, key % num_nodes
     pairs = np.unique(np.stack([lo[keep], hi[keep]], axis=1), axis=0) if keep.any() else np.zeros((0, 2), dtype=np.int64)
     return pairs[:, 0], pairs[:, 1]
 
@@ -46,10 +51,12 @@ def _finish(order, n_in, n_lo, n_hi, num_edges, definition):
     return Sweep(float(profile[best]), best + 1, counts, order.astype(np.int32), profile)
 
 
-def sweep(edge_index, n, score, definition='conductance'):
+def prefix_counts(edge_index, n, score):
+    """(order, n_in, n_lo, n_hi of every prefix S_1 .. S_{n-1}, the number of edges): everything of a sweep that does not depend
+    on the definition, so that a test of both definitions computes it once."""
     if n < 2:
         raise ValueError('a sweep needs two nodes')
-    a, b = undirected_edges(edge_index)
+    a, b = undirected_edges(edge_index, n)
     order = order_of(score)
     rank = np.empty(n, dtype=np.int64)
     rank[order] = np.arange(n)
@@ -62,7 +69,15 @@ def sweep(edge_index, n, score, definition='conductance'):
     np.add.at(d[2], p[~up] + 1, -1)
     np.add.at(d[0], np.maximum(p, q) + 1, 1)   # in from k = max + 1
     c = np.cumsum(d, axis=1)[:, 1:n]
-    return _finish(order, c[0], c[1], c[2], a.shape[0], definition)
+    return order, c[0], c[1], c[2], a.shape[0]
+
+
+def from_counts(counts, definition):
+    return _finish(*counts, definition)
+
+
+def sweep(edge_index, n, score, definition='conductance'):
+    return from_counts(prefix_counts(edge_index, n, score), definition)
 
 
 def brute(edge_index, n, score, definition='conductance'):

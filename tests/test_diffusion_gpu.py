@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import diffusion_ref as ref
+import scale_ref
 from conftest import GOLDEN, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +141,127 @@ def test_ppr_on_the_plan_family_and_batch_independence(dcr, name):
         for i, s in enumerate(order):
             if s in want:
                 assert (y[i].tobytes(), iy['residual'][i].hex(), int(iy['steps'][i])) == want[s], (name, P, i, s)
+
+
+# ---- 3b. past one grid-stride trip of the element-wise kernels; the groups of a launch ------------------------------------------------
+LARGE_ALPHA = 0.15
+_LARGE = {}
+
+
+def large_sources():
+    """The 17 sources at 33,133 nodes: the hub, a medium row, a lattice corner, an isolated node, the last node, then others."""
+    ei, n, names = scale_ref.diffusion_large()
+    named = [names['hub0'], names['hub3'], names['corner'], names['isolated'], names['last']]
+    others = [v for v in np.random.default_rng(5).permutation(n).tolist() if v not in named]
+    return named + others[:scale_ref.DIFFUSION_P - len(named)]
+
+
+def large_solve(dcr):
+    """(graph handle, sources, the device's columns, info), solved once for the value and the selection test."""
+    if 'solve' not in _LARGE:
+        ei, n, _ = scale_ref.diffusion_large()
+        G = dcr(ei, n)
+        src = large_sources()
+        _LARGE['solve'] = (G, src) + solve(G, src, LARGE_ALPHA)
+    return _LARGE['solve']
+
+
+def test_ppr_past_one_trip_against_the_host_certificate(dcr):
+    """n = 33,133: k_dif_start / update / direction / scale_x take a second grid-stride trip, two launches run at one group.  No
+    dense matrix exists here, so the reference is a certificate, derived and not measured.  With rho the residual of the device's
+    column computed on the host in np.longdouble:
+      |rho - reported residual| <= (d_max + 4) 2^-52 | |M| |x| |_2     the forward error of the float64 mat-vec the device performs
+      |x - x_ref|_inf <= (rho + rho_ref) / alpha                      x_ref from a sparse LU, rho_ref its own host residual:
+    x - S_j = M^-1 (M x - alpha e_j) for both, and lambda_min(M) >= alpha (the argument at the head of this file).  The second
+    line is a theorem about the exact residuals, and at an isolated source it holds with near equality (M is the 1 x 1 matrix
+    1 - (1 - alpha), the device and the LU land on the two floats either side of alpha / M_jj): there the 2^-64 roundings of
+    the host's own np.longdouble residual decide (measured: 4.441e-16 against 4.438e-16).  So rho and rho_ref enter with what
+    their own arithmetic can be off by added (ref.residual_long_rounding), which is nothing beside a residual of 1e-11."""
+    ei, n, _ = scale_ref.diffusion_large()
+    G, src, x, info = large_solve(dcr)
+    M, at, _ = ref.sparse_operator(ei, n, LARGE_ALPHA)
+    d_max = int(at.getnnz(axis=1).max()) - 1
+    assert d_max == G.degree(src[0]) == 2100
+    want = ref.lu_columns(M, src, LARGE_ALPHA)
+    for i, j in enumerate(src):
+        rho, rho_ref = ref.residual_long(at, x[i], j, LARGE_ALPHA), ref.residual_long(at, want[i], j, LARGE_ALPHA)
+        slack = ref.matvec_error(M, x[i], d_max)
+        err = float(np.abs(x[i] - want[i]).max())
+        print(f'  source {j}: reported {info["residual"][i]:.3e}, host {rho:.3e} (may differ by {slack:.3e}), LU {rho_ref:.3e}, '
+              f'error {err:.3e} <= {(rho + rho_ref) / LARGE_ALPHA:.3e}, steps {info["steps"][i]}')
+        assert abs(rho - info['residual'][i]) <= slack, (j, rho, info['residual'][i], slack)
+        own = ref.residual_long_rounding(M, at, x[i]) + ref.residual_long_rounding(M, at, want[i])
+        assert err <= (rho + rho_ref + own) / LARGE_ALPHA, (j, err, rho, rho_ref, own)
+        assert rho <= TOL * LARGE_ALPHA + slack                      # converged by the host's residual too
+    for i in (3, 4):   # the isolated sources: S_jj = 1, nothing else
+        assert abs(x[i, src[i]] - 1.0) <= 4 * ref.EPS and np.count_nonzero(x[i]) == 1
+
+
+def test_selection_past_one_trip_is_the_lexsort_of_the_device_columns(dcr):
+    ei, n, _ = scale_ref.diffusion_large()
+    G, src, x, _ = large_solve(dcr)
+    P = len(src)
+    order = np.lexsort((np.broadcast_to(np.arange(n), (P, n)), -x), axis=-1)
+    for k in (1, 64, n):
+        got_ei, w, info = sparse(G, LARGE_ALPHA, k=k, sources=src)
+        assert np.array_equal(np.diff(info['ptr']), np.full(P, k)), k
+        rows = got_ei[0].reshape(P, k)
+        assert np.array_equal(got_ei[1].reshape(P, k), np.broadcast_to(np.asarray(src)[:, None], (P, k)))
+        assert np.array_equal(rows, np.sort(order[:, :k], axis=1)), (k, 'kept sets')
+        value = np.take_along_axis(x, rows, axis=1)
+        assert info['value'].tobytes() == value.tobytes(), (k, 'values')
+        total = np.cumsum(value, axis=1)[:, -1:]           # added in id order, one after the other
+        assert np.all(total > 0) and w.tobytes() == (value / total).tobytes(), (k, 'weights')
+    eps = load_golden('diffusion_reference.json')['cases'][0]['eps']
+    got_ei, w, info = sparse(G, LARGE_ALPHA, eps=eps, sources=src)
+    keep = x >= eps
+    assert keep.sum() > P and np.array_equal(np.diff(info['ptr']), keep.sum(axis=1))
+    jj, ii = np.nonzero(keep)                              # by column, then by node id
+    assert np.array_equal(got_ei[0], ii) and np.array_equal(got_ei[1], np.asarray(src)[jj])
+    assert info['value'].tobytes() == x[jj, ii].tobytes()
+    assert w.tobytes() == np.concatenate([ref.normalise(x[j, keep[j]]) for j in range(P)]).tobytes()
+
+
+def same_as_solo(G, order, named, y, iy, alpha, label):
+    """The named positions of a call: the column, the residual and the step count are those of the source solved alone."""
+    for pos in named:
+        s = order[pos]
+        x1, i1 = solve(G, [s], alpha)
+        got = (y[pos].tobytes(), iy['residual'][pos].hex(), int(iy['steps'][pos]))
+        assert got == (x1[0].tobytes(), i1['residual'][0].hex(), int(i1['steps'][0])), (label, pos, s)
+
+
+def test_groups_limited_by_n_leave_the_columns_alone(dcr):
+    """About 10,000 nodes: 65,536 // n = 6 groups, not 8 and not the 7 batches of P = 101.  One launch of six groups, then five
+    columns alone."""
+    ei, n, names = scale_ref.diffusion_groups()
+    G = dcr(ei, n)
+    P, B = scale_ref.GROUPS_P, 16
+    special = [names['hub0'], names['hub1'], names['hub2'], names['corner'], names['isolated'], names['last'], n // 2, 4321]
+    named = [0, B + 3, 2 * B + 7, 3 * B + 15, 4 * B, 5 * B + 9, 6 * B, P - 1]   # first, one per group 1 .. 5, the second launch's first, last
+    fill = [v for v in np.random.default_rng(7).permutation(n).tolist() if v not in special]
+    order = fill[:P]
+    for pos, s in zip(named, special):
+        order[pos] = s
+    assert len(set(order)) == P
+    y, iy = solve(G, order, LARGE_ALPHA)
+    same_as_solo(G, order, named, y, iy, LARGE_ALPHA, 'six groups')
+
+
+def test_groups_2_to_7_leave_the_columns_alone(dcr):
+    """long3_mid9_short63 with 8 x 16 sources: all eight groups of a launch; the plan's picks sit in groups 2, 5 and 7."""
+    ei, n = {g[0]: g[1:] for g in ref.plan_family()}['long3_mid9_short63']
+    G = dcr(ei, n)
+    picked, others = plan_sources(ei, n)
+    assert len(picked) == 6
+    P, B = scale_ref.SMALL_GROUPS_P, 16
+    named = [2 * B, 2 * B + 15, 5 * B + 1, 5 * B + 8, 7 * B + 6, 7 * B + 15]
+    order = others[:P]
+    for pos, s in zip(named, picked):
+        order[pos] = s
+    assert len(set(order)) == P
+    y, iy = solve(G, order, LARGE_ALPHA)
+    same_as_solo(G, order, named, y, iy, LARGE_ALPHA, 'eight groups')
 
 
 # ---- 4. the selection, exactly -----------------------------------------------------------------------------------------------------

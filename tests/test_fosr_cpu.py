@@ -42,6 +42,81 @@ def test_rule_attains_the_brute_force_minimum():
     assert cases >= 300
 
 
+def test_fast_row_products_are_the_rule():
+    """fosr_ref.row_products_fast (array operations on the CSR adjacency, what the GPU tests of 70,001 and 262,182 nodes compare
+    with) returns what fosr_ref.row_products returns, on every graph and vector kind of this file: products by bits, partners by
+    value, the rows without a candidate included."""
+    rng = np.random.Generator(np.random.PCG64(9))
+    graphs = small_graphs() + [spectral_ref.complete(n) for n in (2, 3, 6, 11)] + [spectral_ref.path(4)]
+    graphs += [fosr_ref.irregular_graph(300, seed=5, isolated=1), spectral_ref.row_classes_graph()]
+    graphs += [fosr_ref.loop_fixture(name)[:2] for name, *_ in fosr_ref.LOOP_FIXTURES]
+    cases = 0
+    for ei, n in graphs:
+        a, deg, rows = fosr_ref.degrees_and_rows(ei, n)
+        vectors = dict(fosr_ref.vector_kinds(n, rng))
+        vectors['with_infinities'] = np.where(rng.random(n) < 0.3, np.inf, vectors['both_zeros'])    # 0 x inf: not a candidate
+        for name, x in vectors.items():
+            if n > 1000 and name not in ('normal', 'small_integers', 'both_zeros', 'negative'):
+                continue
+            y = fosr_ref.y_of(x, deg)
+            with np.errstate(invalid='ignore'):
+                p, partner = fosr_ref.row_products(y, rows)
+            fp, fpartner = fosr_ref.row_products_fast(y, a)
+            assert p.tobytes() == fp.tobytes() and np.array_equal(partner, fpartner), (n, name)
+            assert fosr_ref.pick_of(p, partner) == fosr_ref.pick_of(fp, fpartner)
+            cases += 1
+    assert cases >= 400
+
+
+def test_fast_loop_is_the_loop():
+    name = 'irregular200'
+    ei, n, x0, iters, (edges, x, margins) = fosr_ref.loop_fixture(name)
+    fast = fosr_ref.loop_fast(ei, n, iters, fosr_ref.LOOP_INITIAL, x0)
+    assert np.array_equal(fast[0], edges) and fast[1].tobytes() == x.tobytes() and fast[2] == margins
+    assert [list(p[:2]) for p in fast[3]] == edges.T.tolist()
+    again = fosr_ref.loop_fast(ei, n, iters, fosr_ref.LOOP_INITIAL, x0, replay=edges)
+    assert np.array_equal(again[0], edges) and again[1].tobytes() == x.tobytes()
+
+
+def test_large_loop_has_a_margin_and_the_reference_knows_its_rounding():
+    """The loop of tests/test_fosr_gpu.py at 70,001 nodes: in the restatement's own run every one of the ten runner-up margins is
+    above the bound the GPU test uses (16 times the float64 step's difference from the np.longdouble step), far above; the GPU
+    test allows one iteration under it.  And that bound stays under the ceiling of 1e-12 at 262,182 nodes too."""
+    import scale_ref
+    ei, n = scale_ref.whole_small()
+    a = spectral_ref.adjacency(ei, n)
+    deg = np.diff(a.indptr).astype(np.int64)
+    x0 = np.random.Generator(np.random.PCG64(fosr_ref.LOOP_LARGE_SEED)).standard_normal(n)
+    own = fosr_ref.own_rounding(a, deg, x0, 1)
+    edges, x, margins, picks = fosr_ref.loop_fast(ei, n, fosr_ref.LOOP_LARGE_ITERS, fosr_ref.LOOP_INITIAL, x0)
+    print(f'n = {n}: the reference against itself {own:.3e}; margins {min(margins):.3e} .. {max(margins):.3e}')
+    assert 0 < 16 * own < 1e-12 and len(margins) == fosr_ref.LOOP_LARGE_ITERS
+    assert sum(m <= 16 * own for m in margins) == 0 and min(margins) >= 1e-6
+    assert abs(np.linalg.norm(x) - 1.0) < 1e-12
+    ei, n = scale_ref.fosr_large()
+    a = spectral_ref.adjacency(ei, n)
+    deg = np.diff(a.indptr).astype(np.int64)
+    x0 = np.random.Generator(np.random.PCG64(26)).standard_normal(n)
+    for steps in (1, 5):
+        own = fosr_ref.own_rounding(a, deg, x0, steps)
+        print(f'n = {n}, {steps} steps: the reference against itself {own:.3e}')
+        assert 0 < 16 * own < 1e-12
+
+
+def test_long_double_step_is_the_step():
+    """power_step_long is power_step in another precision: on a small graph they agree to float64 rounding, and np.longdouble is
+    wider than float64 here (otherwise own_rounding would measure nothing)."""
+    assert np.finfo(np.longdouble).eps < np.finfo(np.float64).eps
+    ei, n = fosr_ref.irregular_graph(300, seed=5, isolated=1)
+    a, deg, _ = fosr_ref.degrees_and_rows(ei, n)
+    x0 = np.random.Generator(np.random.PCG64(1)).standard_normal(n)
+    xl = fosr_ref.power_step_long(a, deg, x0)
+    assert xl.dtype == np.longdouble and np.abs(fosr_ref.power_step(a, deg, x0) - xl).max() < 1e-15
+    assert 0 < fosr_ref.own_rounding(a, deg, x0, 1) < 1e-15
+    dense = a.toarray().astype(np.longdouble) @ x0.astype(np.longdouble)
+    assert np.abs(spectral_ref.csr_matvec_long(a, x0) - dense).max() < 1e-17
+
+
 @pytest.mark.parametrize('n', [2, 3, 6, 11])
 def test_complete_graphs_have_no_pick(n):
     ei, _ = spectral_ref.complete(n)

@@ -1,0 +1,171 @@
+"""Where the sweep, diffusion and FoSR kernels change their control flow, on the CPU: the constants are read out of the sources
+(tests/scale_ref.py), the launch arithmetic of sweep_buffers, diffusion_batches and row_grid is restated there, and every size
+that tests/test_sweep_gpu.py, tests/test_diffusion_gpu.py and tests/test_fosr_gpu.py run at is asserted to sit just past the
+boundary it is there for, with the size below it on the other side.  A failure names the GPU size that a changed constant has
+left stale."""
+import numpy as np
+import pytest
+
+import scale_ref as sc
+import spectral_ref
+
+
+@pytest.fixture(scope='module')
+def c():
+    return sc.constants()
+
+
+def test_constants_are_those_the_sizes_were_chosen_for(c):
+    """Not a demand on the kernels: a changed constant is allowed, and the tests below then say which size moved.  This one only
+    prints what was read and pins what the restatement itself assumes."""
+    print('  ' + ', '.join(f'{k} = {v}' for k, v in c.items()))
+    assert sc.CLOSING_STRIDE == 256
+    assert c['SP_SHORT_DEG'] == spectral_ref.SHORT_DEG and c['SP_LONG_DEG'] == spectral_ref.LONG_DEG
+    assert c['DIF_B'] % 2 == 0 and c['SW_SCAN_BLOCK'] == 8 * 256   # eight elements a thread
+
+
+# ---- the sweep -----------------------------------------------------------------------------------------------------------------------
+def test_sweep_value_closing_loop_and_grid_caps(c):
+    stale = 'stale GPU size: scale_ref.WHOLE_SMALL (the closing loop of k_sweep_value past 256 partials)'
+    grid, trips = sc.value_grid(sc.WHOLE_SMALL, c)
+    assert sc.CLOSING_STRIDE < grid < c['SW_VALUE_BLOCKS'] and trips == 1, stale
+    at = sc.CLOSING_STRIDE * 256 + 1                        # the largest n with 256 partials
+    assert sc.value_grid(at, c)[0] == sc.CLOSING_STRIDE and sc.value_grid(at + 1, c)[0] == sc.CLOSING_STRIDE + 1, stale
+    assert sc.sweep_buffers(sc.WHOLE_SMALL, c)[3] <= sc.CLOSING_STRIDE, stale   # and nothing else yet
+    stale = 'stale GPU size: scale_ref.WHOLE_LARGE (second grid-stride trip of k_sweep_keys and k_sweep_value)'
+    assert sc.value_grid(sc.WHOLE_LARGE, c) == (c['SW_VALUE_BLOCKS'], 2) and sc.keys_trips(sc.WHOLE_LARGE, c) == 3, stale
+    assert sc.WHOLE_LARGE % (c['SW_KEYS_BLOCKS'] * 256) == 1, stale             # the third trip of k_sweep_keys holds the last key alone
+    at = c['SW_KEYS_BLOCKS'] * 256
+    assert sc.keys_trips(at, c) == 1 and sc.keys_trips(at + 1, c) == 2, stale
+    assert sc.value_grid(at + 1, c)[1] == 1 and sc.value_grid(at + 2, c)[1] == 2, stale
+
+
+def test_scan_closing_loop_on_the_difference_arrays(c):
+    stale = 'stale GPU size: scale_ref.WHOLE_LARGE and SORT_SIZES[0] (carry of k_scan_reduce, difference arrays)'
+    n = sc.WHOLE_LARGE
+    assert n == sc.SORT_SIZES[0]
+    assert sc.sweep_buffers(n, c)[3] == sc.CLOSING_STRIDE + 1 and sc.sweep_buffers(n - 1, c)[3] == sc.CLOSING_STRIDE, stale
+    assert sc.sweep_buffers(n, c)[:3] == (c['SW_TILE'], 513, 65), stale        # the sort table is still within one trip
+
+
+def test_scan_carry_is_read_by_a_prefix(c):
+    """nb_diff = 257 is not enough: at 524,289 nodes the 257th block is element n - 1, the count of all nodes, and k_sweep_value
+    stops at n - 2.  WHOLE_CARRY puts 1,499 valued prefixes into that block, isolated nodes and the chord-free tail among them."""
+    stale = 'stale GPU size: scale_ref.WHOLE_CARRY (carry of k_scan_reduce read by k_sweep_value)'
+    first = sc.CLOSING_STRIDE * c['SW_SCAN_BLOCK']          # the first element of the 257th block
+    assert sc.WHOLE_LARGE - 2 < first, stale                # the issue's size: no prefix in it
+    n = sc.WHOLE_CARRY
+    assert sc.sweep_buffers(n, c)[3] == sc.CLOSING_STRIDE + 1 and (n - 2) - first + 1 == 1_499, stale
+    assert sc.value_grid(n, c) == (c['SW_VALUE_BLOCKS'], 3), stale
+
+
+def test_best_prefix_of_the_id_score_lies_in_the_last_workgroups(c):
+    """With the node id as score the best prefix ends where the chord-free tail begins (one cut edge).  Its arg-min partial has an
+    index above 256, so the closing loop of k_sweep_value must carry it on a later trip; at the larger sizes the prefix itself
+    is taken on the second or third grid-stride trip."""
+    import sweep_ref
+    for build, n in ((sc.whole_small, sc.WHOLE_SMALL), (sc.whole_large, sc.WHOLE_LARGE), (sc.whole_carry, sc.WHOLE_CARRY)):
+        ei, _ = build()
+        isolated = int((sc.degrees(ei, n) == 0).sum())
+        want = sweep_ref.sweep(ei, n, np.arange(n, dtype=np.float64), 'conductance')
+        assert want.size == n - isolated - sc.TAIL and want.counts[1] + want.counts[2] == 1, (n, want.size)
+        grid, trips = sc.value_grid(n, c)
+        index = want.size - 1
+        assert index // (256 * grid) == trips - 1, f'stale GPU size: {n} (the best prefix on the last grid-stride trip)'
+        if n != sc.WHOLE_CARRY:   # (there the third trip starts over at workgroup 0, which takes it)
+            assert (index // 256) % grid >= sc.CLOSING_STRIDE, f'stale GPU size: {n} (closing loop of k_sweep_value)'
+
+
+def test_scan_closing_loop_on_the_sort_table(c):
+    stale = 'stale GPU size: scale_ref.SORT_SIZES[1] (carry of k_scan_reduce, sort table)'
+    n = sc.SORT_SIZES[1]
+    tile, tiles, nb_table, nb_diff = sc.sweep_buffers(n, c)
+    assert (tile, tiles, nb_table) == (c['SW_TILE'], 2050, sc.CLOSING_STRIDE + 1), stale
+    at = sc.CLOSING_STRIDE * c['SW_SCAN_BLOCK'] // 256 * c['SW_TILE']           # 2,048 tiles: the last n with 256 blocks
+    assert sc.sweep_buffers(at, c)[2] == sc.CLOSING_STRIDE and sc.sweep_buffers(at + 1, c)[2] == sc.CLOSING_STRIDE + 1, stale
+    assert at < n <= at + 2 * c['SW_TILE'] and tiles % 4 != 0 and n % tile == 1, stale   # a last tile of one key, a last workgroup of two waves
+
+
+def test_sort_tiles_beyond_the_tile_limit(c):
+    stale = 'stale GPU size: scale_ref.SORT_SIZES[2] (tile above SW_TILE, tiles capped)'
+    n = sc.SORT_SIZES[2]
+    at = c['SW_MAX_TILES'] * c['SW_TILE']
+    assert n == at + 1, stale
+    assert sc.sweep_buffers(at, c)[:2] == (c['SW_TILE'], c['SW_MAX_TILES']), stale
+    tile, tiles, nb_table, nb_diff = sc.sweep_buffers(n, c)
+    assert tile == c['SW_TILE'] + 64 and tile % 64 == 0 and tiles < c['SW_MAX_TILES'] and tiles * tile >= n > (tiles - 1) * tile, stale
+    assert nb_diff > 8 * sc.CLOSING_STRIDE and nb_table > sc.CLOSING_STRIDE, stale
+
+
+# ---- diffusion -----------------------------------------------------------------------------------------------------------------------
+def test_diffusion_elementwise_second_trip(c):
+    stale = 'stale GPU size: scale_ref.DIFFUSION_SIDE (second grid-stride trip of k_dif_start / update / direction / scale_x)'
+    ei, n, names = sc.diffusion_large()
+    at = c['DIF_UPDATE_BLOCKS'] * 256 // (c['DIF_B'] // 2)   # 32,768: the largest n of one trip
+    assert sc.diffusion_batches(at, sc.DIFFUSION_P, c)[1:] == (c['DIF_UPDATE_BLOCKS'], 1), stale
+    assert sc.diffusion_batches(at + 1, sc.DIFFUSION_P, c)[1:] == (c['DIF_UPDATE_BLOCKS'], 2), stale
+    groups, nb_el, trips = sc.diffusion_batches(n, sc.DIFFUSION_P, c)
+    assert at < n < at + at // 16 and (groups, nb_el, trips) == (1, c['DIF_UPDATE_BLOCKS'], 2), stale
+    assert -(-sc.DIFFUSION_P // (groups * c['DIF_B'])) == 2, stale              # two launches
+    # every class of the mat-vec, and the sources the test names
+    deg = sc.degrees(ei, n)
+    nl, nm, ns = sc.class_counts(deg, c)
+    assert nl == 1 and nm == 4 and deg[names['hub0']] == 2100 > c['SP_LONG_DEG'] and deg[names['hub1']] == c['SP_SHORT_DEG'] + 1, stale
+    assert deg[names['isolated']] == 0 and deg[names['last']] == 0 and 2 <= deg[names['corner']] <= c['SP_SHORT_DEG'] and (deg == 0).sum() == 4
+    mv_grid = nl + sc.blocks_of(nm, c['MID_ROWS']) + sc.blocks_of(ns, c['DIF_SHORT_ROWS'])
+    assert mv_grid > 2 * (256 // (c['DIF_B'] // 2)), stale                      # dif_close_partials: more than one trip of 32 partials
+
+
+def test_diffusion_groups_limited_by_n(c):
+    stale = 'stale GPU size: scale_ref.GROUPS_SIDE / GROUPS_P (group count limited by n)'
+    ei, n, names = sc.diffusion_groups()
+    groups = sc.diffusion_batches(n, sc.GROUPS_P, c)[0]
+    assert groups == c['DIF_GROUP_NODES'] // n == 6 < min(c['DIF_MAX_GROUPS'], sc.blocks_of(sc.GROUPS_P, c['DIF_B'])), stale
+    assert sc.GROUPS_P == groups * c['DIF_B'] + 5, stale                         # a full launch of six groups, then five columns
+    assert c['DIF_GROUP_NODES'] // c['DIF_MAX_GROUPS'] < n, stale
+    deg = sc.degrees(ei, n)
+    assert sc.class_counts(deg, c)[:2] == (1, 2) and deg[names['last']] == 0
+
+
+def test_diffusion_all_eight_groups_at_small_n(c):
+    stale = 'stale GPU size: scale_ref.SMALL_GROUPS_P (groups 2 .. 7 of one launch)'
+    n = next(m for name, e, m in spectral_ref.plan_family() if name == 'long3_mid9_short63')
+    assert sc.diffusion_batches(n, sc.SMALL_GROUPS_P, c)[0] == c['DIF_MAX_GROUPS'] == 8, stale
+    assert sc.SMALL_GROUPS_P == c['DIF_MAX_GROUPS'] * c['DIF_B'] and n <= c['DIF_GROUP_NODES'] // c['DIF_MAX_GROUPS'], stale
+    assert sc.diffusion_batches(n, 17, c)[0] == 2      # what the batch-independence test of the plan family reaches
+
+
+# ---- FoSR ----------------------------------------------------------------------------------------------------------------------------
+def test_fosr_closing_loops_and_dot_cap(c):
+    stale = 'stale GPU size: scale_ref.FOSR_SMALL (closing loop of k_fosr_pick, close_partials of k_fosr_matvec past 256 workgroups)'
+    ei, n = sc.whole_small()
+    deg = sc.degrees(ei, n)
+    counts = sc.class_counts(deg, c)
+    grid = sc.row_grid(counts, c)
+    print(f'  n = {n}: classes {counts}, row grid {grid}')
+    assert counts[0] == 1 and counts[1] >= 4 and grid > 8 * sc.CLOSING_STRIDE, stale
+    assert sc.row_grid((0, 0, sc.CLOSING_STRIDE * c['SHORT_ROWS']), c) == sc.CLOSING_STRIDE, stale   # 8,192 short rows: one trip
+    assert sc.row_grid((0, 0, sc.CLOSING_STRIDE * c['SHORT_ROWS'] + 1), c) == sc.CLOSING_STRIDE + 1, stale
+    assert sc.dot_trips(n, c) == 1 and sc.blocks_of(n) > sc.CLOSING_STRIDE, stale
+    assert (deg[-3:] == 0).all() and deg[-4] > 0 and counts[2] % c['SHORT_ROWS'] >= 2, stale     # the last two rows share the last workgroup
+    stale = 'stale GPU size: scale_ref.FOSR_LARGE (second grid-stride trip of k_fosr_dot)'
+    ei, n = sc.fosr_large()
+    at = c['FSR_DOT_BLOCKS'] * 256
+    assert sc.dot_trips(at, c) == 1 and sc.dot_trips(at + 1, c) == 2, stale
+    assert at < n <= at + 64 and sc.dot_trips(n, c) == 2, stale
+    deg = sc.degrees(ei, n)
+    counts = sc.class_counts(deg, c)
+    assert counts[:2] == (0, 0) and (deg[-37:] == 0).all() and deg[-38] > 0 and counts[2] % c['SHORT_ROWS'] >= 2, stale
+
+
+def test_whole_call_graphs_are_what_the_gpu_tests_rely_on(c):
+    ei, n = sc.whole_small()
+    deg = sc.degrees(ei, n)
+    assert n == sc.WHOLE_SMALL and ei.shape[1] % 2 == 0 and (ei[0] != ei[1]).all()
+    assert deg[40_000] > c['SP_LONG_DEG'] and (deg > c['SP_LONG_DEG']).sum() == 1
+    assert ((deg > c['SP_SHORT_DEG']) & (deg <= c['SP_LONG_DEG'])).sum() >= 4
+    ei, n = sc.whole_large()
+    deg = sc.degrees(ei, n)
+    assert n == sc.WHOLE_LARGE and (deg[-37:] == 0).all() and (deg[:-37] > 0).all() and 9.5 < deg.mean() < 10.0
+    assert np.array_equal(ei[0] * n + ei[1], np.unique(ei[0] * n + ei[1]))      # sorted, no repeats: ascending rows
+    assert ei.shape[1] < 2 ** 31

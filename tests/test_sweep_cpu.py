@@ -35,6 +35,27 @@ def test_difference_arrays_equal_brute_force(definition):
             assert a.profile.shape == (n - 1,) and a.counts.sum() == sweep_ref.undirected_edges(ei)[0].shape[0]
 
 
+def test_keyed_edges_are_the_unique_rows():
+    """sweep_ref.undirected_edges with the node count takes a sort of a * n + b in place of np.unique(axis=0) (which costs seconds
+    on half a million nodes): the same arrays on every graph of this file, on an edge index with both directions, loops and
+    repeats in any order, and the old code where the key cannot be used."""
+    rng = np.random.Generator(np.random.PCG64(17))
+    graphs = small_graphs() + [case[1] for case in sweep_ref.table_graphs()]
+    assert len(graphs) >= 15
+    for ei, n in graphs:
+        messy = np.concatenate([ei[:, ::-1], ei[::-1], np.tile(np.arange(n), (2, 1)), ei[:, :3]], axis=1)[:, rng.permutation(2 * ei.shape[1] + n + min(3, ei.shape[1]))]
+        for edges in (ei, messy):
+            want = sweep_ref.undirected_edges(edges)
+            got = sweep_ref.undirected_edges(edges, n)
+            for g, w in zip(got, want):
+                assert g.dtype == w.dtype == np.int64 and np.array_equal(g, w)
+        assert np.array_equal(want[0], sweep_ref.undirected_edges(ei)[0]) and np.array_equal(want[1], sweep_ref.undirected_edges(ei)[1])
+    ei, n = spectral_ref.path(5)
+    for unusable in (0, 3, 2 ** 31):   # no nodes, an id outside, a key past int64
+        got = sweep_ref.undirected_edges(ei, unusable)
+        assert np.array_equal(got[0], np.arange(4)) and np.array_equal(got[1], np.arange(1, 5))
+
+
 def test_order_rules():
     score = np.array([0.0, -0.0, np.inf, -np.inf, 5e-324, -5e-324, 1e308, -1e308, 0.0])
     assert sweep_ref.order_of(score).tolist() == [3, 7, 5, 0, 1, 8, 4, 6, 2]

@@ -7,6 +7,7 @@ import warnings
 import numpy as np
 import pytest
 
+import scale_ref
 import spectral_ref
 import sweep_ref
 
@@ -30,11 +31,14 @@ def assert_same(got, want, label=''):
 
 
 # ---- 1. the sort alone ---------------------------------------------------------------------------------------------------------
+SPECIALS = np.array([0.0, -0.0, np.inf, -np.inf, 5e-324, -5e-324, 2.2e-308, -2.2e-308, 1e308, -1e308, 1.0, -1.0])
+
+
 def score_families(n, rng):
     x = rng.standard_normal(n)
     base = np.float64(1.5)
     low_byte = (np.full(n, base).view(np.uint64) + rng.integers(0, 256, n).astype(np.uint64)).view(np.float64)
-    mix = rng.choice(np.array([0.0, -0.0, np.inf, -np.inf, 5e-324, -5e-324, 2.2e-308, -2.2e-308, 1e308, -1e308, 1.0, -1.0]), n)
+    mix = rng.choice(SPECIALS, n)
     return {
         'normal': x,
         'seven_values': rng.integers(0, 7, n).astype(np.float64) - 3.0,
@@ -55,6 +59,26 @@ def test_order_is_the_lexsort(dcr, n):
     for name, score in score_families(n, rng).items():
         got = G.sweep_cut(score).order
         assert np.array_equal(got, sweep_ref.order_of(score)), (n, name)
+
+
+# Sizes past the scans' closing stride and the tile limit (tests/test_scale_thresholds_cpu.py says which boundary each one is past):
+# a single edge, since the sort does not read the graph, and the families that can tell a wrong carry or tile bound: distinct
+# keys, ties that must keep id order through every pass and across tile borders, and the special values.  np.lexsort of 4.2M keys
+# takes a second, so the largest size runs two families.
+LARGE_SORTS = [(n, name) for n in scale_ref.SORT_SIZES for name in ('normal', 'seven_values', 'specials')
+               if not (n == scale_ref.SORT_SIZES[2] and name == 'specials')]
+
+
+@pytest.mark.parametrize('n,name', LARGE_SORTS)
+def test_order_is_the_lexsort_past_the_closing_strides(dcr, n, name):
+    ei, _ = scale_ref.single_edge(n)
+    rng = np.random.Generator(np.random.PCG64(n))    # the one family: all eight of score_families cost seconds at these sizes
+    score = {'normal': lambda: rng.standard_normal(n), 'seven_values': lambda: rng.integers(0, 7, n).astype(np.float64) - 3.0,
+             'specials': lambda: rng.choice(SPECIALS, n)}[name]()
+    got = dcr(ei, n).sweep_cut(score).order
+    want = sweep_ref.order_of(score)
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, (n, name, bad.size, bad[:4].tolist(), got[bad[:4]].tolist(), want[bad[:4]].tolist())
 
 
 # ---- 2. the whole call -----------------------------------------------------------------------------------------------------------
@@ -84,6 +108,38 @@ def test_whole_call_bit_exact(dcr, name, definition):
         assert_same(got, sweep_ref.sweep(ei, n, score, definition), name)
     if name == 'no_edges':
         assert np.isinf(got.value) and got.size == 1 and np.isinf(got.profile).all()
+
+
+_LARGE = {}
+
+
+def large_case(size, score_name):
+    """(edge_index, n, score, the counts of sweep_ref.prefix_counts): computed once, for both definitions."""
+    if (size, score_name) not in _LARGE:
+        ei, n = {scale_ref.WHOLE_SMALL: scale_ref.whole_small, scale_ref.WHOLE_LARGE: scale_ref.whole_large,
+                 scale_ref.WHOLE_CARRY: scale_ref.whole_carry}[size]()
+        rng = np.random.Generator(np.random.PCG64(size))
+        score = {'normal': rng.standard_normal(n), 'four_values': rng.integers(0, 4, n).astype(np.float64),
+                 'arange': np.arange(n, dtype=np.float64)}[score_name]
+        _LARGE[size, score_name] = (ei, n, score, sweep_ref.prefix_counts(ei, n, score))
+    return _LARGE[size, score_name]
+
+
+@pytest.mark.parametrize('definition', DEFINITIONS)
+@pytest.mark.parametrize('size', [scale_ref.WHOLE_SMALL, scale_ref.WHOLE_LARGE, scale_ref.WHOLE_CARRY])
+def test_whole_call_bit_exact_past_the_closing_strides(dcr, size, definition):
+    """70,001 nodes: more than 256 arg-min partials, all three row classes in k_sweep_edges.  524,289 nodes: a second grid-stride
+    trip of k_sweep_keys and k_sweep_value, 257 blocks of the difference arrays' scan, 37 isolated nodes at the end.  525,788
+    nodes: the same, and prefixes that read the 257th block, so a wrong carry shows (at 524,289 that block holds the count of
+    the whole node set alone, which nothing reads).  With the node id as score the best prefix is found by a workgroup whose
+    partial the closing loop reaches on a later trip (tests/test_scale_thresholds_cpu.py)."""
+    G = None
+    for score_name in ('normal', 'four_values', 'arange'):
+        ei, n, score, counts = large_case(size, score_name)
+        G = G or dcr(ei, n)
+        got = G.sweep_cut(score, definition=definition, return_profile=True)
+        assert_same(got, sweep_ref.from_counts(counts, definition), (size, score_name, definition))
+        assert np.isfinite(got.value) and 1 <= got.size < n
 
 
 def test_every_prefix_has_a_zero_volume(dcr):
