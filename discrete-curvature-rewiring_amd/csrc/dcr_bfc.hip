@@ -900,6 +900,20 @@ int dcr_pass_engine(dcr_graph *g, int *out) {
     return DCR_OK;
 }
 
+int dcr_h2_stats(dcr_graph *g, int32_t out[6]) {
+    if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (g->last_engine != 0 || !g->hres) return DCR_OK;
+    const DevResult &h = *g->hres;
+    out[0] = h.h2_ncand[0];
+    out[1] = h.h2_ncand[1];
+    out[2] = h.h2_fallback;
+    out[3] = h.h2_count[3];
+    out[4] = h.h2_count[4];
+    out[5] = h.h2_retry;
+    return DCR_OK;
+}
+
 int dcr_pass_plan(int64_t n, int64_t n_edges, int64_t cap_total, double sum_deg2, int32_t max_deg_bound, int pending_edits,
                   int pass_impl, int fine_on, int fine_full_set, int64_t fine_full_slots, int fine_sweep, int curv_type,
                   int incremental, int *out_route, int *out_list_by_rows, int *out_hub_supplement, double out_ms[3]) {

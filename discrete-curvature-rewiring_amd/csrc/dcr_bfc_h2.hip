@@ -735,6 +735,7 @@ struct H2Tab {
     unsigned *key;  // [EXS] 4-slot buckets
     unsigned *cnt;  // [EXS / 2] their state, 16 bits each
     int *full;      // set when the table fills up
+    int *wsum;      // [waves of the unit] per-wave totals of the join's slot scan
 };
 
 // M_u(w) and whether w is a member of N(u); {1, false} for a key this unit keeps no exact state for
@@ -869,6 +870,7 @@ struct H2Tasks {
     const int32_t *weight;  // bit 31: the node went to the retry list (what its first attempt listed is void)
     unsigned retry_flag;    // 0x80000000 in the retry launch
     unsigned *lists;        // per-wave lists of the third step (H2_LIST_WORDS each, one per wave of the launch; nullptr: none)
+    H2EdgeSet es;           // probed by the units that join their triangle term themselves (h2_batch_join)
 };
 // Pool space is handed out in chunks per wave (a reservation per edge on three shared counters cost more than the whole
 // step: same-address atomics serialise); what a wave leaves of a candidate chunk is marked void.  All members are uniform.
@@ -979,20 +981,28 @@ __device__ inline void h2_partners_short(const View &g, const H2Tasks tk, int u,
 // A wave whose list would overflow, or with more batches than the array holds, falls back to streaming (the old path).
 constexpr int H2_ITEMS = 2048;       // items per wave and unit
 constexpr int H2_REV_BATCHES = 16;   // batches of 64 rows per wave whose "position of u" the array holds
-constexpr int H2_LIST_WORDS = H2_ITEMS + H2_REV_BATCHES * 64;  // 32-bit words per wave
+constexpr int H2_LIST_OWN = H2_ITEMS + H2_REV_BATCHES * 64;  // a wave's own items and row array
+// ... plus, per workgroup, one array of as many words as its waves have items: the rows of the repeated keys grouped by key
+// (h2_join_prepare).  Layout of a workgroup's part of the pool: the waves' own parts, then that array.
+constexpr int H2_LIST_WORDS = H2_LIST_OWN + H2_ITEMS;  // 32-bit words per wave
 struct H2List {       // all members uniform over the wave
     unsigned *items;  // slot | row << 13 | batch << 19
     int *revs;        // [batch][row of the batch]: slot of u inside that row, -1: not found
+    int32_t *srt;     // the workgroup's: for every key that repeats, the members of N(u) whose rows hold it, one run per table slot
     int n;            // items appended (counts past the capacity)
     bool over;        // the list does not describe the unit: stream the third sweep
+    bool join;        // uniform over the workgroup: no wave's list overflowed, the unit joins its triangle term itself
 };
 __device__ inline H2List h2_list_of(unsigned *pool, int waves_per_group) {
     H2List ls;
-    unsigned *mine = pool ? pool + ((int64_t)blockIdx.x * waves_per_group + (threadIdx.x >> 6)) * H2_LIST_WORDS : nullptr;
+    unsigned *group = pool ? pool + (int64_t)blockIdx.x * waves_per_group * H2_LIST_WORDS : nullptr;
+    unsigned *mine = group ? group + (int64_t)(threadIdx.x >> 6) * H2_LIST_OWN : nullptr;
     ls.items = mine;
     ls.revs = reinterpret_cast<int *>(mine ? mine + H2_ITEMS : nullptr);
+    ls.srt = reinterpret_cast<int32_t *>(group ? group + (int64_t)waves_per_group * H2_LIST_OWN : nullptr);
     ls.n = 0;
     ls.over = mine == nullptr;
+    ls.join = false;
     return ls;
 }
 
@@ -1230,6 +1240,137 @@ __device__ inline void h2_batch_end(const View &g, const H2Tasks tk, H2Alloc &al
     }
 }
 
+// ---- the triangle term joined inside the unit -----------------------------------------------------------------------------
+// c(w) for the occurrence of w in row r (edge {u, v_r}) is M_u(w) - 1 - |{ t in N(u) ∩ N(v_r) : t adjacent to w }|.  Every such t
+// is itself a row j of u, and "t adjacent to w" is "w occurs in row j": the second sweep has listed exactly these occurrences
+// (an item {slot of w, row j} per occurrence of a repeated key).  So the last term is
+//     |{ j in rows(w), j != r : v_j adjacent to v_r }|,
+// M_u(w) - 1 probes of the edge set for a candidate instead of one per triangle partner of its edge (hundreds on a hub-to-hub
+// edge, nearly all of them misses), asked by the unit itself with the counts at hand: it publishes final records and lists
+// nothing for k_h2_triangles.  rows(w) comes from a counting sort of the unit's items by table slot: the counts are the
+// table's own, the cursors live in B1 (dead after the first sweep, and exactly EXS 16-bit words large), the sorted members go
+// to the workgroup's array in device memory.  Needs every wave's list complete: a unit with an overflowed list keeps the old
+// path (pools and k_h2_triangles) and is counted in DevResult::h2_fallback.
+// Cost: a key met in M rows is a candidate in up to M of them and each asks M times: M (M - 1) probes per key, against T_r per
+// candidate on the old path — far fewer on power-law graphs (M <= 43 on S100k, <= 54 on S1M, T_r in the hundreds on hub-to-hub
+// edges), but quadratic where two hubs share thousands of neighbours.  A unit with a key in more than H2_JOIN_MAXM rows therefore
+// keeps the old path as well: a candidate's serial loop stays at most 32 rounds of 8 probes in flight, what the old path spends on an
+// edge with 256 partners.
+constexpr int H2_JOIN_MAXM = 256;
+__device__ inline int h2_probe_partners(const H2EdgeSet es, int w, const int32_t *pt, int np);
+
+// all threads of the unit; the table is complete, no wave's list overflowed.  false (uniform, nothing written but B1): some key is
+// in more rows than the join takes
+template <int L1, int EXS, int NW>
+__device__ inline bool h2_join_prepare(const View &g, const H2Tab t, int2 ru, const H2List &ls) {
+    constexpr int NT = 64 * NW, PER = EXS / NT;  // consecutive table slots per thread
+    static_assert(PER >= 2 && PER % 2 == 0, "a thread owns whole cursor words");
+    static_assert(EXS / 2 <= (1 << L1) / 32, "the cursors fit B1");
+    static_assert(NW * H2_ITEMS < 65536 && EXS <= 8192, "16-bit cursors, 13-bit slots");
+    const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    unsigned *cur = t.b1;
+    int n[PER], sum = 0, most = 0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const unsigned c16 = h2_cnt_get(t.cnt, tid * PER + q);
+        n[q] = ((c16 & 0x8000u) || c16 < 2u) ? 0 : (int)c16;  // (members of N(u) and keys met once are no candidates)
+        sum += n[q];
+        most = n[q] > most ? n[q] : most;
+    }
+    if (__syncthreads_or(most > H2_JOIN_MAXM)) return false;
+    int excl;
+    const int wtot = h2_prefix(sum, excl);
+    if (lane == 0) t.wsum[wid] = wtot;
+    __syncthreads();
+    int off = excl;
+    for (int w = 0; w < wid; ++w) off += t.wsum[w];
+#pragma unroll
+    for (int q = 0; q < PER; q += 2) {
+        const unsigned lo = (unsigned)off;
+        off += n[q];
+        const unsigned hi = (unsigned)off;
+        off += n[q + 1];
+        cur[(tid * PER + q) >> 1] = lo | (hi << 16);
+    }
+    __syncthreads();
+    for (int base = 0; base < ls.n; base += 64) {
+        const int j = base + lane;
+        if (j >= ls.n) continue;
+        const unsigned item = ls.items[j];
+        const int s = (int)(item & 0x1FFFu), r = (int)((item >> 13) & 63u), b = (int)(item >> 19);
+        const unsigned c16 = h2_cnt_get(t.cnt, s);
+        if ((c16 & 0x8000u) || c16 < 2u) continue;
+        const int row = (b * 64 + r) * NW + wid;  // (see h2_stream: lane r of batch b of wave wid)
+        if (row >= ru.y) {
+            row_ok(g, make_int2(-1, row), 44, ru.y, (int)item);  // an item of a row the node does not have: report, the pass fails
+            continue;
+        }
+        const int v = g.col[ru.x + row];
+        const unsigned old = atomicAdd(&cur[s >> 1], 1u << ((s & 1) * 16));
+        const int p = (int)((old >> ((s & 1) * 16)) & 0xFFFFu);
+        if (p < NW * H2_ITEMS) ls.srt[p] = v;
+        else row_ok(g, make_int2(-1, p), 45, s, (int)c16);  // more occurrences listed than counted: report, never write
+    }
+    __syncthreads();  // every cursor now stands at the END of its slot's run
+    return true;
+}
+
+// One batch of rows of one wave in join mode: triangle counts, corrected candidate counts, records.  lcur: the wave's next item.
+template <int L1, int EXS, int NW, bool PARTS>
+__device__ inline void h2_batch_join(const View &g, const H2Tasks tk, H2Alloc &al, int u, int2 ru, int i, int k, int2 rk, int part,
+                                     const H2Tab t, H2Scratch *sc, uint4 *rec, const H2List &ls, int &lcur, int bidx, int rev) {
+    const int lane = threadIdx.x & 63;
+    sc->rowT[lane] = 0;
+    sc->rowPos[lane] = 0;
+    sc->rowMx[lane] = 0;
+    sc->rowRev[lane] = rev;
+    if (lane == 0) sc->pln = 0;
+    h2_wave_sync();
+    const int lfrom = lcur;
+#pragma unroll 1
+    while (true) {  // the batch's items (batch-monotone): a flagged one is a triangle partner of its row
+        const int j = lcur + lane;
+        const unsigned item = j < ls.n ? ls.items[j] : 0xFFFFFFFFu;
+        const bool mine = j < ls.n && (int)(item >> 19) == bidx;
+        const int cnt = __popcll(__ballot(mine));
+        if (cnt == 0) break;  // uniform
+        if (mine && (h2_cnt_get(t.cnt, (int)(item & 0x1FFFu)) & 0x8000u)) atomicAdd(&sc->rowT[(item >> 13) & 63u], 1);
+        lcur += cnt;
+        if (cnt < 64) break;
+    }
+    h2_wave_sync();
+    const unsigned *cur = t.b1;
+#pragma unroll 1
+    for (int base = lfrom; base < lcur; base += 64) {
+        const int j = base + lane;
+        const bool have = j < lcur;
+        const unsigned item = have ? ls.items[j] : 0u;
+        const int s = (int)(item & 0x1FFFu), r = (int)((item >> 13) & 63u);
+        const int vr = __shfl(k, r);
+        if (!have) continue;
+        const unsigned c16 = h2_cnt_get(t.cnt, s);
+        if (c16 & 0x8000u) continue;
+        const int m = (int)(c16 & 0x7FFFu);
+        int c = m - 1;
+        if (c <= 0) continue;
+        if (sc->rowT[r] > 0 && vr >= 0) {
+            const int end = (int)((cur[s >> 1] >> ((s & 1) * 16)) & 0xFFFFu);
+            if (end >= m && end <= NW * H2_ITEMS) {
+                c -= h2_probe_partners(tk.es, vr, ls.srt + (end - m), m);  // (v_r itself is in the run: no edge)
+            } else {
+                row_ok(g, make_int2(-1, end), 46, s, m);  // the cursor is not at the end of its run: report, never publish uncorrected
+                c = 0;
+            }
+        }
+        if (c > 0) {
+            atomicAdd(&sc->rowPos[r], 1);
+            atomicMax(&sc->rowMx[r], c);
+        }
+    }
+    h2_wave_sync();
+    h2_batch_end<L1, EXS, PARTS>(g, tk, al, u, ru, i, k, rk, -1, 0, part, t, sc, rec);  // (no task base: lists nothing, publishes)
+}
+
 // Wave `wid` of NW takes the rows i = wid, wid + NW, ... of row u (strided: a hub's heaviest rows, adjacent at the
 // front of its row, spread over the waves); lane l of the batch starting at `base` stands for row base + l * NW + wid.
 // PHASE 0: bitmaps; 1: occurrences of the repeated keys; 2: per-row statistics, triangle step, records.
@@ -1270,6 +1411,11 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
         int tbase = -1, trow = 0;  // third sweep: the tasks of this batch's rows (tbase uniform; trow: this lane's row)
         if (PHASE == 2 && !ls.over) {
             // the third step from the second sweep's list: no row is streamed, no entry tested or looked up again
+            if (ls.join) {
+                h2_batch_join<L1, EXS, NW, PARTS>(g, tk, al, u, ru, i, k, rk, part, t, sc, rec, ls, lcur, bidx, ls.revs[bidx * 64 + lane]);
+                h2_wave_sync();  // the scratch is rewritten by the next batch
+                continue;
+            }
             h2_batch_begin(tk, al, sc, k, tbase, trow, ls.revs[bidx * 64 + lane]);
             h2_wave_sync();
             const int lfrom = lcur;
@@ -1456,7 +1602,15 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
     }
     __syncthreads();
     ok = *t.full == 0;  // uniform
-    if (ok) {
+    ls.join = !__syncthreads_or(ls.over) && ok;
+    if (ls.join) ls.join = h2_join_prepare<L1, EXS, NW>(g, t, ru, ls);
+    if (ls.join) {
+        int lcur = 0;
+        const int myrev = sc->rowRev[lane];
+        h2_wave_sync();
+        h2_batch_join<L1, EXS, NW, PARTS>(g, tk, al, u, ru, i, k, rk, part, t, sc, rec, ls, lcur, 0, myrev);
+    } else if (ok) {
+        if (tid == 0) atomicAdd(&tk.res->h2_fallback, 1);
         if (!ls.over) {  // uniform over the wave
             int lcur = 0;
             const int myrev = sc->rowRev[lane];
@@ -1524,6 +1678,9 @@ __device__ inline bool h2_node(const View &g, const H2Tasks tk, H2Alloc &al, int
     h2_stream<L1, EXS, NW, PARTS, 1>(g, tk, al, u, ru, part, nparts, t, sc, rec, k0, rk0, ls);
     __syncthreads();
     const bool ok = *t.full == 0;  // uniform
+    ls.join = !__syncthreads_or(ls.over) && ok;
+    if (ls.join) ls.join = h2_join_prepare<L1, EXS, NW>(g, t, ru, ls);
+    if (!ls.join && ok && tid == 0) atomicAdd(&tk.res->h2_fallback, 1);
     if (ok) h2_stream<L1, EXS, NW, PARTS, 2>(g, tk, al, u, ru, part, nparts, t, sc, rec, k0, rk0, ls);
     __syncthreads();  // the tables are rewritten by the next unit
     return ok;
@@ -1540,13 +1697,14 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
     __shared__ __attribute__((aligned(16))) unsigned cnt[EXS / 2];
     __shared__ H2Scratch sc_all[NW];
     __shared__ int full;
+    __shared__ int wsum[NW];
     const int wid = threadIdx.x >> 6;
     const int total = *count;
     if (total < 0 || total > unit_cap) {  // uniform
         row_ok(g, make_int2(-1, total), 37, 0, 0);
         return;
     }
-    const H2Tab t{bits, bits + (1 << L1) / 32, key, cnt, &full};
+    const H2Tab t{bits, bits + (1 << L1) / 32, key, cnt, &full, wsum};
     H2Alloc al;
     for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {  // every value steering the barriers is uniform
         const int4 un = units[it];
@@ -1813,6 +1971,7 @@ __global__ void __launch_bounds__(256) k_h2_clear(DevResult *res, int32_t *weigh
         res->h2_retry = 0;
         for (int p = 0; p < 2; ++p) res->h2_ntask[p] = res->h2_ncand[p] = res->h2_npart[p] = res->h2_ncand_done[p] = 0;
         for (int c = 0; c < 6; ++c) res->h2_failed[c] = 0;
+        res->h2_fallback = 0;
         res->flag_too_big = 0;
     }
 }
@@ -2046,10 +2205,11 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     const int64_t tcap = g->h2_task_cap / 2, ccap = g->h2_cand_cap / 2, pcap = g->h2_part_cap / 2;
     DevResult *dr = g->dres;
     unsigned *lists_L = g->h2_lists, *lists_M = g->h2_lists + (int64_t)g->num_cu * 16 * H2_LIST_WORDS;
+    const H2EdgeSet es{g->h2_eset, g->h2_eset_bits, g->h2_bloom, g->h2_bloom_bits};
     H2Tasks tk{g->h2_task, g->h2_cand, g->h2_part, tcap, ccap, pcap, &dr->h2_ntask[0], &dr->h2_ncand[0], &dr->h2_npart[0],
-               &dr->h2_ncand_done[0], g->dres, g->h2_weight, 0u, lists_L};  // pool 0: the split class and the retry launch
+               &dr->h2_ncand_done[0], g->dres, g->h2_weight, 0u, lists_L, es};  // pool 0: the split class and the retry launch
     const H2Tasks tkM{g->h2_task + tcap, g->h2_cand + ccap, g->h2_part + pcap, tcap, ccap, pcap, &dr->h2_ntask[1], &dr->h2_ncand[1],
-                      &dr->h2_npart[1], &dr->h2_ncand_done[1], g->dres, g->h2_weight, 0u, lists_M};  // pool 1: class M
+                      &dr->h2_npart[1], &dr->h2_ncand_done[1], g->dres, g->h2_weight, 0u, lists_M, es};  // pool 1: class M
     {
         const int64_t cb = (g->n + 255) / 256;
         // (dirty: n bytes, allocated in whole words? — only the whole words are zeroed here, the caller's fill takes the rest)
@@ -2059,7 +2219,6 @@ int launch_curvature_pass_h2(dcr_graph *g) {
         g->h2_cleared_dirty = whole;
     }
     const int64_t sblocks = (g->cap_total + 255) / 256;
-    const H2EdgeSet es{g->h2_eset, g->h2_eset_bits, g->h2_bloom, g->h2_bloom_bits};
     if (sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight);
     const int64_t pblocks = (g->n + H2_PLAN_THREADS - 1) / H2_PLAN_THREADS;
     if (pblocks > 0) {
@@ -2119,13 +2278,17 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     g->h2_eset_pending = 0;
     const int64_t hint4 = g->h2_last_count[4] >= 0 ? (int64_t)g->h2_last_count[4] + 8 : g->num_cu;
     const int64_t hint3 = g->h2_last_count[3] >= 0 ? (int64_t)g->h2_last_count[3] + 8 : 3 * (int64_t)g->num_cu;
-    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, on(0));
-    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, on(1));
+    // (the block classes probe the edge set themselves: a set that is being rebuilt has to be complete before they start)
+    hipStream_t st_split = on(0), st_mid = on(1);
+    if (eset_on_aux) {
+        DCR_HIP(hipStreamWaitEvent(st_split, g->ev_aux, 0));
+        if (st_mid != st_split) DCR_HIP(hipStreamWaitEvent(st_mid, g->ev_aux, 0));
+    }
+    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, st_split);
+    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, st_mid);
     // each block class's triangle step right behind it on its own stream (class M's behind the split class's: 292 us beside
     // the other classes, 60 alone — it started 90 us after M's end and sat on the critical path)
-    if (eset_on_aux) DCR_HIP(hipStreamWaitEvent(pool[lay[0]], g->ev_aux, 0));
     hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
-    if (eset_on_aux && lay[1] != lay[0]) DCR_HIP(hipStreamWaitEvent(pool[lay[1]], g->ev_aux, 0));
     hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
     launch_h2_small<2>(g, vw, rt, on(2));
     launch_h2_small<1>(g, vw, rt, on(3));

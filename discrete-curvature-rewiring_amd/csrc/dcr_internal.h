@@ -83,6 +83,7 @@ struct DevResult {
     // k_h2_triangles launch of the pool has taken
     int32_t h2_ntask[2], h2_ncand[2], h2_npart[2];
     int32_t h2_ncand_done[2];
+    int32_t h2_fallback;  // block-class units that listed their triangle work for k_h2_triangles instead of joining it themselves
     // Edit journal (round 4): every edge the device adds or removes since the two-hop pass last brought its edge set up to
     // date: {+1 / -1, u, v} per edit, in order; edit_n keeps counting past the capacity (the host then knows the bound on
     // its own and rebuilds the set).  Written by dev_add_edge / dev_remove_edge, consumed by k_h2_eset_apply.

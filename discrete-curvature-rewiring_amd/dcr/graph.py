@@ -588,6 +588,13 @@ class DcrGraph:
         check(lib().dcr_pass_engine(self._h, ctypes.byref(out)))
         return {0: 'two-hop', 1: 'edge-centric', 2: 'node-centric'}.get(out.value, 'none')
 
+    def h2_stats(self):
+        """Diagnostics of the last two-hop pass: candidates listed for the triangle kernel per pool, block-class units that
+        took that probe path, units of class M and of the split class, units on the retry list."""
+        out = (ctypes.c_int32 * 6)()
+        check(lib().dcr_h2_stats(self._h, out))
+        return {'ncand': (out[0], out[1]), 'fallback': out[2], 'units_m': out[3], 'units_split': out[4], 'retry': out[5]}
+
     def bfc_algorithmic_bytes(self, one_sided=False):
         """SURVEY §8(d) bytes of one BFC pass; ``one_sided``: only the cheaper difference set's rows per edge."""
         out = ctypes.c_double()

@@ -128,6 +128,10 @@ int dcr_sdrf_tail_at(dcr_graph *g, int64_t cand_index, int do_remove, double rem
  * graph is created), 2 node-centric kernels (csrc/dcr_bfc_nc.hip: everything else, or DCR_PASS=nc), 1 edge-centric kernels
  * (DCR_PASS=edge); -1 before the first pass.  All three produce the same bits. */
 int dcr_pass_engine(dcr_graph *g, int *out);
+/* Diagnostics of the last two-hop pass: candidates listed for the triangle kernel by the split class's pool and by class
+ * M's, block-class units that took that probe path (their item list overflowed) instead of joining the triangle term
+ * themselves, units of class M, units of the split class, units on the retry list.  Zeros after a pass of another engine. */
+int dcr_h2_stats(dcr_graph *g, int32_t out[6]);
 /* The route a pass with these facts and switches takes (csrc/dcr_pass_route.h: plan_pass, the function every pass calls): no
  * handle, no environment, no GPU.  Facts: nodes, undirected edges, adjacency slots, sum of squared degrees, upper bound on the
  * degrees, edits since the last pass.  Switches: pass_impl 0 automatic / 1 edge / 2 nc / 3 h2 (DCR_PASS), fine_on (DCR_NC_FINE),
