@@ -810,6 +810,8 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
     if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
     DCR_HIP(hipSetDevice(g->device));
+    g->h2_launches = 0;
+    g->h2_last_retry_stage = g->h2_last_tri_stage = false;
     g->amax_valid = false;
     g->ext_part_valid = false;  // (set again by the two-hop pass's closing kernel)
     // first minimum in G.edges order, same host sync as the pass: from the closing kernel's per-block minima when it left some
@@ -850,12 +852,24 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     };
     DCR_TRY(read_result());
     if (g->last_engine == 0) {
+        // (the bound: the longest chain of one call is four more launches — a missing retry stage (3), then a missing triangle
+        //  stage for what only the retry launch listed (4), then pools grown once or twice (2); six leaves room for a third growth)
         for (int again = 0; again < 6 && g->hres->misc[0] == 0; ++again) {
-            if (g->hres->h2_status == 3) {
+            const int st = g->hres->h2_status;
+            // a pass without its triangle stage in which some block-class unit listed for it: whatever else the pass reports, the
+            // next launch carries the stage, and so does every later pass of this graph (the closing kernel leaves 4 only in place
+            // of 0: behind a 3 or a 2 the count says the same)
+            const bool want_tri = !g->h2_last_tri_stage && g->hres->h2_fallback > 0;
+            if (want_tri) g->h2_expect_triangles = true;
+            if (st == 3) {
                 // launched without its retry stage, and some node's tables filled up: nothing was written; from now on every
                 // pass of this graph carries the stage
                 g->h2_expect_retry = true;
-            } else if (g->hres->h2_status == 2 && h2_grow_pools(g)) {
+            } else if (st == 4 && want_tri) {
+                // launched without its triangle stage, see above: nothing was written.  Like a 3, a 4 stands only where nothing
+                // else went wrong, so k_h2_eset_apply has applied the whole journal (a failure there leaves 1): the launch that
+                // follows finds a valid edge set with no edit pending and patches nothing
+            } else if (st == 2 && h2_grow_pools(g)) {
                 // the pools of its triangle step were too small (dense neighbourhoods): run it again with what it asked for
             } else {
                 break;
@@ -911,6 +925,14 @@ int dcr_h2_stats(dcr_graph *g, int32_t out[6]) {
     out[3] = h.h2_count[3];
     out[4] = h.h2_count[4];
     out[5] = h.h2_retry;
+    return DCR_OK;
+}
+
+int dcr_h2_launch_info(dcr_graph *g, int32_t out[3]) {
+    if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
+    out[0] = g->h2_launches;
+    out[1] = g->h2_last_retry_stage ? 1 : 0;
+    out[2] = g->h2_last_tri_stage ? 1 : 0;
     return DCR_OK;
 }
 

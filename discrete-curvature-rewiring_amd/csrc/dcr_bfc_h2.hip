@@ -2006,10 +2006,18 @@ __global__ void __launch_bounds__(256) k_h2_retry_zero(View g, const int4 *units
 // `when` = 0: the pass was launched WITHOUT its retry stage (no pass of this graph has needed it so far: three launches and a
 // stream join less on the critical path of every pass); should the retry list turn out not to be empty, nothing is written,
 // status 3 is left and the host runs the pass again with the stage.  `when` = 1: behind the retry stage, unconditionally.
+// `tri_stage` = 0: the pass was launched WITHOUT its k_h2_triangles launches (no pass of this graph has had a block-class unit on
+// the probe path so far); should some unit have listed for them after all, its records lack their corrections: nothing is
+// written, status 4 is left and the host runs the pass again with the launches.
 __global__ void __launch_bounds__(256) k_h2_final(View g, const uint4 *rec, double *curv, const int32_t *status, Ext *part_min,
-                                                  Ext *part_max, const int32_t *retry_count, int when) {
+                                                  Ext *part_max, const int32_t *retry_count, int when, const int32_t *fallback_count,
+                                                  int tri_stage) {
     if (when == 0 && *retry_count > 0) {  // uniform (the count is final once the class kernels are through)
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicCAS(const_cast<int32_t *>(status), 0, 3);
+        return;
+    }
+    if (tri_stage == 0 && *fallback_count > 0) {  // uniform (final as well: the class kernels and the retry launch are through)
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicCAS(const_cast<int32_t *>(status), 0, 4);
         return;
     }
     double lo_v = 0.0, hi_v = 0.0;
@@ -2239,7 +2247,13 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     // timelines).  Measured (profiles/r05_layouts.txt, interleaved rounds, pass ms): S100k five streams 1.020, {0,1,2,2,1} 0.962,
     // {0,1,1,2,2} 0.962, {0,1,2,2,2} 0.984, {0,1,2,3,3} 0.983, {0,1,1,1,1} 1.094; S1M five streams 10.10, {0,1,2,2,1} 10.70 —
     // the fixed costs do not matter there and five abreast packs the chip better.
-    static const int three_streams[H2_CLASSES] = {0, 1, 2, 2, 1}, five_streams[H2_CLASSES] = {0, 1, 2, 3, 4};
+    // Re-dealt once the triangle launches were gone from the pass (profiles/tristage_layouts.txt, the same method): behind the
+    // split class the main stream stood idle from about 400 us on while wave class 0 waited behind class M until 564 us and
+    // ended the pass.  S100k pass ms, medians of three interleaved rounds: {0,1,2,2,1} 0.818, {0,1,2,2,0} 0.809, {0,1,2,0,1}
+    // 0.799, {0,1,2,0,2} 0.791 (spread of each below 0.003) — wave class 1 behind the split class, classes 2 and 0 share the
+    // second side stream, class M has the first to itself.  With the triangle stage (h2_expect_triangles) each block class's
+    // triangle launch stays right behind it on its stream, ahead of whatever the table puts there next.
+    static const int three_streams[H2_CLASSES] = {0, 1, 2, 0, 2}, five_streams[H2_CLASSES] = {0, 1, 2, 3, 4};
     const int *lay = g->n < 400000 ? three_streams : five_streams;
     hipStream_t pool[5] = {g->stream, g->side[1], g->low[0], g->low[1], g->side[2]};
     hipEvent_t done[5] = {nullptr, g->ev_join[1], g->ev_join[2], g->ev_join[3], g->ev_aux2};
@@ -2286,10 +2300,17 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     }
     launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, st_split);
     launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, st_mid);
-    // each block class's triangle step right behind it on its own stream (class M's behind the split class's: 292 us beside
-    // the other classes, 60 alone — it started 90 us after M's end and sat on the critical path)
-    hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
-    hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
+    // The triangle stage (both launches here and the one behind the retry launch) goes with the pass only once some pass of this
+    // graph has had a block-class unit on the probe path: the units join their triangle term themselves, and on a graph where all
+    // of them can the launches found nothing to do, yet each pushed a full-chip grid through a full chip (32 us on average on the
+    // bench graph, the one behind class M ahead of the kernel that ends the pass).  k_h2_final checks the expectation (status 4).
+    const bool tri_stage = g->h2_expect_triangles;
+    if (tri_stage) {
+        // each block class's triangle step right behind it on its own stream (class M's behind the split class's: 292 us beside
+        // the other classes, 60 alone — it started 90 us after M's end and sat on the critical path)
+        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
+        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
+    }
     launch_h2_small<2>(g, vw, rt, on(2));
     launch_h2_small<1>(g, vw, rt, on(3));
     launch_h2_small<0>(g, vw, rt, on(4));
@@ -2314,10 +2335,15 @@ int launch_curvature_pass_h2(dcr_graph *g) {
                            g->h2_rec);
         tk.retry_flag = 0x80000000u;
         launch_h2_block<4, true>(g, vw, tk, rt, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap, 64, 1, g->stream);
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 2)), dim3(256), 0, g->stream, es, tk, g->h2_rec, status, 1);
+        if (tri_stage)
+            hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 2)), dim3(256), 0, g->stream, es, tk, g->h2_rec, status, 1);
     }
     hipLaunchKernelGGL(k_h2_final, dim3((unsigned)fblocks), dim3(256), 0, g->stream, vw, g->h2_rec, g->curv, status, (Ext *)g->ext_part,
-                       (Ext *)g->ext_part + EXT_PART_BLOCKS, &g->dres->h2_retry, retry_stage ? 1 : 0);
+                       (Ext *)g->ext_part + EXT_PART_BLOCKS, &g->dres->h2_retry, retry_stage ? 1 : 0, &g->dres->h2_fallback,
+                       tri_stage ? 1 : 0);
+    g->h2_launches += 1;
+    g->h2_last_retry_stage = retry_stage;
+    g->h2_last_tri_stage = tri_stage;
     g->ext_part_n = (int)fblocks * 4;
     g->ext_part_valid = true;  // (dropped again by the caller if the pass reports a failure, and by every edit)
     DCR_HIP(hipGetLastError());

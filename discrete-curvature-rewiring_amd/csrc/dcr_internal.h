@@ -94,7 +94,10 @@ struct DevResult {
     int32_t h2_retry;   // units on the retry list (nodes whose tables filled up in their class, redone by the largest class)
     int32_t h2_status;  // 0 ok; 1: a table filled up or a list overflowed (the pass is then redone by the node-centric kernels);
                         // 2: the triangle step's pools were too small (run again with larger ones); 3: the pass was launched
-                        // without its retry stage and some node needed it (run again with the stage)
+                        // without its retry stage and some node needed it (run again with the stage); 4: the pass was launched
+                        // without its triangle stage and some block-class unit listed for it (h2_fallback > 0: run again with
+                        // the stage).  3 and 4 are only ever put in place of 0, and the closing kernel asks for the retry stage
+                        // first: a pass that misses both stages leaves 3, and the host reads h2_fallback next to it
 };
 
 // Incremental pass: which edges an edit can have changed.  BFC(a,b) is a function of deg a, deg b, N(a) ∩ N(b) and the
@@ -274,6 +277,10 @@ struct dcr_graph {
     unsigned long long *h2_eset = nullptr;  // every undirected edge as one 64-bit key (open addressing), rebuilt per pass
     int h2_eset_bits = 0;
     bool h2_expect_retry = false;      // some pass of this graph had nodes on the retry list: the retry stage is launched with every pass
+    bool h2_expect_triangles = false;  // some pass of this graph had a block-class unit on the probe path (DevResult::h2_fallback):
+                                       // the k_h2_triangles launches go with every pass
+    int h2_launches = 0;               // two-hop launches of the last dcr_curvature_pass* call, and which stages the last of them carried
+    bool h2_last_retry_stage = false, h2_last_tri_stage = false;
     bool h2_cleared_dirty = false;     // the last two-hop launch zeroed the incremental pass's node flags itself
     bool h2_eset_valid = false;        // the set holds the graph's edges as of the last two-hop pass; later edits are in the journal
     int h2_eset_pending = 0;           // upper bound of the edits journaled since (host-side count of the edit launches)

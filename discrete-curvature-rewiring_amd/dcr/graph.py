@@ -595,6 +595,13 @@ class DcrGraph:
         check(lib().dcr_h2_stats(self._h, out))
         return {'ncand': (out[0], out[1]), 'fallback': out[2], 'units_m': out[3], 'units_split': out[4], 'retry': out[5]}
 
+    def h2_launch_info(self):
+        """How the last curvature pass call ran the two-hop pass: times it was launched (0: another engine ran), and whether
+        the last launch carried the retry stage and the triangle stage."""
+        out = (ctypes.c_int32 * 3)()
+        check(lib().dcr_h2_launch_info(self._h, out))
+        return {'launches': out[0], 'retry_stage': bool(out[1]), 'triangle_stage': bool(out[2])}
+
     def bfc_algorithmic_bytes(self, one_sided=False):
         """SURVEY §8(d) bytes of one BFC pass; ``one_sided``: only the cheaper difference set's rows per edge."""
         out = ctypes.c_double()

@@ -132,6 +132,11 @@ int dcr_pass_engine(dcr_graph *g, int *out);
  * M's, block-class units that took that probe path (their item list overflowed) instead of joining the triangle term
  * themselves, units of class M, units of the split class, units on the retry list.  Zeros after a pass of another engine. */
 int dcr_h2_stats(dcr_graph *g, int32_t out[6]);
+/* How the last dcr_curvature_pass* call ran the two-hop pass: how many times it was launched (0: another engine; more than 1: a
+ * launch found that it needed a stage it was launched without, or larger pools, and was run again), and whether the last of the
+ * launches carried the retry stage and the triangle stage (k_h2_triangles).  Both stages are left out until a pass of the graph
+ * needs them and go with every pass from then on. */
+int dcr_h2_launch_info(dcr_graph *g, int32_t out[3]);
 /* The route a pass with these facts and switches takes (csrc/dcr_pass_route.h: plan_pass, the function every pass calls): no
  * handle, no environment, no GPU.  Facts: nodes, undirected edges, adjacency slots, sum of squared degrees, upper bound on the
  * degrees, edits since the last pass.  Switches: pass_impl 0 automatic / 1 edge / 2 nc / 3 h2 (DCR_PASS), fine_on (DCR_NC_FINE),
