@@ -40,6 +40,19 @@
 // fill the device with one batch, so up to DIF_MAX_GROUPS batches share every launch as blockIdx.y (while groups x nodes stays
 // within DIF_GROUP_NODES), each with its own vectors, partials, ticket and control block: the arithmetic of a column is that of
 // its batch alone, however many batches run beside it.
+//
+// The heat kernel, GDC's other diffusion: S = exp(-t (I - H)) = e^-t Σ_k t^k / k! H^k for 0 < t <= 256.  Every term is non-negative,
+// so nothing cancels and a partial sum is an entrywise lower bound of the column; H √d̃ = √d̃, so with r = √d̃ the mass the partial sum
+// x = Σ_{k <= K} θ_k H^k e_j (θ_k = e^-t t^k / k!) still lacks is r_j - Σ_i r_i x_i = r_j ρ_K, ρ_K = Σ_{k > K} θ_k, and
+// 0 <= S_ij - x_i <= deficit_j / r_i.  K is fixed on the host before the first launch (heat_terms: the smallest K with ρ_K <= tol / 2,
+// the tail added term by term from its small end, or max_terms where that is lower): no data-dependent stop, no ticket and no
+// read-back between terms.  The recurrence v_0 = e^-t e_j, v_{k+1} = t / (k + 1) s̃ ⊙ ((A + I)(s̃ ⊙ v_k)), x += v_{k+1} keeps only
+// z = s̃ ⊙ v between terms, in two buffers by turns (z and p of the PageRank layout): other rows read z_in during the sweep.
+//   k_heat_start     x = e^-t e_j, z = s̃ ⊙ x for all columns (padding columns are zero and stay zero)
+//   k_heat_term      one launch a term, the row walk of k_dif_matvec: v = c (s̃_u (Σ z_in[col] + z_in[u])), x[u] += v,
+//                    z_out[u] = s̃_u v, with c = t / (k + 1) an argument
+//   k_heat_mass      partials of Σ_i r_i x_i per column; the last arriver writes deficit_j = r_j - Σ_i r_i x_i
+// K + 2 launches a batch, then k_dif_select / k_dif_fill as they are.  A column's bits depend on its source, t and K only.
 #include <algorithm>
 #include <cmath>
 
@@ -60,7 +73,7 @@ struct DifCtl {
     double rr[DIF_B];      // |r|^2 of the recurrence
     double gain[DIF_B];    // the step length of CG (its "alpha"; α is the teleport probability here)
     double beta[DIF_B];
-    double resid[DIF_B];   // the closing mat-vec's |α e_j - M x|_2
+    double resid[DIF_B];   // the closing mat-vec's |α e_j - M x|_2; heat: the deficit r_j - Σ_i r_i x_i
     double teleport, damp; // α, 1 - α
     double stop;           // tol α
     uint64_t thr[DIF_B];   // selection: the threshold key
@@ -284,6 +297,80 @@ __global__ void __launch_bounds__(256) k_dif_scale_x(int64_t n, const double *__
     }
 }
 
+// ---- heat kernel -------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_heat_start(const double *__restrict__ s, int64_t n, const DifCtl *__restrict__ ctl, double start,
+                                                     double *__restrict__ z, double *__restrict__ x, int64_t gstride) {
+    const int cp = threadIdx.x % DIF_CP;
+    const int64_t go = (int64_t)blockIdx.y * gstride;
+    ctl += blockIdx.y, z += go, x += go;
+    const int32_t j0 = ctl->src[2 * cp], j1 = ctl->src[2 * cp + 1];
+    const int64_t total = n * DIF_CP;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t node = e / DIF_CP;
+        const double sn = s[node];
+        const double2 c = make_double2(dif_rhs((int32_t)node, j0, start), dif_rhs((int32_t)node, j1, start));  // e^-t e_src
+        dif_st2(x, node, cp, c);
+        dif_st2(z, node, cp, make_double2(sn * c.x, sn * c.y));
+    }
+}
+
+// x += v, z_out = s̃ ⊙ v with v = c s̃ ⊙ ((A + I) z_in) for all columns in one sweep of the rows; a row's x and z_out are written by its
+// owner lanes alone, z_in by nobody
+__global__ void __launch_bounds__(256) k_heat_term(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
+                                                    const double *__restrict__ z_in, const double *__restrict__ s, double c,
+                                                    double *__restrict__ z_out, double *__restrict__ x, int64_t gstride) {
+    __shared__ double2 sh[4 * DIF_CP];
+    const int cp = threadIdx.x % DIF_CP;
+    const int64_t go = (int64_t)blockIdx.y * gstride;
+    z_in += go, z_out += go, x += go;
+    walk_rows<DifRows>(plan, rowinfo, sh, [=](auto scope, int32_t row, int2 ri) {
+        double2 acc = make_double2(0.0, 0.0);  // (A z)_row
+        for (int j = scope.first(); j < ri.y; j += scope.stride) {
+            const double2 zv = dif_ld2(z_in, col[ri.x + j], cp);
+            acc.x += zv.x;
+            acc.y += zv.y;
+        }
+        acc = scope.sum(acc);
+        if (!scope.owner()) return;
+        const double2 zu = dif_ld2(z_in, row, cp);
+        const double su = s[row];
+        const double2 v = make_double2(c * (su * (acc.x + zu.x)), c * (su * (acc.y + zu.y)));
+        double2 xu = dif_ld2(x, row, cp);
+        xu.x += v.x;
+        xu.y += v.y;
+        dif_st2(x, row, cp, xu);
+        dif_st2(z_out, row, cp, make_double2(su * v.x, su * v.y));
+    });
+}
+
+__global__ void __launch_bounds__(256) k_heat_mass(const int2 *__restrict__ rowinfo, int64_t n, DifCtl *ctl, const double *__restrict__ x,
+                                                    double *part, int64_t gstride, int64_t pstride) {
+    __shared__ double2 sh[4 * DIF_CP];
+    const int t = threadIdx.x, cp = t % DIF_CP;
+    ctl += blockIdx.y, x += (int64_t)blockIdx.y * gstride, part += (int64_t)blockIdx.y * pstride;
+    double2 acc = make_double2(0.0, 0.0);
+    const int64_t total = n * DIF_CP;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + t; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t node = e / DIF_CP;
+        const double rn = sqrt((double)rowinfo[node].y + 1.0);
+        const double2 xv = dif_ld2(x, node, cp);
+        acc.x += rn * xv.x;
+        acc.y += rn * xv.y;
+    }
+    acc = block_sum<DIF_CP>(acc, sh);
+    if (t < DIF_CP) dif_store_partial(part, blockIdx.x, acc);
+    if (!last_arriver(&ctl->ticket, (unsigned)gridDim.x)) return;
+    const double2 a = dif_close_partials(part, gridDim.x, sh);
+    if (t < DIF_CP) {
+        for (int h = 0; h < 2; ++h) {
+            const int k = 2 * t + h;
+            const int32_t j = ctl->src[k];
+            ctl->resid[k] = j >= 0 ? sqrt((double)rowinfo[j].y + 1.0) - (h ? a.y : a.x) : 0.0;
+        }
+    }
+    if (t == 0) __hip_atomic_store(&ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- selection ---------------------------------------------------------------------------------------------------------------------
 // fp64 -> uint64 in the order of the values (-0.0 below +0.0; the solve never produces it)
 __host__ __device__ inline uint64_t dif_key(double v) {
@@ -426,10 +513,28 @@ struct DifSparse {  // the caller's buffers of dcr_diffusion_sparsify; mode 0: t
     int64_t nnz;  // out: entries of all columns, also where they did not fit
 };
 
+struct HeatPlan {  // the heat solve of a call: t and the number of terms after the first
+    double t;
+    int64_t K;
+};
+
+// K of the heat kernel: the smallest K whose tail ρ_K = Σ_{k > K} θ_k is <= tol / 2, or max_terms where that is lower.  θ_k by its
+// recurrence until it has underflowed to zero (t <= 256: within 2,000 terms); the tail is the sum of its terms, small end first,
+// never 1 - the partial sum, which could say nothing below 2^-53.
+static int64_t heat_terms(double t, double tol, int64_t max_terms) {
+    std::vector<double> theta;
+    for (double th = std::exp(-t); th > 0.0 && theta.size() < 65536; th *= t / (double)theta.size()) theta.push_back(th);
+    int64_t K = (int64_t)theta.size() - 1;  // nothing above it is left to add
+    double tail = 0.0;                      // ρ_K
+    while (K > 0 && tail + theta[(size_t)K] <= 0.5 * tol) tail += theta[(size_t)K--];
+    return std::min(K, max_terms);
+}
+
 // sources NULL: column i is node i.  dense: host [P][n], or NULL with `sp` set.  Up to DIF_MAX_GROUPS batches go through the same
 // launches as blockIdx.y, each with its own vectors, partials and control block: a column's arithmetic is that of a batch alone.
-static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_diffusion_opts &o, double *dense, DifSparse *sp,
-                             double *out_residual, int32_t *out_steps) {
+// heat NULL: the PageRank solve with `o`; else the heat kernel's partial sum, out_residual takes the deficits and `o` plays no part.
+static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_diffusion_opts &o, const HeatPlan *heat,
+                             double *dense, DifSparse *sp, double *out_residual, int32_t *out_steps) {
     const int64_t n = g->n;
     RowPlan plan;
     DCR_TRY(build_row_plan(g, &plan, nullptr));
@@ -444,7 +549,7 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
     DCR_TRY(dev_regrow(&A.dif_vec, &A.dif_vec_cap, n + groups * gstride));
     DCR_TRY(dev_regrow(&A.dif_part, &A.dif_part_cap, groups * pstride));
     DCR_TRY(dev_regrow(&A.dif_ctl, &A.dif_ctl_cap, (int64_t)sizeof(DifCtl) * groups));
-    // per group z, p, r, x, q (16-byte aligned each), then the scale once
+    // per group z, p, r, x, q (16-byte aligned each), then the scale once; the heat kernel has z by turns in z and p, and x
     double *z = A.dif_vec, *p = z + n * DIF_B, *r = p + n * DIF_B, *x = r + n * DIF_B, *q = x + n * DIF_B;
     double *s = A.dif_vec + groups * gstride;
     DifCtl *ctl = reinterpret_cast<DifCtl *>(A.dif_ctl);
@@ -478,23 +583,32 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
         }
         DCR_HIP(hipMemcpyAsync(ctl, h.data(), sizeof(DifCtl) * (size_t)ng, hipMemcpyHostToDevice, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));  // h is reused below
-        hipLaunchKernelGGL(k_dif_start, grid_el, dim3(256), 0, g->stream, s, n, ctl, z, p, r, x, gstride);
-        for (int64_t step = 0; step < o.max_steps; ++step) {
-            hipLaunchKernelGGL(k_dif_matvec<0>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, p, z, s, q, ctl, A.dif_part, gstride,
+        if (heat) {
+            hipLaunchKernelGGL(k_heat_start, grid_el, dim3(256), 0, g->stream, s, n, ctl, std::exp(-heat->t), z, x, gstride);
+            double *z_in = z, *z_out = p;
+            for (int64_t k = 0; k < heat->K; ++k, std::swap(z_in, z_out))
+                hipLaunchKernelGGL(k_heat_term, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, z_in, s, heat->t / (double)(k + 1),
+                                   z_out, x, gstride);
+            hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo, n, ctl, x, A.dif_part, gstride, pstride);
+        } else {
+            hipLaunchKernelGGL(k_dif_start, grid_el, dim3(256), 0, g->stream, s, n, ctl, z, p, r, x, gstride);
+            for (int64_t step = 0; step < o.max_steps; ++step) {
+                hipLaunchKernelGGL(k_dif_matvec<0>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, p, z, s, q, ctl, A.dif_part, gstride,
+                                   pstride);
+                hipLaunchKernelGGL(k_dif_update, grid_el, dim3(256), 0, g->stream, n, ctl, p, q, x, r, A.dif_part, gstride, pstride);
+                hipLaunchKernelGGL(k_dif_direction, grid_el, dim3(256), 0, g->stream, n, ctl, s, r, p, z, gstride);
+                if ((step + 1) % SP_CHECK_EVERY != 0 && step + 1 != o.max_steps) continue;
+                DCR_HIP(hipGetLastError());
+                DCR_HIP(hipMemcpyAsync(h.data(), ctl, sizeof(DifCtl) * (size_t)ng, hipMemcpyDeviceToHost, g->stream));
+                DCR_HIP(hipStreamSynchronize(g->stream));
+                int active = 0;
+                for (int i = 0; i < ng; ++i) active += h[(size_t)i].active;
+                if (active == 0) break;
+            }
+            hipLaunchKernelGGL(k_dif_scale_x, grid_el, dim3(256), 0, g->stream, n, s, x, z, gstride);
+            hipLaunchKernelGGL(k_dif_matvec<1>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, x, z, s, q, ctl, A.dif_part, gstride,
                                pstride);
-            hipLaunchKernelGGL(k_dif_update, grid_el, dim3(256), 0, g->stream, n, ctl, p, q, x, r, A.dif_part, gstride, pstride);
-            hipLaunchKernelGGL(k_dif_direction, grid_el, dim3(256), 0, g->stream, n, ctl, s, r, p, z, gstride);
-            if ((step + 1) % SP_CHECK_EVERY != 0 && step + 1 != o.max_steps) continue;
-            DCR_HIP(hipGetLastError());
-            DCR_HIP(hipMemcpyAsync(h.data(), ctl, sizeof(DifCtl) * (size_t)ng, hipMemcpyDeviceToHost, g->stream));
-            DCR_HIP(hipStreamSynchronize(g->stream));
-            int active = 0;
-            for (int i = 0; i < ng; ++i) active += h[(size_t)i].active;
-            if (active == 0) break;
         }
-        hipLaunchKernelGGL(k_dif_scale_x, grid_el, dim3(256), 0, g->stream, n, s, x, z, gstride);
-        hipLaunchKernelGGL(k_dif_matvec<1>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, x, z, s, q, ctl, A.dif_part, gstride,
-                           pstride);
         if (sp) hipLaunchKernelGGL(k_dif_select, grid_col, dim3(256), 0, g->stream, x, n, ctl, sp->mode, kk, gstride);
         DCR_HIP(hipGetLastError());
         DCR_HIP(hipMemcpyAsync(h.data(), ctl, sizeof(DifCtl) * (size_t)ng, hipMemcpyDeviceToHost, g->stream));
@@ -547,12 +661,44 @@ static int diffusion_opts(const dcr_diffusion_opts *opts, dcr_diffusion_opts *o)
     return DCR_OK;
 }
 
+static int heat_opts(const dcr_heat_opts *opts, dcr_heat_opts *o) {
+    *o = {5.0, 1e-10, 4096};
+    if (opts) *o = *opts;
+    if (!(o->t > 0.0 && o->t <= 256.0)) DCR_FAIL(DCR_EINVAL, "t must lie in (0, 256]");
+    if (!(o->tol >= 0.0) || o->max_terms < 1) DCR_FAIL(DCR_EINVAL, "tol must be >= 0, max_terms >= 1");
+    return DCR_OK;
+}
+
 static int diffusion_sources(const dcr_graph *g, const int32_t *sources, int64_t P) {
     if (P < 0) DCR_FAIL(DCR_EINVAL, "the number of sources must be >= 0");
     if (!sources && P != g->n) DCR_FAIL(DCR_EINVAL, "sources NULL stands for all nodes: P must be num_nodes");
     for (int64_t i = 0; sources && i < P; ++i)
         if (sources[i] < 0 || sources[i] >= g->n) DCR_FAIL(DCR_EINVAL, "source " + std::to_string(i) + " outside 0 .. num_nodes - 1");
     return DCR_OK;
+}
+
+// what dcr_diffusion_sparsify and dcr_heat_sparsify share once their options are read: the remaining argument checks, the
+// capacity of a top-k call, the solve and selection
+static int sparsify_call(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_diffusion_opts &o, const HeatPlan *heat, DifSparse *sp,
+                         double *out_residual, int32_t *out_steps, int64_t *out_nnz) {
+    if (sp->cap < 0 || (sp->cap > 0 && (!sp->row || !sp->weight || !sp->value)))
+        DCR_FAIL(DCR_EINVAL, "cap entries of row, weight and value are needed");
+    if (sp->mode != 0 && sp->mode != 1) DCR_FAIL(DCR_EINVAL, "mode must be 0 (top-k) or 1 (threshold)");
+    if (sp->mode == 0 && sp->k < 1) DCR_FAIL(DCR_EINVAL, "k must be >= 1");
+    if (sp->mode == 1 && !(sp->eps == sp->eps)) DCR_FAIL(DCR_EINVAL, "eps must not be NaN");
+    DCR_TRY(diffusion_sources(g, sources, P));
+    if (P == 0) return DCR_OK;
+    if (sp->mode == 0) {  // the size is known before any solve
+        const int64_t need = P * std::min<int64_t>(sp->k, g->n);
+        if (need > sp->cap) {
+            *out_nnz = need;
+            DCR_FAIL(DCR_ECAPACITY, "diffusion: " + std::to_string(need) + " entries kept, room for " + std::to_string(sp->cap));
+        }
+    }
+    DCR_HIP(hipSetDevice(g->device));
+    const int rc = diffusion_batches(g, sources, P, o, heat, nullptr, sp, out_residual, out_steps);
+    if (rc == DCR_OK || rc == DCR_ECAPACITY) *out_nnz = sp->nnz;
+    return rc;
 }
 
 }  // namespace dcr
@@ -569,32 +715,42 @@ int dcr_ppr_columns(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_d
     DCR_TRY(diffusion_sources(g, sources, P));
     if (P == 0) return DCR_OK;
     DCR_HIP(hipSetDevice(g->device));
-    return diffusion_batches(g, sources, P, o, out, nullptr, out_residual, out_steps);
+    return diffusion_batches(g, sources, P, o, nullptr, out, nullptr, out_residual, out_steps);
 }
 
 int dcr_diffusion_sparsify(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_diffusion_opts *opts, int mode, int64_t k, double eps,
                            int64_t *out_ptr, int64_t cap, int32_t *out_row, double *out_weight, double *out_value, double *out_residual,
                            int32_t *out_steps, int64_t *out_nnz) {
     if (!g || !out_ptr || !out_residual || !out_nnz) DCR_FAIL(DCR_EINVAL, "null argument");
-    if (cap < 0 || (cap > 0 && (!out_row || !out_weight || !out_value))) DCR_FAIL(DCR_EINVAL, "cap entries of row, weight and value are needed");
     dcr_diffusion_opts o;
     DCR_TRY(diffusion_opts(opts, &o));
-    if (mode != 0 && mode != 1) DCR_FAIL(DCR_EINVAL, "mode must be 0 (top-k) or 1 (threshold)");
-    if (mode == 0 && k < 1) DCR_FAIL(DCR_EINVAL, "k must be >= 1");
-    if (mode == 1 && !(eps == eps)) DCR_FAIL(DCR_EINVAL, "eps must not be NaN");
+    DifSparse sp = {mode, k, eps, out_ptr, cap, out_row, out_weight, out_value, 0};
+    return sparsify_call(g, sources, P, o, nullptr, &sp, out_residual, out_steps, out_nnz);
+}
+
+int dcr_heat_columns(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_heat_opts *opts, double *out, double *out_deficit,
+                     int64_t *out_terms) {
+    if (!g || !sources || !out || !out_deficit) DCR_FAIL(DCR_EINVAL, "null argument");
+    dcr_heat_opts o;
+    DCR_TRY(heat_opts(opts, &o));
     DCR_TRY(diffusion_sources(g, sources, P));
     if (P == 0) return DCR_OK;
-    DifSparse sp = {mode, k, eps, out_ptr, cap, out_row, out_weight, out_value, 0};
-    if (mode == 0) {  // the size is known before any solve
-        const int64_t need = P * std::min<int64_t>(k, g->n);
-        if (need > cap) {
-            *out_nnz = need;
-            DCR_FAIL(DCR_ECAPACITY, "diffusion: " + std::to_string(need) + " entries kept, room for " + std::to_string(cap));
-        }
-    }
+    const HeatPlan heat = {o.t, heat_terms(o.t, o.tol, o.max_terms)};
+    if (out_terms) *out_terms = heat.K;
     DCR_HIP(hipSetDevice(g->device));
-    const int rc = diffusion_batches(g, sources, P, o, nullptr, &sp, out_residual, out_steps);
-    if (rc == DCR_OK || rc == DCR_ECAPACITY) *out_nnz = sp.nnz;
+    return diffusion_batches(g, sources, P, {}, &heat, out, nullptr, out_deficit, nullptr);
+}
+
+int dcr_heat_sparsify(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_heat_opts *opts, int mode, int64_t k, double eps,
+                      int64_t *out_ptr, int64_t cap, int32_t *out_row, double *out_weight, double *out_value, double *out_deficit,
+                      int64_t *out_terms, int64_t *out_nnz) {
+    if (!g || !out_ptr || !out_deficit || !out_nnz) DCR_FAIL(DCR_EINVAL, "null argument");
+    dcr_heat_opts o;
+    DCR_TRY(heat_opts(opts, &o));
+    const HeatPlan heat = {o.t, heat_terms(o.t, o.tol, o.max_terms)};
+    DifSparse sp = {mode, k, eps, out_ptr, cap, out_row, out_weight, out_value, 0};
+    const int rc = sparsify_call(g, sources, P, {}, &heat, &sp, out_deficit, nullptr, out_nnz);
+    if (out_terms && P > 0 && (rc == DCR_OK || rc == DCR_ECAPACITY)) *out_terms = heat.K;
     return rc;
 }
 

@@ -47,6 +47,11 @@ class DiffusionOpts(ctypes.Structure):
     _fields_ = [('alpha', _f64), ('tol', _f64), ('max_steps', _i64)]
 
 
+class HeatOpts(ctypes.Structure):
+    """dcr_heat_opts of include/dcr.h."""
+    _fields_ = [('t', _f64), ('tol', _f64), ('max_terms', _i64)]
+
+
 class FosrOpts(ctypes.Structure):
     """dcr_fosr_opts of include/dcr.h."""
     _fields_ = [('num_iterations', _i64), ('initial_power_iters', _i64), ('seed', ctypes.c_uint64)]
@@ -106,6 +111,9 @@ SIGNATURES = {
     'dcr_ppr_columns': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), _f64p, _f64p, _i32p]),
     'dcr_diffusion_sparsify': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), ctypes.c_int, _i64, _f64, _i64p, _i64, _i32p,
                                               _f64p, _f64p, _f64p, _i32p, _i64p]),
+    'dcr_heat_columns': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(HeatOpts), _f64p, _f64p, _i64p]),
+    'dcr_heat_sparsify': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(HeatOpts), ctypes.c_int, _i64, _f64, _i64p, _i64, _i32p, _f64p,
+                                         _f64p, _f64p, _i64p, _i64p]),
     'dcr_fosr_pick': (ctypes.c_int, [_vp, _f64p, _i32p, _i32p, _f64p, _f64p, ctypes.POINTER(ctypes.c_int)]),
     'dcr_fosr': (ctypes.c_int, [_vp, ctypes.POINTER(FosrOpts), _f64p, _i32p, _i32p, _i64p, _f64p]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),

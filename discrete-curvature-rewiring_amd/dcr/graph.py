@@ -478,7 +478,44 @@ class DcrGraph:
             return out, {'residual': residual, 'steps': steps, 'converged': converged}
         return out
 
-    def diffusion(self, alpha=0.15, k=None, eps=None, sources=None, return_info=False, tol=1e-10, max_steps=20000):
+    HEAT_MAX_TERMS = 4096   # the default of dcr_heat_opts
+
+    def _heat_converged(self, src, deficit, tol):
+        """deficit <= tol sqrt(deg_j + 1) per column; src None stands for all nodes."""
+        nodes = np.arange(self.num_nodes) if src is None else src
+        if nodes.size <= 64:
+            deg = np.array([self.degree(int(v)) for v in nodes], dtype=np.float64)
+        else:
+            deg = np.bincount(np.concatenate(self.edges()), minlength=self.num_nodes).astype(np.float64)[nodes]
+        return deficit <= float(tol) * np.sqrt(deg + 1.0)
+
+    def heat(self, sources, t=5.0, tol=1e-10, max_terms=None, return_info=False):
+        """Columns of the heat-kernel matrix ``S = exp(-t (I - D~^-1/2 (A + I) D~^-1/2))`` of the live graph (``D~ = D + I``,
+        ``0 < t <= 256``; include/dcr.h has the definition), as float64 ``[len(sources), n]``: row ``i`` is the Taylor partial sum
+        ``e^-t sum_{k <= K} t^k / k! H^k e_j`` of column ``sources[i]``, with ``K`` the smallest count whose tail
+        ``sum_{k > K} e^-t t^k / k!`` is at most ``tol / 2`` (``max_terms`` where that is lower; default 4096).  Every term is
+        non-negative, so the result is an entrywise lower bound of ``S``.  ``return_info``: also a dict of ``deficit`` (float64,
+        ``sqrt(deg_j + 1) - sum_i sqrt(deg_i + 1) x_i``: ``0 <= S_ij - x_i <= deficit / sqrt(deg_i + 1)``), ``terms`` (``K``) and
+        ``converged`` (bool: ``deficit <= tol sqrt(deg_j + 1)``).  ``RuntimeWarning`` when the sum was cut short; ``ValueError`` on
+        a source outside the graph or ``t`` outside (0, 256]."""
+        if not 0.0 < float(t) <= 256.0:
+            raise ValueError('t must lie in (0, 256]')
+        src = self._sources(sources)
+        P = src.shape[0]
+        max_terms = self.HEAT_MAX_TERMS if max_terms is None else int(max_terms)
+        out = np.empty((P, self.num_nodes), dtype=np.float64)
+        deficit, terms = np.empty(P, dtype=np.float64), ctypes.c_int64(0)
+        opts = _lib.HeatOpts(float(t), float(tol), max_terms)
+        check(lib().dcr_heat_columns(self._h, src.ctypes.data_as(_lib._i32p), P, ctypes.byref(opts), out.ctypes.data_as(_lib._f64p),
+                                     deficit.ctypes.data_as(_lib._f64p), ctypes.byref(terms)))
+        converged = self._heat_converged(src, deficit, tol)
+        self._warn_unconverged('heat', converged, deficit, tol, terms.value)
+        if return_info:
+            return out, {'deficit': deficit, 'terms': int(terms.value), 'converged': converged}
+        return out
+
+    def diffusion(self, alpha=0.15, k=None, eps=None, sources=None, return_info=False, tol=1e-10, max_steps=20000, kernel='ppr', t=5.0,
+                  max_terms=None):
         """The sparsified personalised-PageRank matrix of the live graph (DIGL / GDC): per column ``j`` of ``S`` (``ppr``) either
         the ``k`` largest entries (larger value first, among equal bits the smaller node id first; everything where ``k >= n``)
         or the entries ``>= eps``, as the reference's ``get_top_k_matrix`` / ``get_clipped_matrix``
@@ -488,13 +525,25 @@ class DcrGraph:
 
         Returns ``(edge_index, weight)``: int64 ``[2, nnz]`` holding ``[i; j]`` and float64 ``[nnz]``, grouped by column in the
         order of ``sources`` and by ``i`` ascending within a column.  ``return_info``: also a dict of ``value`` (the raw
-        ``S_ij``), ``ptr`` (int64 ``[columns + 1]``), ``residual``, ``steps`` and ``converged`` per column as ``ppr`` has them."""
+        ``S_ij``), ``ptr`` (int64 ``[columns + 1]``), ``residual``, ``steps`` and ``converged`` per column as ``ppr`` has them.
+
+        ``kernel='heat'``: ``S`` is the heat-kernel matrix of ``heat`` at ``t`` (``tol``, ``max_terms`` as there; ``alpha`` and
+        ``max_steps`` are not used) and the dict holds ``deficit`` and ``terms`` as ``heat`` has them in place of ``residual`` and
+        ``steps``.  Any other ``kernel`` than ``'ppr'`` and ``'heat'`` is a ``ValueError``."""
+        if kernel not in ('ppr', 'heat'):
+            raise ValueError("kernel must be 'ppr' or 'heat'")
+        heat = kernel == 'heat'
         if (k is None) == (eps is None):
             raise ValueError('exactly one of k and eps must be given')
         n = self.num_nodes
         src = None if sources is None else self._sources(sources)
         P = n if src is None else src.shape[0]
-        opts = _lib.DiffusionOpts(float(alpha), float(tol), int(max_steps))
+        if heat:
+            opts = _lib.HeatOpts(float(t), float(tol), self.HEAT_MAX_TERMS if max_terms is None else int(max_terms))
+            call, terms = lib().dcr_heat_sparsify, ctypes.c_int64(0)
+        else:
+            opts = _lib.DiffusionOpts(float(alpha), float(tol), int(max_steps))
+            call = lib().dcr_diffusion_sparsify
         mode = 0 if eps is None else 1
         if mode == 0 and int(k) < 1:
             raise ValueError('k must be >= 1')
@@ -511,12 +560,11 @@ class DcrGraph:
             nnz = ctypes.c_int64()
             part_src = np.arange(first, first + count, dtype=np.int32) if src is None else src[first:first + count]
             whole = src is None and count == n
-            check(lib().dcr_diffusion_sparsify(self._h, None if whole else part_src.ctypes.data_as(_lib._i32p), count, ctypes.byref(opts),
-                                               mode, int(k) if mode == 0 else 0, float(eps) if mode == 1 else 0.0,
-                                               part_ptr.ctypes.data_as(_lib._i64p), cap, row.ctypes.data_as(_lib._i32p),
-                                               weight.ctypes.data_as(_lib._f64p), value.ctypes.data_as(_lib._f64p),
-                                               residual[first:].ctypes.data_as(_lib._f64p), steps[first:].ctypes.data_as(_lib._i32p),
-                                               ctypes.byref(nnz)))
+            check(call(self._h, None if whole else part_src.ctypes.data_as(_lib._i32p), count, ctypes.byref(opts),
+                       mode, int(k) if mode == 0 else 0, float(eps) if mode == 1 else 0.0,
+                       part_ptr.ctypes.data_as(_lib._i64p), cap, row.ctypes.data_as(_lib._i32p),
+                       weight.ctypes.data_as(_lib._f64p), value.ctypes.data_as(_lib._f64p), residual[first:].ctypes.data_as(_lib._f64p),
+                       ctypes.byref(terms) if heat else steps[first:].ctypes.data_as(_lib._i32p), ctypes.byref(nnz)))
             ptr[first + 1:first + count + 1] = ptr[first] + part_ptr[1:]
             rows.append(row[:nnz.value])
             weights.append(weight[:nnz.value])
@@ -526,6 +574,12 @@ class DcrGraph:
         value = np.concatenate(values) if values else np.empty(0, dtype=np.float64)
         cols = np.arange(n, dtype=np.int64) if src is None else src.astype(np.int64)
         edge_index = np.stack([row.astype(np.int64), np.repeat(cols, np.diff(ptr))])
+        if heat:
+            converged = self._heat_converged(src, residual, tol)
+            self._warn_unconverged('diffusion', converged, residual, tol, terms.value)
+            if return_info:
+                return edge_index, weight, {'value': value, 'ptr': ptr, 'deficit': residual, 'terms': int(terms.value), 'converged': converged}
+            return edge_index, weight
         converged = residual <= float(tol) * float(alpha)
         self._warn_unconverged('diffusion', converged, residual, tol, max_steps)
         if return_info:

@@ -334,6 +334,38 @@ int dcr_diffusion_sparsify(dcr_graph *g, const int32_t *sources /* NULL = all no
                            double *out_value, double *out_residual /* host [P] */, int32_t *out_steps /* host [P] or NULL */,
                            int64_t *out_nnz);
 
+/* ---- Heat-kernel diffusion, GDC's other kernel (csrc/dcr_diffusion.hip; upstream's get_heat_matrix, which the reference did not
+ * take over) ---------------------------------------------------------------------------------------------------------------------
+ * With A~, d~ = deg + 1, s~ = 1 / sqrt(d~), r = sqrt(d~) and H = D~^-1/2 A~ D~^-1/2 of the live graph as above, and 0 < t <= 256:
+ * S = exp(-t (I - H)) = sum_k theta_k H^k with theta_k = e^-t t^k / k!.  Column j is computed as the partial sum
+ * x = sum_{k = 0 .. K} theta_k H^k e_j by the recurrence
+ *   v_0 = e^-t e_j;   v_{k+1} = (t / (k + 1)) s~ ⊙ ((A + I)(s~ ⊙ v_k));   x += v_{k+1}
+ * 16 columns at a time, one launch a term.  K is chosen on the host before any launch: the smallest K whose tail
+ * rho_K = sum_{k > K} theta_k, added term by term, is <= tol / 2; or max_terms where that is lower: the call is then still DCR_OK
+ * and the deficit says that the sum was cut short.  Nothing on the device decides when to stop and the host reads nothing back
+ * between terms.  An isolated node has H_jj = 1 and S_jj = 1.
+ * Every term is non-negative, so nothing cancels and x <= S_j entrywise; H r = r, so the mass that x lacks is known exactly:
+ *   out_deficit  host double [P]: r_j - sum_i r_i x_i, in exact arithmetic r_j rho_K >= 0.  0 <= S_ij - x_i <= out_deficit / r_i
+ *                for every i.  A column has converged when it is <= tol r_j.
+ *   out_terms    one host int64 or NULL: K, the same for every column of the call.
+ *   dcr_heat_columns   out: host double [P][num_nodes], row i = the partial sum of column sources[i] of S.
+ *   dcr_heat_sparsify  the selection of dcr_diffusion_sparsify on these columns: mode, k, eps, out_ptr, cap, out_row, out_weight,
+ *                      out_value, out_nnz, DCR_ECAPACITY and the counting call are as stated there.
+ * opts NULL = defaults: t 5.0, tol 1e-10, max_terms 4096.  fp64 without floating-point atomics, every sum in an order the graph
+ * alone fixes: the bits of a column depend on its source, t and K only, not on its place in the call, on the other columns or on
+ * how many batches share a launch.  READ-ONLY on the graph, on the graph's stream, synchronous on return; the work buffers are
+ * those of the PageRank solve.
+ * Null g, out, out_ptr, out_deficit, out_nnz (sources too in dcr_heat_columns); t outside (0, 256] or NaN; tol negative or NaN;
+ * max_terms < 1; and what dcr_diffusion_sparsify rejects in P, sources, mode, k, eps and cap: DCR_EINVAL before any device call.
+ * P == 0: DCR_OK, nothing written. */
+typedef struct { double t, tol; int64_t max_terms; } dcr_heat_opts;
+int dcr_heat_columns(dcr_graph *g, const int32_t *sources, int64_t P, const dcr_heat_opts *opts /* NULL = defaults */,
+                     double *out /* host [P][n] */, double *out_deficit /* host [P] */, int64_t *out_terms /* one, or NULL */);
+int dcr_heat_sparsify(dcr_graph *g, const int32_t *sources /* NULL = all nodes */, int64_t P,
+                      const dcr_heat_opts *opts /* NULL = defaults */, int mode /* 0 top-k, 1 threshold */, int64_t k, double eps,
+                      int64_t *out_ptr /* host [P + 1] */, int64_t cap, int32_t *out_row, double *out_weight, double *out_value,
+                      double *out_deficit /* host [P] */, int64_t *out_terms /* one, or NULL */, int64_t *out_nnz);
+
 /* ---- FoSR, first-order spectral rewiring (csrc/dcr_fosr.hip; Karhadkar, Banerjee, Montufar, ICLR 2023; no counterpart in the
  * reference) ------------------------------------------------------------------------------------------------------------------
  * Adds, one at a time, the edge that raises the spectral gap most to first order.  With deg the current degrees, r = sqrt(deg),
