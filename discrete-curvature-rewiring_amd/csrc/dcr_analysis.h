@@ -1,5 +1,5 @@
 // What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
-// dcr_diffusion.hip, dcr_fosr.hip) and the
+// dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
 // dcr_graph.hip stay as they are.
@@ -208,6 +208,14 @@ struct AnalysisState {
     int64_t fsr_part_cap = 0;
     unsigned char *fsr_ctl = nullptr;  // tickets and the result block (FsrCtl of dcr_fosr.hip)
     int64_t fsr_ctl_cap = 0;
+
+    // hop distances (dcr_hops.hip): O(n W) words, W <= 4 the words of a batch of 64 W sources; O(64 W n) only where rows are asked for
+    uint64_t *hop_bits = nullptr;   // visited, frontier, next as [n][W] each
+    int64_t hop_bits_cap = 0;
+    unsigned char *hop_ctl = nullptr;  // the batch's running totals [256] (64-bit), then its sources [256]
+    int64_t hop_ctl_cap = 0;
+    int32_t *hop_dist = nullptr;    // [64 W][n] distance rows of a batch
+    int64_t hop_dist_cap = 0;
 
     void release();  // frees every buffer
 };

@@ -627,6 +627,35 @@ class DcrGraph:
         edges = np.stack([u[:added.value], v[:added.value]]).astype(np.int64)
         return (edges, x) if return_vector else edges
 
+    # ---- hop distances (csrc/dcr_hops.hip) ------------------------------------------------
+    def _hops(self, sources, max_hops, want_dist):
+        src = None if sources is None else self._sources(sources)
+        P = self.num_nodes if src is None else src.shape[0]
+        if max_hops is not None and not 0 <= int(max_hops) < 2 ** 31:
+            raise ValueError('max_hops must be None or lie in 0 .. 2^31 - 1')
+        opts = _lib.HopsOpts(-1 if max_hops is None else int(max_hops))
+        dist = np.empty((P, self.num_nodes), dtype=np.int32) if want_dist else None
+        ecc, reached, total = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int64), np.empty(P, dtype=np.int64)
+        check(lib().dcr_hop_distances(self._h, None if src is None else src.ctypes.data_as(_lib._i32p), P, ctypes.byref(opts),
+                                      dist.ctypes.data_as(_lib._i32p) if want_dist else None, ecc.ctypes.data_as(_lib._i32p),
+                                      reached.ctypes.data_as(_lib._i64p), total.ctypes.data_as(_lib._i64p)))
+        return dist, ecc, reached, total
+
+    def hop_distances(self, sources, max_hops=None):
+        """Hop distances on the live graph as int32 ``[len(sources), n]``: row ``i`` holds the number of edges of a shortest path
+        from ``sources[i]`` to every node, ``-1`` where there is none (another component) or it is longer than ``max_hops``.
+        Breadth-first search on the device, up to 256 sources a sweep of the adjacency (include/dcr.h has the rule), read-only on
+        the graph; the rows come back a batch at a time, so the returned array is the only ``P x n`` object.  Duplicated sources
+        are legal.  ``ValueError`` on a source outside the graph."""
+        return self._hops(sources, max_hops, True)[0]
+
+    def hop_summary(self, sources=None, max_hops=None):
+        """``(ecc, reached, total)`` per source (int32, int64, int64 ``[len(sources)]``; ``sources=None``: every node): the
+        largest distance reached, the number of nodes within ``max_hops`` (the source included: the ball size; the component's
+        size without a limit) and the sum of their distances.  An isolated source gives ``(0, 1, 0)``, and so does every source at
+        ``max_hops=0``.  The search of ``hop_distances`` without its rows: no distance row exists on either side."""
+        return self._hops(sources, max_hops, False)[1:]
+
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):
         check(lib().dcr_profile_reset(self._h))

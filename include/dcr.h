@@ -408,6 +408,36 @@ int dcr_fosr_pick(dcr_graph *g, const double *x /* host [n] */, int32_t *out_u, 
 int dcr_fosr(dcr_graph *g, const dcr_fosr_opts *opts, const double *x0 /* host [n] or NULL */, int32_t *out_u,
              int32_t *out_v /* host [num_iterations] */, int64_t *out_added, double *out_x /* host [n] or NULL */);
 
+/* ---- hop distances, eccentricities and ball sizes (csrc/dcr_hops.hip; no counterpart in the reference) ----------------------
+ * d(s, v) is the number of edges of a shortest path from s to v in the live graph, unweighted and undirected: d(s, s) = 0, and
+ * level L = 1, 2, ... holds the nodes that have a neighbour at level L - 1 and are in no earlier level.  With a hop limit H
+ * (max_hops >= 0) the levels stop at H.  Per source s, over the nodes its levels hold (s itself included, at distance 0):
+ *   out_dist     host int32 [P][num_nodes] or NULL: row i holds d(sources[i], v); -1 where v was not reached (another
+ *                component, or beyond max_hops).  Without it no distance row exists anywhere.
+ *   out_ecc      host int32 [P] or NULL: the largest distance reached, the last level that holds a node.  0 for an isolated source.
+ *   out_reached  host int64 [P] or NULL: the nodes at distance <= max_hops, the source included: the ball size |B_H(s)|; the size
+ *                of the source's component where there is no limit.
+ *   out_total    host int64 [P] or NULL: the sum of the distances of those nodes.
+ * An isolated source gives ecc 0, reached 1, total 0, and so does every source at max_hops = 0.
+ * Breadth-first search from 64 W sources at a time (W = 1, 2 or 4: the narrowest that holds what is left of the call, so a call
+ * of up to 64 sources runs at W = 1 and a long one 256 sources a sweep): every node carries one bit per
+ * source in W 64-bit words, one sweep of the live adjacency advances every source of the batch by one hop, and the host reads
+ * the 64 W per-source counts once per level and stops when all are zero.  Duplicated sources are legal, each is a source of its
+ * own.  sources NULL stands for every node in order, and P must then be num_nodes.  All arithmetic is integer: a source's outputs
+ * are the same bits whatever else is in the call and wherever in it the source stands.
+ * READ-ONLY on the graph, runs on the graph's stream and is synchronous on return; 24 W num_nodes bytes of work buffers, and
+ * 256 W num_nodes more where out_dist is given, stay on the handle until dcr_graph_destroy.  No num_nodes x num_nodes buffer
+ * exists on the device.
+ * Null g; P < 0; sources NULL with P != num_nodes; a source outside 0 .. num_nodes - 1: DCR_EINVAL before any device call.
+ * P == 0: DCR_OK, nothing written.  More levels than nodes (a corrupted graph): DCR_ESTATE. */
+typedef struct { int32_t max_hops; /* < 0: no limit */ } dcr_hops_opts;
+int dcr_hop_distances(dcr_graph *g, const int32_t *sources /* NULL = every node, P must then be n */, int64_t P,
+                      const dcr_hops_opts *opts /* NULL = no limit */,
+                      int32_t *out_dist    /* host [P][n] or NULL; -1 = not reached (other component, or beyond max_hops) */,
+                      int32_t *out_ecc     /* host [P]: largest distance reached */,
+                      int64_t *out_reached /* host [P]: nodes at distance <= max_hops, the source included */,
+                      int64_t *out_total   /* host [P]: sum of the distances of those nodes */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
