@@ -42,6 +42,7 @@ def one(ei, n, mode):
 
 def run(seed=1, seconds=300.0, verbose=True):
     rng = np.random.Generator(np.random.PCG64(seed))
+    kind_rng = np.random.Generator(np.random.PCG64(seed + 0x7261))   # its own stream: the graphs and edits of a seed stay what they were
     t_end = time.time() + seconds
     graphs = values = 0
     while time.time() < t_end:
@@ -56,17 +57,21 @@ def run(seed=1, seconds=300.0, verbose=True):
             assert np.array_equal(hu, eu) and np.array_equal(hv, ev) and bad.size == 0, (mode, n, E, bad[:5], hc[bad[:5]], ref[bad[:5]])
             values += hc.shape[0]
             H.close()
-        # a few edits among the first nodes (the hubs of every family here), an incremental pass, against a full one
+        # a few edits among the first nodes (the hubs of every family here), an incremental pass, against a full one: of Balanced
+        # Forman or of a triangle kind (then on top of a full pass of that kind: a pass of another kind than the last is a full one)
         os.environ.pop('DCR_NC_FINE_FULL', None)
+        ict = ('bfc', 'augmented', 'haantjes')[int(kind_rng.integers(0, 3))]
+        if ict != 'bfc':
+            G.curvature_pass(ict)
         for _ in range(3):
             a, b = int(rng.integers(0, min(n, 50))), int(rng.integers(0, n))
             if a != b:
                 (G.remove_edge if G.has_edge(a, b) else G.add_edge)(a, b)
-        G.curvature_pass('bfc', incremental=True)
+        G.curvature_pass(ict, incremental=True)
         inc = G.curvature_read()[2].copy()
-        G.curvature_pass('bfc')
+        G.curvature_pass(ict)
         full = G.curvature_read()[2]
-        assert np.array_equal(inc.view(np.int64), full.view(np.int64)), ('incremental', n, E)
+        assert np.array_equal(inc.view(np.int64), full.view(np.int64)), ('incremental', ict, n, E)
         G.close()
         graphs += 1
         if verbose and graphs % 10 == 0:

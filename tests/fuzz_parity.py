@@ -51,6 +51,7 @@ def random_graph(rng, hub_prob):
 def run(seed=1, seconds=240.0, graphs=None, engines=('nc', 'edge', 'h2'), hub_prob=0.04, verbose=True):
     """Returns (graphs, edge values, SDRF runs) checked; raises AssertionError at the first difference."""
     rng = np.random.Generator(np.random.PCG64(seed))
+    kind_rng = np.random.Generator(np.random.PCG64(seed + 0x7261))   # its own stream: the graphs and edits of a seed stay what they were
     t_end = time.time() + seconds
     n_graphs = n_edges_checked = n_sdrf = 0
     while time.time() < t_end and (graphs is None or n_graphs < graphs):
@@ -70,8 +71,9 @@ def run(seed=1, seconds=240.0, graphs=None, engines=('nc', 'edge', 'h2'), hub_pr
                 assert np.array_equal(eu, ou) and np.array_equal(ev, ov) and bad.size == 0, \
                     (impl, ct, n, ei.shape, [(int(eu[i]), int(ev[i]), cv[i], oc[i]) for i in bad[:5]])
                 n_edges_checked += cv.shape[0]
-        # random edits + incremental passes
-        G.curvature_pass('bfc')
+        # random edits + incremental passes, of Balanced Forman or of a triangle kind (MODE_TRI of the same kernels)
+        ict = ('bfc', 'augmented', 'haantjes')[int(kind_rng.integers(0, 3))]
+        G.curvature_pass(ict)
         for step in range(12):
             u, v = (int(t) for t in rng.integers(0, n, 2))
             if u == v:
@@ -81,8 +83,8 @@ def run(seed=1, seconds=240.0, graphs=None, engines=('nc', 'edge', 'h2'), hub_pr
             else:
                 G.add_edge(u, v); C.add_edge(u, v)
             if step % 4 == 3:
-                G.curvature_pass('bfc', incremental=True)
-                assert np.array_equal(G.curvature_read()[2], C.curv_all('bfc', nthreads=8)[2]), ('incremental', n, step)
+                G.curvature_pass(ict, incremental=True)
+                assert np.array_equal(G.curvature_read()[2], C.curv_all(ict, nthreads=8)[2]), ('incremental', ict, n, step)
         # a short SDRF run through the public entry point
         if ei.shape[1] >= 4 and n <= 1500:
             ct = ('bfc', 'augmented', 'haantjes', '1d')[int(rng.integers(0, 4))]

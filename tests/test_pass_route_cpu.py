@@ -114,6 +114,34 @@ def test_grid_reaches_every_outcome(grid_plans):
     assert {p[3] < p[4] for _, p in grid_plans} == {False, True}      # two-hop against the class kernels
 
 
+@pytest.mark.parametrize('curv', [AUGMENTED, HAANTJES])
+def test_incremental_pass_of_a_triangle_kind(curv):
+    """The rows tests/test_tri_incremental_gpu.py relies on, stated as literals (not through rules()): an incremental pass of
+    'augmented' / 'haantjes' never takes the two-hop route, whatever DCR_PASS says short of 'edge'; goes edge by edge up to
+    DIRTY_EDITS pending edits and through the class kernels beyond; carries the hub supplement above NC_MAXD on both."""
+    n, E = 100000, 500000
+    sd2 = 40.0 * n                      # sparse: a full Balanced Forman pass of these facts is the two-hop engine's
+    assert library_plan(n, E, 2 * E, sd2, 300, 0, 0, True, None, None, BFC, False)[0] == TWO_HOP
+    for impl, pending, deg, fine_on, sweep, full in itertools.product(
+            (0, 2, 3), (0, 1, DIRTY_EDITS, DIRTY_EDITS + 1, 40), (62, H2_MAXDEG, NC_MAXD, NC_MAXD + 1, 17000), (True, False),
+            (None, 0, 1), (None, 0, 2 ** 40)):
+        case = (n, E, 2 * E, sd2, deg, pending, impl, fine_on, full, sweep, curv, True)
+        route, rows, hub = library_plan(*case)[:3]
+        assert route != TWO_HOP, case
+        assert route == (NC_EDGES if fine_on and pending <= DIRTY_EDITS else NC_CLASSES), case
+        assert hub == (deg > NC_MAXD), case
+        assert rows == (route == NC_EDGES and sweep == 0), case      # (2 E slots: below the 4 M of the automatic choice)
+        assert library_plan(*case) == rules(*case)
+    # by rows from 4 M slots where DCR_NC_FINE_SWEEP is unset; DCR_PASS=edge: the edge-centric kernels, no supplement
+    assert library_plan(n, E, 4000000, sd2, 300, 2, 0, True, None, None, curv, True)[:3] == (NC_EDGES, True, False)
+    assert library_plan(n, E, 3999999, sd2, 300, 2, 0, True, None, None, curv, True)[:3] == (NC_EDGES, False, False)
+    for pending, deg in ((1, 300), (9, 300), (1, NC_MAXD + 1)):
+        assert library_plan(n, E, 2 * E, sd2, deg, pending, 1, True, None, None, curv, True)[:3] == (EDGE_CENTRIC, False, False)
+    # a full pass of a triangle kind is never the two-hop engine's either (DCR_PASS=h2 included)
+    for impl in (0, 2, 3):
+        assert library_plan(n, E, 2 * E, sd2, 300, 0, impl, True, None, None, curv, False)[0] in (NC_CLASSES, NC_EDGES)
+
+
 def test_constants_are_those_of_the_sources():
     """The limits and guards this file's transcription uses, as the sources spell them: a changed constant is a diff here."""
     assert (H2_MAXDEG, NC_MAXD, DIRTY_EDITS) == (5000, 8190, 3)
