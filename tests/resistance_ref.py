@@ -1,8 +1,9 @@
 """Dense numpy restatement of what DcrGraph.effective_resistance computes (host only, graphs of a few thousand nodes at most):
 R(u, v) = (e_u - e_v)^T pinv(D - A) (e_u - e_v), the spectral gap lambda_1 of the normalised Laplacian by ``eigvalsh``, and the
 same conjugate-gradient iteration as csrc/dcr_resistance.hip, column by column: on L' = I - D^-1/2 A D^-1/2 with
-c = s_u e_u - s_v e_v from y = 0, returning ``lower = 2 c.y - y.L'y`` and the true residual ``|c - L'y|``.  Nothing here imports the
-package under test."""
+c = s_u e_u - s_v e_v from y = 0, returning ``lower = 2 c.y - y.L'y`` and the true residual ``|c - L'y|``.  For tens of thousands
+of nodes: ``sparse_resistance`` (grounded Laplacian, sparse LU) and ``lambda1_lower`` (shift-invert Lanczos).  Nothing here imports
+the package under test."""
 import numpy as np
 
 EPS = 2.0 ** -52
@@ -167,6 +168,83 @@ class Dense:
         np.subtract.at(p, e[:, 0], 0.5 * r)
         np.subtract.at(p, e[:, 1], 0.5 * r)
         return p, e, 2.0 * (p[e[:, 0]] + p[e[:, 1]]) / r
+
+
+# ---- without a dense matrix: the reference of tests/test_resistance_gpu.py at 33,000 nodes -----------------------------------------
+def _sparse_adjacency(edge_index, n):
+    import scipy.sparse
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
+    ei = ei[:, ei[0] != ei[1]]
+    a = scipy.sparse.coo_matrix((np.ones(ei.shape[1]), (ei[0], ei[1])), shape=(n, n)).tocsr()
+    a = a + a.T
+    a.data[:] = 1.0
+    return a
+
+
+def _matvec_long(m, x):
+    """m @ x in np.longdouble for a scipy CSR matrix with no empty row, x [k, columns]."""
+    prod = m.data.astype(np.longdouble)[:, None] * x[m.indices]
+    return np.add.reduceat(prod, m.indptr[:-1], axis=0)
+
+
+def sparse_resistance(edge_index, n, pairs, ground='smallest'):
+    """float64 [P]: R(u, v) from the grounded Laplacian, component by component.  In a component C with the node g removed
+    (``ground``: its 'smallest' or its 'largest' id), L_g = (D - A)[C - g, C - g] is positive definite and x = L_g^-1 (e_u - e_v),
+    with x_g = 0 and the entry of g dropped from the right-hand side, gives R = x_u - x_v.  ``scipy.sparse.linalg.splu``, then one
+    step of refinement with the residual e_u - e_v - L_g x formed in np.longdouble.  0 for u == v, inf across components."""
+    import scipy.sparse.csgraph
+    import scipy.sparse.linalg
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    a = _sparse_adjacency(edge_index, n)
+    lap = (scipy.sparse.diags(np.asarray(a.sum(axis=1)).ravel()) - a).tocsr()
+    _, labels = scipy.sparse.csgraph.connected_components(a, directed=False)
+    out = np.where(pr[:, 0] == pr[:, 1], 0.0, np.inf)
+    todo = np.flatnonzero((pr[:, 0] != pr[:, 1]) & (labels[pr[:, 0]] == labels[pr[:, 1]]))
+    for comp in np.unique(labels[pr[todo, 0]]):
+        mine = todo[labels[pr[todo, 0]] == comp]
+        nodes = np.flatnonzero(labels == comp)
+        g = nodes[0] if ground == 'smallest' else nodes[-1]
+        keep = nodes[nodes != g]
+        at = np.full(n, -1, dtype=np.int64)          # position in the grounded system; -1: the ground
+        at[keep] = np.arange(keep.size)
+        m = lap[keep][:, keep].tocsr()
+        m.sort_indices()
+        rhs = np.zeros((keep.size, mine.size))
+        for col, (u, v) in enumerate(pr[mine]):
+            if at[u] >= 0:
+                rhs[at[u], col] += 1.0
+            if at[v] >= 0:
+                rhs[at[v], col] -= 1.0
+        lu = scipy.sparse.linalg.splu(m.tocsc())
+        x = lu.solve(rhs)
+        defect = rhs.astype(np.longdouble) - _matvec_long(m, x.astype(np.longdouble))
+        x = (x.astype(np.longdouble) + lu.solve(defect.astype(np.float64))).astype(np.float64)
+        x = np.concatenate([x, np.zeros((1, mine.size))])   # at == -1 reads the ground's 0
+        cols = np.arange(mine.size)
+        out[mine] = x[at[pr[mine, 0]], cols] - x[at[pr[mine, 1]], cols]
+    return out
+
+
+def lambda1_lower(edge_index, n, node):
+    """(lam_lo, theta, ritz_residual): a lower bound of lambda_1 of the normalised Laplacian I - D^-1/2 A D^-1/2 of the component
+    of ``node``.  ``scipy.sparse.linalg.eigsh`` in shift-invert mode just below 0 returns the two Ritz pairs nearest the shift: the
+    null vector D^1/2 1 and (theta, w).  Some eigenvalue lies within |L' w - theta w| / |w| of theta, the residual evaluated with
+    a plain sparse product; lam_lo = theta - that residual."""
+    import scipy.sparse.csgraph
+    import scipy.sparse.linalg
+    a = _sparse_adjacency(edge_index, n)
+    _, labels = scipy.sparse.csgraph.connected_components(a, directed=False)
+    nodes = np.flatnonzero(labels == labels[node])
+    a = a[nodes][:, nodes].tocsr()
+    s = scipy.sparse.diags(1.0 / np.sqrt(np.asarray(a.sum(axis=1)).ravel()))
+    lap = (scipy.sparse.identity(nodes.size) - s @ a @ s).tocsc()
+    v0 = np.random.Generator(np.random.PCG64(1)).standard_normal(nodes.size)
+    vals, vecs = scipy.sparse.linalg.eigsh(lap, k=2, sigma=-1e-3, which='LM', v0=v0, tol=1e-12)
+    order = np.argsort(vals)
+    theta, w = float(vals[order[1]]), vecs[:, order[1]]
+    assert abs(vals[order[0]]) <= 1e-10 < theta, vals     # one null vector in a component, and theta is not it
+    resid = float(np.linalg.norm(lap @ w - theta * w) / np.linalg.norm(w))
+    return theta - resid, theta, resid
 
 
 def allow(n, r_ref):

@@ -1,8 +1,8 @@
-"""The sizes at which the sweep, diffusion and FoSR kernels change their control flow, and the graphs the GPU tests use there (host
-only).  The constants are read out of csrc/*.hip and csrc/dcr_analysis.h, the launch arithmetic of sweep_buffers, diffusion_batches
-and row_grid is restated in Python, and tests/test_scale_thresholds_cpu.py asserts that every size named here sits just past the
-boundary it is there for.  The graphs are built with array operations only: a Python loop over half a million nodes costs more
-than the kernels under test."""
+"""The sizes at which the sweep, diffusion, FoSR, resistance and hop kernels change their control flow, and the graphs the GPU tests
+use there (host only).  The constants are read out of csrc/*.hip and csrc/dcr_analysis.h, the launch arithmetic of sweep_buffers,
+diffusion_batches, resistance_batches, the hop count and row_grid is restated in Python, and tests/test_scale_thresholds_cpu.py
+asserts that every size named here sits just past the boundary it is there for.  The graphs are built with array operations
+only: a Python loop over half a million nodes costs more than the kernels under test."""
 import os
 import re
 
@@ -57,6 +57,29 @@ def constants():
     assert m, 'the medium rows of a workgroup in row_grid'
     c['MID_ROWS'] = int(m.group(1))
     assert re.search(r'using\s+DifRows\s*=\s*RowGeom<DIF_SHORT_LANES,\s*DIF_SHORT_ROWS\s*/\s*8,\s*DIF_CP>\s*;', dif)
+    c.update(resistance_and_hops_constants())
+    return c
+
+
+def resistance_and_hops_constants():
+    """The constants of csrc/dcr_resistance.hip and csrc/dcr_hops.hip that RESISTANCE_SIZE, HOPS_SMALL and HOPS_LARGE depend on
+    ('DCR_RES_B' is the default of the #define, which is what the library is built with)."""
+    res, hops = source('dcr_resistance.hip'), source('dcr_hops.hip')
+    c = {name: constant(res, name) for name in ('RES_UPDATE_BLOCKS', 'RES_SHORT_LANES', 'RES_SHORT_ROWS')}
+    m = re.search(r'#ifndef\s+DCR_RES_B\s*\n\s*#define\s+DCR_RES_B\s+(\d+)', res)
+    assert m, 'the default of DCR_RES_B not found'
+    c['DCR_RES_B'] = int(m.group(1))
+    assert re.search(r'constexpr\s+int\s+RES_B\s*=\s*DCR_RES_B\s*;', res) and re.search(r'constexpr\s+int\s+RES_CP\s*=\s*RES_B\s*/\s*2\s*;', res)
+    c['RES_CP'] = c['DCR_RES_B'] // 2
+    assert re.search(r'nb_el\s*=\s*\(int\)std::min<int64_t>\(RES_UPDATE_BLOCKS,\s*blocks_of\(n\s*\*\s*RES_CP\)\)', res), 'nb_el of resistance_batches'
+    assert re.search(r'nb_mv\s*=\s*\(int\)row_grid<ResRows>\(plan\)', res)
+    assert re.search(r'using\s+ResRows\s*=\s*RowGeom<RES_SHORT_LANES,\s*RES_SHORT_ROWS\s*/\s*8,\s*RES_CP>\s*;', res)
+    assert len(re.findall(r'e\s*<\s*total;\s*e\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*256\)', res)) == 4, 'the four grid-stride loops over n * RES_CP'
+    assert re.search(r'i\s*<\s*count;\s*i\s*\+=\s*256\s*/\s*RES_CP\)', res), 'the stride of cols_close_partials'
+    c['HOP_COUNT_BLOCKS'] = constant(hops, 'HOP_COUNT_BLOCKS')
+    assert re.search(r'k_hop_count<W>,\s*dim3\(std::min\(blocks_of\(\(n\s*\+\s*63\)\s*/\s*64,\s*4\),\s*\(unsigned\)HOP_COUNT_BLOCKS\)\)', hops), 'the grid of k_hop_count'
+    assert re.search(r'c\s*=\s*\(int64_t\)blockIdx\.x\s*\*\s*4\s*\+\s*wave;\s*c\s*<\s*chunks;\s*c\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*4\)', hops), 'the chunk loop of k_hop_count'
+    assert re.search(r'k_hop_level<W>,\s*dim3\(row_grid<HopRows>\(plan\)\)', hops) and re.search(r'using\s+HopRows\s*=\s*RowGeom<>\s*;', hops)
     return c
 
 
@@ -95,10 +118,25 @@ def diffusion_batches(n, P, c):
     return groups, nb_el, blocks_of(n * cp, nb_el * 256)
 
 
-def row_grid(counts, c):
-    """row_grid<RowGeom<>> of csrc/dcr_analysis.h for (n_long, n_mid, n_short)."""
+def row_grid(counts, c, short_rows=None):
+    """row_grid<RowGeom<>> of csrc/dcr_analysis.h for (n_long, n_mid, n_short); short_rows: those of another geometry."""
     nl, nm, ns = counts
-    return nl + blocks_of(nm, c['MID_ROWS']) + blocks_of(ns, c['SHORT_ROWS'])
+    return nl + blocks_of(nm, c['MID_ROWS']) + blocks_of(ns, short_rows or c['SHORT_ROWS'])
+
+
+def resistance_elementwise(n, c):
+    """(nb_el, grid-stride trips, elements of the last trip) of k_res_start / update / direction / scale_y over n * RES_CP elements."""
+    total = n * c['RES_CP']
+    nb_el = min(c['RES_UPDATE_BLOCKS'], blocks_of(total))
+    trips = blocks_of(total, nb_el * 256)
+    return nb_el, trips, total - (trips - 1) * nb_el * 256
+
+
+def hop_count_grid(n, c):
+    """(workgroups of k_hop_count, trips of its chunk loop): four waves a workgroup, 64 nodes a wave and trip."""
+    chunks = blocks_of(n, 64)
+    grid = min(blocks_of(chunks, 4), c['HOP_COUNT_BLOCKS'])
+    return grid, blocks_of(chunks, 4 * grid)
 
 
 def dot_trips(n, c):
@@ -113,6 +151,8 @@ DIFFUSION_SIDE, DIFFUSION_P = 182, 17                   # a 182 x 182 lattice, t
 GROUPS_SIDE, GROUPS_P = 100, 6 * 16 + 5                 # groups limited by n
 SMALL_GROUPS_P = 8 * 16                                 # groups 2 .. 7 on long3_mid9_short63
 FOSR_SMALL, FOSR_LARGE = WHOLE_SMALL, 262_145 + 37      # picks; the power step and the loop
+RESISTANCE_SIZE = DIFFUSION_SIDE ** 2 + 5 + 4           # diffusion_large(): the element-wise kernels of the resistance on a second trip
+HOPS_SMALL, HOPS_LARGE = WHOLE_SMALL, FOSR_LARGE        # many workgroups of k_hop_level; the chunk loop of k_hop_count on a second trip
 
 
 # ---- graphs --------------------------------------------------------------------------------------------------------------------
@@ -227,3 +267,64 @@ def class_counts(deg, c):
     """(n_long, n_mid, n_short) of csrc/dcr_analysis.hip::classify_rows."""
     nl, ns = int((deg > c['SP_LONG_DEG']).sum()), int((deg <= c['SP_SHORT_DEG']).sum())
     return nl, deg.shape[0] - nl - ns, ns
+
+
+# ---- what the resistance and hop tests ask at those sizes (tests/test_resistance_gpu.py, tests/test_hops_gpu.py) -------------------
+SECOND_TRIP = 32_768   # the first node of diffusion_large() that the element-wise resistance kernels take on their second trip
+
+
+def resistance_pairs():
+    """(pairs int64 [19, 2], solved [17], names) on diffusion_large(): 17 pairs that take a column, so the second batch of 16 has
+    15 padding columns, and two that the host decides (one with an isolated node, one u == v), which take none."""
+    _, n, names = diffusion_large()
+    side, hub0 = DIFFUSION_SIDE, names['hub0']
+    pairs = np.array([
+        (hub0, names['corner']),                 # 0: the long row and node 0
+        (SECOND_TRIP + 32, 0),                   # 1: a lattice node of the second trip and node 0
+        (33_000, 33_100),                        # 2: both in the second trip
+        (5_000, 5_001),                          # 3: the two ends of a lattice edge, first trip
+        (hub0, names['hub3']),                   # 4: the long row and a medium row
+        (names['isolated'], 7),                  # 5: across components: inf, no column
+        (12_345, 12_345),                        # 6: u == v: 0, no column
+        (33_000, 33_001),                        # 7: a lattice edge inside the second trip
+        (SECOND_TRIP - 1, SECOND_TRIP),          # 8: the lattice edge across the trip boundary
+        (side * side - 1, 0),                    # 9: opposite corners
+        (names['hub1'], SECOND_TRIP),            # 10: a medium row of 33 (the smallest) and the first node of the second trip
+        (names['hub2'], names['hub4']),          # 11: two medium rows
+        (side * side - 1, hub0),                 # 12: the last lattice node and the long row, neighbours in id
+        (side - 1, side * (side - 1)),           # 13: the other two corners
+        (91 * side + 91, hub0),                  # 14: the lattice's centre
+        (names['hub4'], 20_000),                 # 15
+        (SECOND_TRIP + 200, 16_000),             # 16
+        (1, 2 * side),                           # 17: two hops apart near the corner
+        (33_100, names['hub2']),                 # 18: the 17th solved pair: alone in the second batch
+    ], dtype=np.int64)
+    solved = np.array([i for i in range(len(pairs)) if i not in (5, 6)])
+    return pairs, solved, names
+
+
+def hop_sources_small():
+    """21 sources of whole_small(): the long row, a medium row, node 0, an isolated node, the last node, the last connected one."""
+    rng = np.random.Generator(np.random.PCG64(71))
+    n = WHOLE_SMALL
+    return np.concatenate([[40_000, 33_333, 0, n - 3, n - 1, n - 4], rng.integers(0, n, 15)]).astype(np.int32)
+
+
+def hop_sources_large():
+    """130 sources of fosr_large(): two full words and two bits of a third.  They are 26 nodes five times each, in shuffled order,
+    so that the host reference searches 26 times (0.06 s a search: its levels are a thousand numpy steps) while the device gives
+    every one of the 130 bits a search of its own.  Node 262,144 (the one connected node of the second trip of k_hop_count) has
+    a bit in each of the three words, the isolated last node and node 0 sit at the word boundaries."""
+    rng = np.random.Generator(np.random.PCG64(262))
+    n = HOPS_LARGE
+    nodes = np.concatenate([[262_144, n - 1, 0, n - 20, 5], rng.choice(np.arange(6, n - 37), size=21, replace=False)])
+    fixed = {0: 262_144, 63: n - 1, 64: 262_144, 127: 0, 128: 262_144, 129: 0}
+    pool = np.tile(nodes, 5).tolist()
+    for node in fixed.values():
+        pool.remove(node)
+    pool = rng.permutation(pool)
+    src = np.empty(130, dtype=np.int32)
+    free = [i for i in range(130) if i not in fixed]
+    src[free] = pool
+    src[list(fixed)] = list(fixed.values())
+    return src

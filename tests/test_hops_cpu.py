@@ -150,3 +150,33 @@ def test_call_surface():
         assert f'batch<{w}>' in source                                    # the widths the entry point dispatches to
     state = open(os.path.join(CSRC, 'dcr_analysis.h')).read()
     assert all(f'hop_{b}' in state for b in ('bits', 'ctl', 'dist'))
+
+
+# ---- the sparse reference of the 70,001- and 262,182-node tests ---------------------------------------------------------------------
+@pytest.mark.parametrize('name', list(FIXTURES))
+def test_sparse_reference_is_the_reference(name, solved):
+    ei, n = FIXTURES[name]
+    want = solved[name][0]
+    src = np.concatenate([np.arange(n), [n - 1, 0, n // 2, 0]])                      # every node, then repeats: 16 is no divisor
+    got = hops_ref.hops_sparse(ei, n, src)
+    for g, w in zip(got, want):
+        assert g.dtype == w.dtype and np.array_equal(g, w[src])
+    none, e, r, t = hops_ref.hops_sparse(ei, n, src, rows=False)
+    assert none is None and np.array_equal(e, want[1][src]) and np.array_equal(r, want[2][src]) and np.array_equal(t, want[3][src])
+    for max_hops in (0, 1, 2, 7):
+        some = src[::5]
+        for g, w in zip(hops_ref.hops_sparse(ei, n, some, max_hops=max_hops), hops_ref.hops(ei, n, some, max_hops=max_hops)):
+            assert np.array_equal(g, w)
+
+
+def test_sparse_reference_is_scipy_at_70001_nodes():
+    import scale_ref as sc
+    ei, n = sc.whole_small()
+    src = sc.hop_sources_small()[:6]                                                  # the long row, a medium row, node 0, isolated ones
+    dist, ecc, reached, total = hops_ref.hops_sparse(ei, n, src)
+    d = scipy.sparse.csgraph.shortest_path(spectral_ref.adjacency(ei, n), method='D', directed=False, unweighted=True, indices=src)
+    want = np.where(np.isinf(d), -1, d).astype(np.int32)
+    assert np.array_equal(dist, want)
+    e, r, t = hops_ref.summaries_of(want)
+    assert np.array_equal(ecc, e) and np.array_equal(reached, r) and np.array_equal(total, t)
+    assert reached.tolist() == [n - 3, n - 3, n - 3, 1, 1, n - 3]

@@ -2,8 +2,10 @@
 reference is exact (tests/test_hops_cpu.py holds it against scipy on every graph used here), so nothing is skipped, filtered or
 given a tolerance.  Shapes are the smallest at which each piece can go wrong: degenerate and disconnected graphs, more levels
 than an 8-bit counter holds, every row class at its workgroup, wave and turn boundaries, every batch width and the source counts
-either side of them, the hop limit, a graph edited between queries."""
+either side of them, the hop limit, a graph edited between queries.  The last section runs the sizes of tests/scale_ref.py, where
+the level kernel has thousands of workgroups and the count kernel's capped grid takes a second trip."""
 import ctypes
+import time
 
 import numpy as np
 import pytest
@@ -245,3 +247,117 @@ def test_bad_input():
     src = np.array([3], dtype=np.int32)
     assert _lib.lib().dcr_hop_distances(G._h, src.ctypes.data_as(_lib._i32p), 1, None, None, None, ctypes.byref(only), None) == 0
     assert only.value == r[0]
+
+
+# ---- many workgroups of k_hop_level, and k_hop_count past HOP_COUNT_BLOCKS ------------------------------------------------------------
+# tests/test_scale_thresholds_cpu.py says what each size reaches; the reference is hops_ref.hops_sparse, which tests/test_hops_cpu.py
+# holds against hops_ref.hops on every small graph and against scipy at 70,001 nodes.  Both graphs end in a path of 1,000 nodes
+# that no chord reaches, so a search takes about a thousand levels: the tests print them.
+_BIG = {}
+
+
+def big(name):
+    """(DcrGraph, edge_index, n) of scale_ref.whole_small() / fosr_large(), one handle a graph."""
+    import scale_ref as sc
+    if name not in _BIG:
+        ei, n = sc.whole_small() if name == 'small' else sc.fosr_large()
+        _BIG[name] = (graph(ei, n), ei, n)
+    return _BIG[name]
+
+
+def big_reference(key, name, sources, **kw):
+    """hops_sparse of one source list on a big graph, computed once and never written to."""
+    if key not in _REF:
+        _, ei, n = big(name)
+        t0 = time.perf_counter()
+        out = hops_ref.hops_sparse(ei, n, sources, **kw)
+        print(f'  host reference {key}: {time.perf_counter() - t0:.2f} s')
+        for a in out:
+            if a is not None:
+                a.setflags(write=False)
+        _REF[key] = out
+    return _REF[key]
+
+
+def equal_summaries(got, want, label):
+    e, r, t = got
+    assert (e.dtype, r.dtype, t.dtype) == (np.int32, np.int64, np.int64)
+    assert np.array_equal(e, want[1]) and np.array_equal(r, want[2]) and np.array_equal(t, want[3]), label
+
+
+def test_rows_and_summary_at_70001_nodes():
+    import scale_ref as sc
+    G, ei, n = big('small')
+    src = sc.hop_sources_small()
+    want = big_reference('small21', 'small', src)
+    G.hop_summary(src[:1], max_hops=1)                                            # buffers and code objects
+    t0 = time.perf_counter()
+    dist = G.hop_distances(src)
+    t1 = time.perf_counter()
+    got = G.hop_summary(src)
+    t2 = time.perf_counter()
+    print(f'  n = {n}, {src.size} sources: levels {got[0].max()}, hop_distances {1e3 * (t1 - t0):.1f} ms, hop_summary {1e3 * (t2 - t1):.1f} ms')
+    assert dist.dtype == np.int32 and dist.shape == (src.size, n) and np.array_equal(dist, want[0])
+    equal_summaries(got, want, 'whole_small')
+    assert got[1][:6].tolist() == [n - 3, n - 3, n - 3, 1, 1, n - 3] and (dist[:, -3:] == -1).sum() == 3 * src.size - 2
+
+
+@pytest.mark.parametrize('words', ['1', '2', '4'])
+def test_summary_at_262182_nodes(words, monkeypatch):
+    """130 sources under every batch width, so each k_hop_count<W> and k_hop_level<W> takes the capped grid.  A connected source
+    reaches 262,145 nodes: node 262,144 is the one connected node that only the second trip of the count kernel sees."""
+    import scale_ref as sc
+    G, ei, n = big('large')
+    src = sc.hop_sources_large()
+    want = big_reference('large130', 'large', src, rows=False)
+    monkeypatch.setenv('DCR_HOPS_W', words)
+    G.hop_summary(src[:1], max_hops=1)
+    t0 = time.perf_counter()
+    got = G.hop_summary(src)
+    print(f'  n = {n}, {src.size} sources, W = {words}: levels {got[0].max()}, hop_summary {1e3 * (time.perf_counter() - t0):.1f} ms')
+    equal_summaries(got, want, words)
+    connected = src < n - 37
+    assert connected.sum() >= 120 and (got[1][connected] == 262_145).all() and (got[1][~connected] == 1).all()
+    assert got[0][src == 262_144].min() == got[0].max() >= 1_000                  # the end of the tail is the farthest node
+
+
+def test_rows_at_262182_nodes():
+    """Three sources, one word: the batch's block on the device is 3 x n int32 of a buffer of 64 x n (67 MB).  The source at node
+    262,144 writes its distance 0 at dist[i * n + s] from k_hop_init at the far end of a row."""
+    G, ei, n = big('large')
+    src = np.array([262_144, 0, n - 1], dtype=np.int32)
+    want = big_reference('large3', 'large', src)
+    t0 = time.perf_counter()
+    dist = G.hop_distances(src)
+    print(f'  n = {n}, 3 sources: levels {want[1].max()}, hop_distances {1e3 * (time.perf_counter() - t0):.1f} ms')
+    assert dist.dtype == np.int32 and dist.shape == (3, n)
+    assert (dist[:2, 262_144] >= 0).all() and dist[0, 262_144] == 0 and (dist[:2, -1] == -1).all()
+    assert dist[2, -1] == 0 and (dist[2, :-1] == -1).all()                        # the isolated source: its own node alone
+    assert np.array_equal(dist, want[0])
+    equal_summaries(G.hop_summary(src), want, 'three sources')
+
+
+def test_hop_limit_at_262182_nodes():
+    from experiment.hop_metrics import ball_sizes
+    import scale_ref as sc
+    G, ei, n = big('large')
+    src = sc.hop_sources_large()
+    want = big_reference('large130_2hops', 'large', src, max_hops=2, rows=False)
+    t0 = time.perf_counter()
+    got = G.hop_summary(src, max_hops=2)
+    print(f'  n = {n}, {src.size} sources, max_hops = 2: hop_summary {1e3 * (time.perf_counter() - t0):.1f} ms')
+    equal_summaries(got, want, 'max_hops = 2')
+    assert got[0].max() == 2 and got[1][src == 262_144].tolist() == [3] * 5         # the end of a path: itself and two more
+    assert np.array_equal(ball_sizes(G, 2, src), want[2])
+
+
+def test_two_identical_calls_at_262182_nodes():
+    import scale_ref as sc
+    G, ei, n = big('large')
+    src = sc.hop_sources_large()
+    first, second = G.hop_summary(src), G.hop_summary(src)
+    for x, y in zip(first, second):
+        assert x is not y and x.tobytes() == y.tobytes()
+    few = src[[0, 1, 5]]
+    a, b = G.hop_distances(few), G.hop_distances(few)
+    assert a is not b and a.tobytes() == b.tobytes()

@@ -13,6 +13,7 @@ GRAPHS = {
     'barbell20_4': lambda: ref.barbell(20, 4),
     'random300': lambda: ref.random_graph(),
     'triangle_star_isolated': ref.triangle_star_isolated,
+    'hub_with_tail40': lambda: ref.hub_with_tail(40),
 }
 
 
@@ -120,3 +121,44 @@ def test_hub_with_tail_closed_forms():
     ei, n = ref.hub_with_tail(40)
     d = ref.Dense(ei, n)
     assert close(d.resistance([(2, 3), (0, 7), (5, n - 1), (1, n - 1)]), np.array([2.0, 1.0, 5.0, 3.0]), n)
+
+
+# ---- the sparse reference of the 33,133-node test ------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', sorted(GRAPHS))
+@pytest.mark.parametrize('ground', ['smallest', 'largest'])
+def test_sparse_resistance_is_pinv(dense, name, ground):
+    d = dense(name)
+    n = d.n
+    pr = all_pairs(n) if n <= 50 else np.random.default_rng(2).integers(0, n, size=(500, 2))
+    ei = np.stack(np.nonzero(d.a))
+    want = d.resistance(pr)
+    got = ref.sparse_resistance(ei, n, pr, ground=ground)
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isposinf(got), ~fin) and np.all(got[pr[:, 0] == pr[:, 1]] == 0.0)
+    assert close(got[fin], want[fin], n)
+    if name == 'triangle_star_isolated':
+        assert np.isposinf(got[~fin]).all() and (~fin).sum() == 2 * (3 * 5 + 3 + 5)
+
+
+def test_sparse_reference_at_33133_nodes():
+    """What tests/test_resistance_gpu.py holds the device to at 33,133 nodes, measured against itself: e_ref, the largest
+    disagreement of two groundings (at node 0 and at hub4, the last connected node) over the test's 17 solved pairs, and lam_lo.
+    Measured here: e_ref = 2.2e-16 (allow = 4.7e-10), lambda_1 >= 9.4189e-3 with a Ritz residual of 5e-16."""
+    import scale_ref as sc
+    ei, n, names = sc.diffusion_large()
+    pairs, solved, _ = sc.resistance_pairs()
+    first = ref.sparse_resistance(ei, n, pairs)
+    second = ref.sparse_resistance(ei, n, pairs, ground='largest')
+    assert np.isposinf(first[5]) and np.isposinf(second[5]) and first[6] == 0.0 and second[6] == 0.0
+    assert np.isfinite(first[solved]).all()
+    e_ref = np.abs(first[solved] - second[solved]).max()
+    lam_lo, theta, ritz = ref.lambda1_lower(ei, n, 0)
+    print(f'  e_ref = {e_ref:.3e}, allow = {ref.allow(n, 1.0):.3e}; lambda_1 >= {lam_lo:.6e} (theta {theta:.6e}, Ritz residual {ritz:.3e})')
+    print('  R_ref =', np.array2string(first, precision=6))
+    # two exact solutions of the same system agree to the rounding of the arithmetic, which is what allow() stands for
+    assert e_ref <= ref.allow(n, 1.0)
+    deg = sc.degrees(ei, n).astype(float)
+    inv = 1 / deg[pairs[solved, 0]] + 1 / deg[pairs[solved, 1]]
+    assert np.all(0.5 * inv <= first[solved]) and np.all(first[solved] <= inv / lam_lo)          # Lovász, with the certified gap
+    assert np.all(first[[3, 7, 8]] < 1.0)                                                        # an edge that lies on a cycle
+    assert 0.0 < lam_lo <= theta and ritz <= 64 * n * ref.EPS

@@ -307,3 +307,80 @@ def test_scale_s100k_one_batch(dcr):
     print('  lower / (inv / 2) in', (lower / (0.5 * inv)).min(), '..', (lower / (0.5 * inv)).max())
     assert np.all(0.5 * inv - a <= lower)          # Lovász: 1/2 (1/d_u + 1/d_v) <= R, and R - lower <= residual^2 / lambda_1 ~ 1e-20
     assert np.all(lower <= inv / lam + a)          # a sanity check, not a certificate: a Lanczos lambda_1 is never below the true one
+
+
+# ---- 10. past the cap of the element-wise kernels --------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def past_cap(dcr):
+    """scale_ref.diffusion_large(), 33,133 nodes: n RES_CP elements are more than 256 RES_UPDATE_BLOCKS, so k_res_start, update,
+    direction and scale_y take a second, ragged grid-stride trip (the lattice's last 356 nodes, every hub, the isolated nodes)
+    and k_res_update closes a full 1,024 partials, 32 a thread group (tests/test_scale_thresholds_cpu.py).  The reference is
+    resistance_ref.sparse_resistance, measured against itself by a second grounding (e_ref), and lam_lo is a certified lower
+    bound of lambda_1 (tests/test_resistance_cpu.py pins both on the CPU); neither comes from the device.  One 19-pair call,
+    shared by the tests below: 17 pairs take a column (the second batch has 15 padding columns), two are decided on the host."""
+    import scale_ref as sc
+    ei, n, names = sc.diffusion_large()
+    pairs, solved, _ = sc.resistance_pairs()
+    t0 = time.perf_counter()
+    r_ref = ref.sparse_resistance(ei, n, pairs)
+    e_ref = float(np.abs(r_ref[solved] - ref.sparse_resistance(ei, n, pairs, ground='largest')[solved]).max())
+    lam_lo, theta, ritz = ref.lambda1_lower(ei, n, 0)
+    t1 = time.perf_counter()
+    G = dcr(ei, n)
+    with warnings.catch_warnings():   # (the first test asserts that every pair converged: a fixture that raises is an error, not a failure)
+        warnings.simplefilter('ignore', RuntimeWarning)
+        G.effective_resistance(pairs[:1])   # buffers and code objects
+        t2 = time.perf_counter()
+        lower, info = G.effective_resistance(pairs, return_info=True)
+        t3 = time.perf_counter()
+    print(f'  n = {n}: host reference {t1 - t0:.2f} s, e_ref = {e_ref:.3e}, lambda_1 >= {lam_lo:.6e} (Ritz residual {ritz:.3e}); '
+          f'the 19-pair call {1e3 * (t3 - t2):.1f} ms')
+    for a in (r_ref, lower, info['residual'], info['steps']):
+        a.setflags(write=False)
+    return dict(G=G, n=n, pairs=pairs, solved=solved, r_ref=r_ref, e_ref=e_ref, lam_lo=lam_lo, lower=lower, info=info)
+
+
+def test_past_the_cap_against_the_sparse_reference(past_cap):
+    """Per solved pair, with a = allow(n, R_ref) + e_ref:  lower <= R_ref + a  and  R_ref - lower <= residual^2 / lam_lo + a."""
+    p = past_cap
+    n, pairs, solved, lower, info = p['n'], p['pairs'], p['solved'], p['lower'], p['info']
+    host = np.setdiff1d(np.arange(len(pairs)), solved)
+    assert np.isposinf(lower[5]) and lower[6] == 0.0 and not np.signbit(lower[6])
+    assert np.all(info['steps'][host] == 0) and np.all(info['residual'][host] == 0.0)
+    r_ref, res, steps = p['r_ref'][solved], info['residual'][solved], info['steps'][solved]
+    a = ref.allow(n, r_ref) + p['e_ref']
+    gap = r_ref - lower[solved]
+    print(f'  steps {steps.min()} .. {steps.max()}, residual {res.min():.3e} .. {res.max():.3e}, R_ref - lower in {gap.min():.3e} .. {gap.max():.3e}, '
+          f'residual^2 / lam_lo <= {(res ** 2 / p["lam_lo"]).max():.3e}, a >= {a.min():.3e}')
+    assert np.all(np.isfinite(res)) and np.all(np.isfinite(lower[solved]))
+    assert info['converged'].all(), ('not converged', np.flatnonzero(~info['converged']))
+    assert np.all(steps > 0) and np.all(steps < 20000)
+    assert np.all(lower[solved] <= r_ref + a), ('above the reference', np.flatnonzero(lower[solved] > r_ref + a))
+    assert np.all(gap <= res ** 2 / p['lam_lo'] + a), ('the bound of the header comment fails', np.flatnonzero(gap > res ** 2 / p['lam_lo'] + a))
+
+
+def test_past_the_cap_a_column_depends_on_its_own_pair_only(past_cap):
+    from dcr.graph import RESISTANCE_BATCH as B
+    p = past_cap
+    G, pairs, solved = p['G'], p['pairs'], p['solved']
+    at = 2                                                                          # (33,000, 33,100): both nodes in the second trip
+    others = pairs[solved[solved != at]][:B - 1]
+    t0 = time.perf_counter()
+    calls = {'alone': (pairs[at:at + 1], 0), 'column 0': (np.concatenate([pairs[at:at + 1], others]), 0),
+             f'column {B - 1}': (np.concatenate([others, pairs[at:at + 1]]), B - 1)}
+    want = (p['lower'][at:at + 1].tobytes(), p['info']['residual'][at:at + 1].tobytes(), p['info']['steps'][at:at + 1].tobytes())
+    for label, (pr, k) in calls.items():
+        assert len(pr) in (1, B)
+        lower, info = solve(G, pr)
+        got = (lower[k:k + 1].tobytes(), info['residual'][k:k + 1].tobytes(), info['steps'][k:k + 1].tobytes())
+        assert got == want, (label, lower[k], p['lower'][at], info['steps'][k], p['info']['steps'][at])
+    print(f'  three calls {1e3 * (time.perf_counter() - t0):.1f} ms')
+
+
+def test_past_the_cap_two_calls_give_the_same_bytes(past_cap):
+    p = past_cap
+    t0 = time.perf_counter()
+    lower, info = solve(p['G'], p['pairs'])
+    print(f'  the 19-pair call again {1e3 * (time.perf_counter() - t0):.1f} ms')
+    assert lower.tobytes() == p['lower'].tobytes() and info['residual'].tobytes() == p['info']['residual'].tobytes()
+    assert info['steps'].tobytes() == p['info']['steps'].tobytes()

@@ -1,8 +1,8 @@
-"""Where the sweep, diffusion and FoSR kernels change their control flow, on the CPU: the constants are read out of the sources
-(tests/scale_ref.py), the launch arithmetic of sweep_buffers, diffusion_batches and row_grid is restated there, and every size
-that tests/test_sweep_gpu.py, tests/test_diffusion_gpu.py and tests/test_fosr_gpu.py run at is asserted to sit just past the
-boundary it is there for, with the size below it on the other side.  A failure names the GPU size that a changed constant has
-left stale."""
+"""Where the sweep, diffusion, FoSR, resistance and hop kernels change their control flow, on the CPU: the constants are read out
+of the sources (tests/scale_ref.py), the launch arithmetic of sweep_buffers, diffusion_batches, resistance_batches, the hop count
+and row_grid is restated there, and every size that tests/test_sweep_gpu.py, tests/test_diffusion_gpu.py, tests/test_fosr_gpu.py,
+tests/test_resistance_gpu.py and tests/test_hops_gpu.py run at is asserted to sit just past the boundary it is there for, with
+the size below it on the other side.  A failure names the GPU size that a changed constant has left stale."""
 import numpy as np
 import pytest
 
@@ -169,3 +169,77 @@ def test_whole_call_graphs_are_what_the_gpu_tests_rely_on(c):
     assert n == sc.WHOLE_LARGE and (deg[-37:] == 0).all() and (deg[:-37] > 0).all() and 9.5 < deg.mean() < 10.0
     assert np.array_equal(ei[0] * n + ei[1], np.unique(ei[0] * n + ei[1]))      # sorted, no repeats: ascending rows
     assert ei.shape[1] < 2 ** 31
+
+
+# ---- effective resistance ------------------------------------------------------------------------------------------------------------
+def test_resistance_elementwise_second_trip(c):
+    stale = ('stale GPU size: scale_ref.RESISTANCE_SIZE (RES_UPDATE_BLOCKS / DCR_RES_B: second grid-stride trip of k_res_start / update / '
+             'direction / scale_y, tests/test_resistance_gpu.py::test_past_the_cap_*)')
+    ei, n, names = sc.diffusion_large()
+    assert n == sc.RESISTANCE_SIZE
+    at = 256 * c['RES_UPDATE_BLOCKS'] // c['RES_CP']                              # 32,768: the largest n of one trip
+    assert at == sc.SECOND_TRIP, stale
+    assert sc.resistance_elementwise(at, c)[:2] == (c['RES_UPDATE_BLOCKS'], 1), stale
+    assert sc.resistance_elementwise(at + 1, c)[:2] == (c['RES_UPDATE_BLOCKS'], 2), stale
+    nb_el, trips, last = sc.resistance_elementwise(n, c)
+    assert n * c['RES_CP'] > 256 * c['RES_UPDATE_BLOCKS'] and (nb_el, trips) == (c['RES_UPDATE_BLOCKS'], 2), stale
+    assert 0 < last < nb_el * 256 and last == (n - at) * c['RES_CP'], stale       # ragged: fewer elements than one full grid
+    assert last % 256 != 0, stale                                                 # and its last workgroup is partly filled
+    assert nb_el == 32 * (256 // c['RES_CP']), stale                              # cols_close_partials: 32 partials a thread group
+    # what lies in the second trip: the lattice's tail, every hub and every isolated node; every pair the GPU test names
+    deg = sc.degrees(ei, n)
+    assert names['hub0'] >= at and deg[names['hub0']] > c['SP_LONG_DEG'], stale
+    assert all(names[f'hub{i}'] >= at and c['SP_SHORT_DEG'] < deg[names[f'hub{i}']] <= c['SP_LONG_DEG'] for i in range(1, 5)), stale
+    assert (deg[-4:] == 0).all() and (deg[:-4] > 0).all() and names['isolated'] == n - 4 >= at, stale
+    assert sc.DIFFUSION_SIDE ** 2 - at >= 256, stale                               # a few hundred lattice nodes past the boundary
+    pairs, solved, _ = sc.resistance_pairs()
+    assert len(solved) == c['DCR_RES_B'] + 1 and len(pairs) == len(solved) + 2, stale   # the second batch: one column, 15 padded
+    assert (pairs[solved][:, 0] != pairs[solved][:, 1]).all() and (deg[pairs[solved]] > 0).all()
+    assert (pairs[2] >= at).all() and (pairs[7] >= at).all() and pairs[1, 0] >= at > pairs[1, 1] and (pairs[18] >= at).all(), stale
+    assert pairs[8, 0] == at - 1 and pairs[8, 1] == at, stale
+    edge = set(map(tuple, ei.T.tolist()))
+    assert all(tuple(pairs[i]) in edge for i in (3, 7, 8))                          # lattice edges
+    assert deg[pairs[5, 0]] == 0 and pairs[6, 0] == pairs[6, 1]
+    # the mat-vec's grid: more than one step a thread group of cols_close_partials, here and on the 70,001-node graph
+    grid = sc.row_grid(sc.class_counts(deg, c), c, c['RES_SHORT_ROWS'])
+    assert grid > 2 * (256 // c['RES_CP']), stale
+
+
+def test_resistance_and_hop_matvec_grids_past_256_workgroups(c):
+    ei, n = sc.whole_small()
+    counts = sc.class_counts(sc.degrees(ei, n), c)
+    assert c['RES_SHORT_ROWS'] == 256 // c['RES_SHORT_LANES'] * 8                   # RowGeom<RES_SHORT_LANES, RES_SHORT_ROWS / 8, ..>
+    res_grid, hop_grid = sc.row_grid(counts, c, c['RES_SHORT_ROWS']), sc.row_grid(counts, c)
+    print(f'  n = {n}: row_grid<ResRows> {res_grid}, row_grid<HopRows> {hop_grid}')
+    assert res_grid > sc.CLOSING_STRIDE, 'stale GPU size: scale_ref.WHOLE_SMALL (RES_SHORT_ROWS: row_grid<ResRows> past 256 workgroups)'
+    assert hop_grid > sc.CLOSING_STRIDE, ('stale GPU size: scale_ref.HOPS_SMALL (RowGeom<>: row_grid<HopRows> past 256 workgroups, '
+                                          'tests/test_hops_gpu.py::test_rows_and_summary_at_70001_nodes)')
+
+
+# ---- hop distances -------------------------------------------------------------------------------------------------------------------
+def test_hop_count_second_trip(c):
+    stale = ('stale GPU size: scale_ref.HOPS_LARGE (HOP_COUNT_BLOCKS: second trip of the chunk loop of k_hop_count, '
+             'tests/test_hops_gpu.py::test_*_at_262182_nodes)')
+    ei, n = sc.fosr_large()
+    assert n == sc.HOPS_LARGE
+    at = 64 * 4 * c['HOP_COUNT_BLOCKS']                                           # 262,144: the largest n of one trip
+    assert sc.hop_count_grid(at, c) == (c['HOP_COUNT_BLOCKS'], 1) and sc.hop_count_grid(at + 1, c) == (c['HOP_COUNT_BLOCKS'], 2), stale
+    assert sc.blocks_of(n, 64) > 4 * c['HOP_COUNT_BLOCKS'] and sc.hop_count_grid(n, c) == (c['HOP_COUNT_BLOCKS'], 2), stale
+    deg = sc.degrees(ei, n)
+    second = deg[at:]                                                             # the nodes of the second trip: one wave's chunk
+    assert 0 < second.size <= 64 and (second > 0).sum() >= 1 and (second == 0).sum() >= 1, stale
+    assert deg[at] > 0 and (deg[at + 1:] == 0).all() and second.size == 38, stale
+    src = sc.hop_sources_large()
+    assert src.size == 130 and np.unique(src).size == 26, stale
+    for word in (src[:64], src[64:128], src[128:]):
+        assert at in word, stale                                                  # the connected node of the second trip in every word
+    assert n - 1 in src and 0 in src and deg[n - 1] == 0
+    # the smaller size: one trip of the count, many workgroups of the level kernel, all three row classes
+    stale = 'stale GPU size: scale_ref.HOPS_SMALL (tests/test_hops_gpu.py::test_rows_and_summary_at_70001_nodes)'
+    ei, n = sc.whole_small()
+    deg = sc.degrees(ei, n)
+    grid, trips = sc.hop_count_grid(n, c)
+    assert trips == 1 and 1 < grid < c['HOP_COUNT_BLOCKS'] and n % 64 != 0, stale
+    src = sc.hop_sources_small()
+    assert deg[src[0]] > c['SP_LONG_DEG'] and c['SP_SHORT_DEG'] < deg[src[1]] <= c['SP_LONG_DEG'] and src[2] == 0, stale
+    assert deg[src[3]] == 0 and src[4] == n - 1 and deg[src[4]] == 0 and deg[src[5]] > 0 and src[5] == n - 4, stale
