@@ -24,7 +24,8 @@
 //   k_spec_normalise           v_next = w / beta (beta read from device memory), z_next = s ⊙ v_next
 //   k_spec_combine             Ritz vector = basis x coefficients
 // The driver lives in dcr_spectral_gap: explicit restarts from the best Ritz vector, alpha and beta on the device, one host
-// synchronisation per 8 steps, the small tridiagonal problem solved on the host (implicit QL).  A Ritz vector is accepted on its
+// synchronisation per 8 steps (and after steps 1, 2 and 4 of a cycle, where a breakdown on a graph of few distinct eigenvalues
+// shows), the small tridiagonal problem solved on the host (implicit QL).  A Ritz vector is accepted on its
 // TRUE residual only: it becomes column 0 of a fresh cycle, whose first step yields alpha_0 = its Rayleigh quotient and beta_0 =
 // |P(B y) - alpha_0 y| by the same kernels.
 #include <algorithm>
@@ -443,7 +444,11 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
             R.step(j, (int)m);
             ++total;
             const bool forced = total >= o.max_steps - 1;
-            if (!(j == 0 || (j + 1) % SP_CHECK_EVERY == 0 || j + 1 == m || forced)) continue;
+            // The host also looks after steps 1, 2 and 4 of a cycle.  With two or three distinct eigenvalues on the deflated space
+            // (a star, a union of cliques) the recurrence breaks down there, and every step up to the next look would be spent
+            // on a zero column.
+            const bool early = j + 1 < SP_CHECK_EVERY && ((j + 1) & j) == 0;
+            if (!(early || (j + 1) % SP_CHECK_EVERY == 0 || j + 1 == m || forced)) continue;
             DCR_HIP(hipGetLastError());
             DCR_HIP(hipMemcpyAsync(ab.data(), A.spc_small, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, g->stream));
             DCR_HIP(hipStreamSynchronize(g->stream));
