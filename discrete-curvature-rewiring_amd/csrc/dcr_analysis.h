@@ -1,5 +1,5 @@
 // What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
-// dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip) and the
+// dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip, dcr_betweenness.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
 // dcr_graph.hip stay as they are.
@@ -216,6 +216,16 @@ struct AnalysisState {
     int64_t hop_ctl_cap = 0;
     int32_t *hop_dist = nullptr;    // [64 W][n] distance rows of a batch
     int64_t hop_dist_cap = 0;
+
+    // betweenness (dcr_betweenness.hip): O(16 n) for a batch of 16 sources; O(adjacency slots) only where edge values are asked for
+    int32_t *btw_dist = nullptr;    // [n][16] the level of the node for each source of the batch, -1: not reached
+    int64_t btw_dist_cap = 0;
+    double *btw_f64 = nullptr;      // sigma, delta as [n][16] each, then the sum over the batches [n]
+    int64_t btw_f64_cap = 0;
+    double *btw_slot = nullptr;     // [cap_total] the sum over the batches per adjacency slot
+    int64_t btw_slot_cap = 0;
+    unsigned char *btw_ctl = nullptr;  // the batch's control block (BtwCtl of dcr_betweenness.hip)
+    int64_t btw_ctl_cap = 0;
 
     void release();  // frees every buffer
 };

@@ -62,6 +62,11 @@ class HopsOpts(ctypes.Structure):
     _fields_ = [('max_hops', _i32)]
 
 
+class BetweennessInfo(ctypes.Structure):
+    """dcr_betweenness_info of include/dcr.h."""
+    _fields_ = [('levels_max', _i32), ('batches', _i32), ('sigma_max', _f64)]
+
+
 # name -> (restype, argtypes); every symbol include/dcr.h declares
 SIGNATURES = {
     'dcr_last_error': (ctypes.c_char_p, []),
@@ -122,6 +127,7 @@ SIGNATURES = {
     'dcr_fosr_pick': (ctypes.c_int, [_vp, _f64p, _i32p, _i32p, _f64p, _f64p, ctypes.POINTER(ctypes.c_int)]),
     'dcr_fosr': (ctypes.c_int, [_vp, ctypes.POINTER(FosrOpts), _f64p, _i32p, _i32p, _i64p, _f64p]),
     'dcr_hop_distances': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(HopsOpts), _i32p, _i32p, _i64p, _i64p]),
+    'dcr_betweenness': (ctypes.c_int, [_vp, _i32p, _i64, _f64p, _f64p, ctypes.POINTER(BetweennessInfo)]),
     'dcr_host_cdf_from_exp': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_host_cdf_from_exp_plain': (ctypes.c_int, [_f64p, _i64, _f64, _f64p, _f64p]),
     'dcr_spmm_csr_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, ctypes.c_int, _vp]),

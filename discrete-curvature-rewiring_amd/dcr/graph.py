@@ -656,6 +656,33 @@ class DcrGraph:
         ``max_hops=0``.  The search of ``hop_distances`` without its rows: no distance row exists on either side."""
         return self._hops(sources, max_hops, False)[1:]
 
+    # ---- betweenness centrality (csrc/dcr_betweenness.hip) ---------------------------------
+    def betweenness(self, sources=None, edges=False, return_info=False):
+        """Betweenness of the live graph as raw sums over ``sources`` (``None``: every node) of Brandes' dependencies: float64
+        ``node[n]``, and with ``edges=True`` ``(node, (eu, ev, edge))`` where ``eu, ev`` are ``self.edges()`` and ``edge[E]`` the
+        edge values in that order.  With every node a source this is the ordered-pair convention, twice
+        ``networkx.betweenness_centrality(G, normalized=False)`` and ``edge_betweenness_centrality`` of an undirected graph;
+        endpoints are not counted, other components contribute nothing, a duplicated source counts twice (include/dcr.h has the
+        rule; ``experiment/betweenness.py`` the networkx scalings).  16 sources a batch on the device, about ``2 * levels`` sweeps
+        of the adjacency a batch, read-only on the graph, the same bits on every call.  ``return_info``: a dict is appended with
+        ``levels_max``, ``batches`` and ``sigma_max``, the largest number of shortest paths of a pair; above ``2 ** 53`` the path
+        counts were rounded.  ``ValueError`` on a source outside the graph; ``DcrError`` where a path count leaves the float64
+        range."""
+        src = None if sources is None else self._sources(sources)
+        P = self.num_nodes if src is None else src.shape[0]
+        node = np.empty(self.num_nodes, dtype=np.float64)
+        eu = ev = edge = None
+        if edges:
+            eu, ev = self.edges()
+            edge = np.empty(max(eu.shape[0], 1), dtype=np.float64)
+        info = _lib.BetweennessInfo()
+        check(lib().dcr_betweenness(self._h, None if src is None else src.ctypes.data_as(_lib._i32p), P, node.ctypes.data_as(_lib._f64p),
+                                    edge.ctypes.data_as(_lib._f64p) if edges else None, ctypes.byref(info)))
+        out = (node, (eu, ev, edge[:eu.shape[0]])) if edges else (node,)
+        if return_info:
+            out += ({'levels_max': int(info.levels_max), 'batches': int(info.batches), 'sigma_max': float(info.sigma_max)},)
+        return out[0] if len(out) == 1 else out
+
     # ---- measurement hooks ------------------------------------------------------------
     def profile_reset(self):
         check(lib().dcr_profile_reset(self._h))

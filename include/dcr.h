@@ -438,6 +438,36 @@ int dcr_hop_distances(dcr_graph *g, const int32_t *sources /* NULL = every node,
                       int64_t *out_reached /* host [P]: nodes at distance <= max_hops, the source included */,
                       int64_t *out_total   /* host [P]: sum of the distances of those nodes */);
 
+/* ---- node and edge betweenness centrality (csrc/dcr_betweenness.hip; no counterpart in the reference) ------------------------
+ * For a source s, sigma_s(v) is the number of shortest paths from s to v in the live graph (unweighted, undirected; distances as in
+ * the hop-distance section above), and the dependency of s is, from the deepest level upwards,
+ *     delta_s(v)    = sum over the neighbours w of v one level further from s of  sigma_s(v) / sigma_s(w) (1 + delta_s(w)),
+ *     delta_s(v, w) = sigma_s(v) / sigma_s(w) (1 + delta_s(w))   for such an edge, 0 for every other edge
+ * (Brandes 2001).  The values are the RAW sums over the given sources:
+ *   out_node  host double [num_nodes]: sum over s in sources of delta_s(v), the term s == v left out: endpoints are not counted.
+ *   out_edge  host double [num_edges] or NULL: sum over s in sources of delta_s(u, v) + delta_s(v, u), in the order and orientation
+ *             of dcr_graph_edges.  Without it no per-slot buffer exists.
+ * With every node a source this is the ORDERED-pair convention, every pair (s, t) and (t, s) counted: twice the unnormalised value
+ * networkx gives for an undirected graph.  A duplicated source counts as often as it is given.  Nodes in other components than the
+ * source contribute nothing and receive nothing; an isolated node and a graph without edges give zeros.
+ *   out_info  or NULL: levels_max, the largest eccentricity of a source; batches, the batches of 16 sources that ran; sigma_max,
+ *             the largest path count met.  sigma is float64: sigma_max > 2^53 means that path counts were ROUNDED (the values then
+ *             carry that rounding, relative 2^-53 per addition, and stay finite and non-negative).  A path count beyond the float64
+ *             range is DCR_ESTATE with a message: no NaN or infinity is ever returned, and the handle stays usable.
+ * 16 sources a batch, a column each, in node-major int32 / float64 [num_nodes][16] arrays; one sweep of the adjacency per level
+ * forward (the host reads one count per level and stops at zero) and one per level backward, so about 2 (levels) sweeps a batch.
+ * Every sum has an order that the graph and the call fix, no floating-point atomic is used: two calls on the same graph return
+ * the same bits.  Relative error of a value: at most (2 D (maxdeg + 3) + P) 2^-53, D = levels_max + 1, all summands non-negative.
+ * READ-ONLY on the graph, runs on the graph's stream and is synchronous on return; 328 num_nodes bytes of work buffers, and 8 bytes
+ * per adjacency slot more where out_edge is given, stay on the handle until dcr_graph_destroy.  No num_nodes x num_nodes buffer
+ * exists on the device.
+ * Null g or out_node; P < 0; sources NULL with P != num_nodes; a source outside 0 .. num_nodes - 1: DCR_EINVAL before any device
+ * call.  P == 0: DCR_OK, zeros.  More levels than nodes (a corrupted graph): DCR_ESTATE. */
+typedef struct { int32_t levels_max; int32_t batches; double sigma_max; } dcr_betweenness_info;
+int dcr_betweenness(dcr_graph *g, const int32_t *sources /* NULL = every node, P must then be n */, int64_t P,
+                    double *out_node /* host [n] */, double *out_edge /* host [E] or NULL */,
+                    dcr_betweenness_info *out_info /* or NULL */);
+
 /* ---- dense float32 Balanced Forman curvature: the numerics of the reference's numba path (device pointers, caller's
  * stream).  curvature/bfc_cuda.py computes a different number from curvature/bfc_naive.py (float32 dense formula, other
  * 4-cycle term, no degree-1 rule) and it is what rewire('bfc') runs in the reference (rewiring/rewire.py:8-10), so results
