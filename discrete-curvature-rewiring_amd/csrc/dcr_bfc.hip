@@ -811,6 +811,7 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     if (curv_type < DCR_CURV_BFC || curv_type > DCR_CURV_HAANTJES) DCR_FAIL(DCR_EINVAL, "unknown curvature type");
     DCR_HIP(hipSetDevice(g->device));
     g->h2_launches = 0;
+    g->h2_weight_launches = g->h2_clear_launches = 0;
     g->h2_last_retry_stage = g->h2_last_tri_stage = false;
     g->amax_valid = false;
     g->ext_part_valid = false;  // (set again by the two-hop pass's closing kernel)
@@ -844,6 +845,8 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
         DCR_TRY(sync_result(g));
         if (g->last_engine == 0)
             for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres->h2_count[c];
+        // a two-hop pass that reports anything: the next one starts from the stand-alone clear
+        if (g->last_engine == 0 && (g->hres->h2_status != 0 || g->hres->misc[0] != 0 || g->hres->flag_too_big != 0)) g->h2_head_clean = false;
         return DCR_OK;
     };
     auto pass_again = [&](bool node_centric_only) -> int {  // the whole pass once more
@@ -928,12 +931,20 @@ int dcr_h2_stats(dcr_graph *g, int32_t out[6]) {
     return DCR_OK;
 }
 
-int dcr_h2_launch_info(dcr_graph *g, int32_t out[3]) {
+int dcr_h2_launch_info(dcr_graph *g, int32_t out[5]) {
     if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
     out[0] = g->h2_launches;
     out[1] = g->h2_last_retry_stage ? 1 : 0;
     out[2] = g->h2_last_tri_stage ? 1 : 0;
+    out[3] = g->h2_weight_launches;
+    out[4] = g->h2_clear_launches;
     return DCR_OK;
+}
+
+int dcr_h2_weight_check(dcr_graph *g, int64_t *mismatches) {
+    if (!g || !mismatches) DCR_FAIL(DCR_EINVAL, "null argument");
+    DCR_HIP(hipSetDevice(g->device));
+    return h2_weight_check(g, mismatches);
 }
 
 int dcr_pass_plan(int64_t n, int64_t n_edges, int64_t cap_total, double sum_deg2, int32_t max_deg_bound, int pending_edits,

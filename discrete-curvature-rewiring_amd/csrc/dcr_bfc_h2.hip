@@ -1854,11 +1854,29 @@ __global__ void __launch_bounds__(256) k_h2_weight(View g, int32_t *weight) {
 }
 
 // ---- plan: class, partitions and weight bucket per node; units laid out heaviest bucket first inside each class -------
+constexpr int H2_NB = H2_CLASSES * H2_WB;
+// the per-pass fields of the result block and bucket half `half`, by the first threads of one workgroup (tid: at least H2_NB)
+__device__ inline void h2_clear_result(DevResult *res, int tid, int half, bool flags_cleared) {
+    if (tid == 0 && flags_cleared) res->touched_n = 0;   // (the list of flagged nodes goes with the flags)
+    if (tid < 8) res->misc[tid] = 0;
+    if (tid < H2_NB) {
+        res->h2_bucket[half][tid] = 0;
+        res->h2_fill[half][tid] = 0;
+    }
+    if (tid < H2_CLASSES) res->h2_count[tid] = 0;
+    if (tid == 0) {
+        res->h2_status = 0;
+        res->h2_retry = 0;
+        for (int p = 0; p < 2; ++p) res->h2_ntask[p] = res->h2_ncand[p] = res->h2_npart[p] = res->h2_ncand_done[p] = 0;
+        for (int c = 0; c < 6; ++c) res->h2_failed[c] = 0;
+        res->h2_fallback = 0;
+        res->flag_too_big = 0;
+    }
+}
 struct H2Lists {
     int4 *units[H2_CLASSES];  // {node, partitions << 16 | partition, row start, degree}
     int64_t cap[H2_CLASSES];
 };
-constexpr int H2_NB = H2_CLASSES * H2_WB;
 constexpr int H2_PLAN_THREADS = 1024;
 
 __device__ inline void h2_classify(int d, int S, int &cls, int &wb, int &nparts) {
@@ -1880,8 +1898,16 @@ __device__ inline void h2_classify(int d, int S, int &cls, int &wb, int &nparts)
     if (wb < 0) wb = 0;
 }
 
+// PHASE 0 counts the units per bucket, PHASE 1 places them.  Both work in half `parity` of DevResult::h2_bucket / h2_fill.
+// PHASE 0 also takes the retry mark of the last pass (bit 31, h2_retry_push) off the weights it reads: the weights are kept from
+// pass to pass (dev_weight_edit), the mark belongs to one.
+// `head` != 0: the pass has no k_h2_clear and no k_h2_retry_zero ahead of the class kernels, their work is done here.  PHASE 0
+// zeroes the node flags of the incremental pass, and its workgroup 0 the bucket half of the NEXT pass and the per-pass fields of
+// the result block (none is read or written before PHASE 1; this half was left zero by the pass before, or by k_h2_clear);
+// PHASE 1 zeroes the records of the nodes it puts into the split class (their partitions add into them), a wave per row.
 template <int PHASE>
-__global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, const int32_t *weight, H2Lists L, DevResult *res) {
+__global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, int32_t *weight, H2Lists L, DevResult *res, int parity, int head,
+                                                             unsigned *dirty_words, int64_t n_dirty_words, uint4 *rec) {
     __shared__ int blk_count[H2_NB];
     __shared__ int blk_base[H2_NB];
     const int u = blockIdx.x * H2_PLAN_THREADS + threadIdx.x;
@@ -1893,10 +1919,17 @@ __global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, const int32
     if (u < g.n) {
         ru = g.rowinfo[u];
         const int d = ru.y;
+        const int wraw = weight[u];
+        if (PHASE == 0 && wraw < 0) weight[u] = wraw & 0x7FFFFFFF;
         if (d > 0 && d <= H2_MAXDEG) {
-            h2_classify(d, weight[u], cls, wb, nparts);
+            h2_classify(d, wraw & 0x7FFFFFFF, cls, wb, nparts);
             bkt = cls * H2_WB + wb;
         }
+    }
+    if (PHASE == 0 && head) {
+        const int64_t stride = (int64_t)gridDim.x * H2_PLAN_THREADS;
+        for (int64_t i = (int64_t)blockIdx.x * H2_PLAN_THREADS + threadIdx.x; i < n_dirty_words; i += stride) dirty_words[i] = 0u;
+        if (blockIdx.x == 0) h2_clear_result(res, (int)threadIdx.x, 1 - parity, n_dirty_words > 0);
     }
     const int nunits = bkt < 0 ? 0 : nparts;
     int my_off = 0;
@@ -1918,19 +1951,19 @@ __global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, const int32
     if (threadIdx.x < H2_NB) {
         const int b = threadIdx.x, c = blk_count[b];
         if (PHASE == 0) {
-            if (c) atomicAdd(&res->h2_bucket[b], c);
+            if (c) atomicAdd(&res->h2_bucket[parity][b], c);
         } else {
             int before = 0;
             for (int h = b + 1; h < H2_NB; ++h)  // heavier buckets of the same class come first
-                if (h / H2_WB == b / H2_WB) before += res->h2_bucket[h];
-            blk_base[b] = before + (c ? atomicAdd(&res->h2_fill[b], c) : 0);
+                if (h / H2_WB == b / H2_WB) before += res->h2_bucket[parity][h];
+            blk_base[b] = before + (c ? atomicAdd(&res->h2_fill[parity][b], c) : 0);
         }
     }
     if (PHASE == 0) return;
     if (blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 64 + H2_CLASSES) {
         const int c = (int)threadIdx.x - 64;
         int64_t tot = 0;
-        for (int b = c * H2_WB; b < (c + 1) * H2_WB; ++b) tot += res->h2_bucket[b];
+        for (int b = c * H2_WB; b < (c + 1) * H2_WB; ++b) tot += res->h2_bucket[parity][b];
         if (tot > (c == 0 ? L.cap[0] : c == 1 ? L.cap[1] : c == 2 ? L.cap[2] : c == 3 ? L.cap[3] : L.cap[4])) {  // the list cannot hold them: nothing of this class runs, the pass is redone elsewhere
             res->h2_status = 1;
             tot = 0;
@@ -1950,30 +1983,45 @@ __global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, const int32
             res->h2_status = 1;
         }  // (else: reported through h2_count / h2_status above)
     }
+    if (!head) return;  // (uniform: k_h2_retry_zero follows)
+    // Not the nodes this thread's wave has just placed: the split nodes of a power-law graph are its first few hundred ids, one
+    // workgroup's, whose 16 waves then zero every long row of the graph one after the other (measured: 39 us for this kernel
+    // instead of 10).  The nodes are dealt out again for this step, eight consecutive ids (one 64-byte piece of the row headers)
+    // to eight lanes and the pieces round-robin over the workgroups, then the waves, then the lane groups: a run of 8 * G * 16
+    // consecutive ids has no two pieces in one wave.  Every node below 1,024 * G is looked at by exactly one lane.
+    const int64_t piece = (int64_t)((lane >> 3) * (H2_PLAN_THREADS / 64) + (int)(threadIdx.x >> 6)) * gridDim.x + blockIdx.x;
+    const int64_t z = piece * 8 + (lane & 7);
+    int2 rz = make_int2(0, 0);
+    bool is_split = false;
+    if (z < g.n) {
+        rz = g.rowinfo[z];
+        if (rz.y > 0 && rz.y <= H2_MAXDEG) {
+            int zc, zb, zp;
+            h2_classify(rz.y, weight[z] & 0x7FFFFFFF, zc, zb, zp);
+            is_split = zc == 4;
+        }
+    }
+    unsigned long long split = __ballot(is_split);
+    while (split) {
+        const int src = __ffsll((long long)split) - 1;
+        split &= split - 1ull;
+        const int2 rs = make_int2(__shfl(rz.x, src), __shfl(rz.y, src));
+        if (!row_ok(g, rs, 42, __shfl((int)z, src), -1)) continue;
+        for (int i = lane; i < rs.y; i += 64) rec[(int64_t)rs.x + i] = make_uint4(0u, 0u, 0u, 0u);
+    }
 }
 
-// (round 4: also zeroes the weights — a fill launch of its own before)
+// (round 4: also zeroes the weights — a fill launch of its own before; n = 0 when the weights are kept: dcr_graph::h2_weight_valid)
+// The stand-alone head of a pass whose result block is not known to be ready (dcr_graph::h2_head_clean) or whose weights have to
+// be computed: both bucket halves start from zero.
 __global__ void __launch_bounds__(256) k_h2_clear(DevResult *res, int32_t *weight, int64_t n, unsigned *dirty_words, int64_t n_dirty_words) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) weight[i] = 0;
     // (the incremental pass's per-node flags: a full pass recomputes every edge, so they can go now — a fill launch at the
     //  tail of every pass before)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_dirty_words; i += (int64_t)gridDim.x * 256) dirty_words[i] = 0u;
     if (blockIdx.x != 0) return;
-    if (threadIdx.x == 0 && n_dirty_words > 0) res->touched_n = 0;   // (the list of flagged nodes goes with the flags)
-    if (threadIdx.x < 8) res->misc[threadIdx.x] = 0;
-    if (threadIdx.x < H2_NB) {
-        res->h2_bucket[threadIdx.x] = 0;
-        res->h2_fill[threadIdx.x] = 0;
-    }
-    if (threadIdx.x < H2_CLASSES) res->h2_count[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        res->h2_status = 0;
-        res->h2_retry = 0;
-        for (int p = 0; p < 2; ++p) res->h2_ntask[p] = res->h2_ncand[p] = res->h2_npart[p] = res->h2_ncand_done[p] = 0;
-        for (int c = 0; c < 6; ++c) res->h2_failed[c] = 0;
-        res->h2_fallback = 0;
-        res->flag_too_big = 0;
-    }
+    h2_clear_result(res, (int)threadIdx.x, 0, n_dirty_words > 0);
+    h2_clear_result(res, (int)threadIdx.x, 1, n_dirty_words > 0);
 }
 
 // the records of the nodes on the retry list start from zero again (a split node's partitions add into them)
@@ -2119,7 +2167,11 @@ bool h2_grow_pools(dcr_graph *g) {
 }
 
 static int ensure_h2(dcr_graph *g) {
-    DCR_TRY(dev_regrow(&g->h2_weight, &g->h2_weight_cap, g->n + 64));
+    {
+        const int32_t *before = g->h2_weight;
+        DCR_TRY(dev_regrow(&g->h2_weight, &g->h2_weight_cap, g->n + 64));
+        if (g->h2_weight != before) g->h2_weight_valid = false;  // a new array: k_h2_weight fills it
+    }
     DCR_TRY(dev_regrow(&g->h2_rec, &g->h2_rec_cap, g->cap_total + 64));
     // edge set: at most cap_total / 2 undirected edges, load <= 1/2
     int bits = 10;
@@ -2218,26 +2270,42 @@ int launch_curvature_pass_h2(dcr_graph *g) {
                &dr->h2_ncand_done[0], g->dres, g->h2_weight, 0u, lists_L, es};  // pool 0: the split class and the retry launch
     const H2Tasks tkM{g->h2_task + tcap, g->h2_cand + ccap, g->h2_part + pcap, tcap, ccap, pcap, &dr->h2_ntask[1], &dr->h2_ncand[1],
                       &dr->h2_npart[1], &dr->h2_ncand_done[1], g->dres, g->h2_weight, 0u, lists_M, es};  // pool 1: class M
-    {
-        const int64_t cb = (g->n + 255) / 256;
-        // (dirty: n bytes, allocated in whole words? — only the whole words are zeroed here, the caller's fill takes the rest)
-        const bool whole = g->n % 4 == 0;
-        hipLaunchKernelGGL(k_h2_clear, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->dres, g->h2_weight,
-                           g->n, reinterpret_cast<unsigned *>(g->dirty), whole ? g->n / 4 : (int64_t)0);
-        g->h2_cleared_dirty = whole;
-    }
+    // The head of the pass.  Steady state (the weights are kept by the edit kernels and the last pass left the result block
+    // ready): the two plan kernels and nothing else, they clear what has to be cleared on their way.  Otherwise the stand-alone
+    // k_h2_clear first (both bucket halves, and the weights when they have to be computed), k_h2_weight if so, the plan kernels
+    // and k_h2_retry_zero.  Like SdrfScratch::table_dirty, h2_head_clean is dropped here and set again once everything that
+    // makes it true is enqueued; whoever reads a status behind the pass drops it again (curvature_pass_impl).
     const int64_t sblocks = (g->cap_total + 255) / 256;
-    if (sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight);
     const int64_t pblocks = (g->n + H2_PLAN_THREADS - 1) / H2_PLAN_THREADS;
+    // (dirty: n bytes, allocated in whole words? — only the whole words are zeroed here, the caller's fill takes the rest)
+    const bool whole = g->n % 4 == 0;
+    unsigned *dirty_words = reinterpret_cast<unsigned *>(g->dirty);
+    const int64_t n_dirty_words = whole ? g->n / 4 : (int64_t)0;
+    const bool run_weight = !g->h2_weight_valid;
+    const bool fast_head = !run_weight && g->h2_head_clean && pblocks > 0;
+    const int parity = g->h2_parity & 1;
+    g->h2_head_clean = false;
+    if (!fast_head) {
+        const int64_t cb = (g->n + 255) / 256;
+        hipLaunchKernelGGL(k_h2_clear, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->dres, g->h2_weight,
+                           run_weight ? g->n : (int64_t)0, dirty_words, n_dirty_words);
+        if (run_weight && sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight);
+        g->h2_weight_valid = true;  // (from here on the edit kernels keep them)
+    }
+    g->h2_cleared_dirty = whole;
     if (pblocks > 0) {
         hipLaunchKernelGGL(k_h2_plan<0>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight, L,
-                           g->dres);
+                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec);
         hipLaunchKernelGGL(k_h2_plan<1>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight, L,
-                           g->dres);
+                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec);
     }
-    // records of split nodes are accumulated with atomics: start from zero
-    hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4],
-                       g->h2_rec);
+    // records of split nodes are accumulated with atomics: start from zero (the fast head: k_h2_plan<1> has done it)
+    if (!fast_head)
+        hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4],
+                           g->h2_rec);
+    g->h2_parity = 1 - parity;  // (the half of this pass is used; the other one is zero: k_h2_clear, or k_h2_plan<0> of this pass)
+    g->h2_weight_launches += run_weight ? 1 : 0;
+    g->h2_clear_launches += fast_head ? 0 : 1;
     // The stream each class kernel is launched on ({split class, class M, wave classes 2, 1, 0}: an index into `pool`; kernels on
     // one stream run one after the other).  The split class stays on the main stream, launched first: its workgroups need most
     // of a CU's LDS and find no CU free once the other kernels are resident (measured: started 60 us late, finished last).
@@ -2347,6 +2415,34 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     g->ext_part_n = (int)fblocks * 4;
     g->ext_part_valid = true;  // (dropped again by the caller if the pass reports a failure, and by every edit)
     DCR_HIP(hipGetLastError());
+    g->h2_head_clean = pblocks > 0;  // (everything that leaves the other bucket half zero is enqueued)
+    return DCR_OK;
+}
+
+// diagnostic: W recomputed from the rows into an array of its own and compared with the kept one (bit 31 aside)
+__global__ void __launch_bounds__(256) k_h2_weight_diff(const int32_t *kept, const int32_t *fresh, int64_t n, int32_t *out) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        bad += (kept[i] & 0x7FFFFFFF) != fresh[i];
+    if (bad) atomicAdd(out, bad);
+}
+
+int h2_weight_check(dcr_graph *g, int64_t *mismatches) {
+    *mismatches = -1;
+    if (!g->h2_weight_valid || !g->h2_weight) return DCR_OK;
+    DCR_TRY(dev_regrow(&g->h2_weight_chk, &g->h2_weight_chk_cap, g->n + 64));
+    int32_t *fresh = g->h2_weight_chk, *count = g->h2_weight_chk + g->n;  // (the array has 64 words of slack)
+    DCR_HIP(hipMemsetAsync(fresh, 0, sizeof(int32_t) * (size_t)(g->n + 1), g->stream));
+    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
+    const int64_t sblocks = (g->cap_total + 255) / 256, cb = (g->n + 255) / 256;
+    if (sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, fresh);
+    hipLaunchKernelGGL(k_h2_weight_diff, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->h2_weight, fresh,
+                       g->n, count);
+    DCR_HIP(hipGetLastError());
+    int32_t bad = 0;
+    DCR_HIP(hipMemcpyAsync(&bad, count, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipStreamSynchronize(g->stream));
+    *mismatches = bad;
     return DCR_OK;
 }
 

@@ -69,6 +69,24 @@ __device__ inline void wave_erase(int32_t *row, double *crow, int deg, int pos, 
     }
 }
 
+// The two-hop pass's node weights W(x) = sum of deg(k) over k in N(x) (dcr_bfc_h2.hip: k_h2_weight), kept current by the edit
+// kernels.  Called by `nthreads` threads of one workgroup AFTER the edit of {u,v} is in the rows and visible to them.  dir = +1
+// behind an add (the new entry is the last of either row and is skipped), -1 behind a removal (neither row holds the other any
+// more): one for every other member of N(u) and of N(v), a common neighbour gets both; the endpoints gain or lose the other's
+// degree as it is with the edge in place.  Integer atomics: exact in any order; bit 31 (the retry mark of the last pass) is never
+// reached by a carry, 0 <= W < 2^31 before and after.
+__device__ inline void dev_weight_edit(const int2 *rowinfo, const int32_t *col, int32_t *weight, int32_t u, int32_t v, int dir,
+                                       int tid, int nthreads) {
+    const int2 ru = rowinfo[u], rv = rowinfo[v];
+    const int nu = dir > 0 ? ru.y - 1 : ru.y, nv = dir > 0 ? rv.y - 1 : rv.y;
+    for (int i = tid; i < nu; i += nthreads) atomicAdd(&weight[col[ru.x + i]], dir);
+    for (int i = tid; i < nv; i += nthreads) atomicAdd(&weight[col[rv.x + i]], dir);
+    if (tid == 0) {
+        atomicAdd(&weight[u], dir > 0 ? rv.y : -(rv.y + 1));
+        atomicAdd(&weight[v], dir > 0 ? ru.y : -(ru.y + 1));
+    }
+}
+
 __device__ void dev_remove_edge(int2 *rowinfo, int32_t *col, double *curv, int32_t u, int32_t v, int lane,
                                 int *status, DevResult *res) {
     int2 ru = rowinfo[u], rv = rowinfo[v];
@@ -123,20 +141,32 @@ __device__ inline void dev_add_edge(int2 *rowinfo, const int32_t *rowcap, int32_
 }
 
 __global__ void __launch_bounds__(64) k_add_edge(int2 *rowinfo, const int32_t *rowcap, int32_t *col, int32_t u,
-                                                 int32_t v, DevResult *res) {
+                                                 int32_t v, DevResult *res, int32_t *weight) {
     dev_add_edge(rowinfo, rowcap, col, u, v, res, threadIdx.x);
+    if (!weight) return;
+    __threadfence_block();
+    __syncthreads();
+    if (u == -2 && res->draw_status == 0) {  // (as dev_add_edge read it; with another draw status the add left status 3)
+        u = res->cand_i;
+        v = res->cand_j;
+    }
+    if (u >= 0 && res->add_status == 0) dev_weight_edit(rowinfo, col, weight, u, v, +1, threadIdx.x, 64);
 }
 
 __global__ void __launch_bounds__(64) k_remove_edge(int2 *rowinfo, int32_t *col, double *curv, int32_t u, int32_t v,
-                                                    DevResult *res) {
+                                                    DevResult *res, int32_t *weight) {
     int st = 0;
     dev_remove_edge(rowinfo, col, curv, u, v, threadIdx.x, &st, res);
     if (threadIdx.x == 0) res->misc[0] = st;
+    if (!weight) return;
+    __threadfence_block();
+    __syncthreads();
+    if (res->misc[0] == 0) dev_weight_edit(rowinfo, col, weight, u, v, -1, threadIdx.x, 64);
 }
 
 // tail of an SDRF iteration: remove the arg-max edge iff its (stale) curvature exceeds the bound
 __global__ void __launch_bounds__(64) k_remove_if_above(int2 *rowinfo, int32_t *col, double *curv, DevResult *res,
-                                                        double bound) {
+                                                        double bound, int32_t *weight) {
     if (res->add_status == 1 || res->add_status == 3) return;  // add overflowed (host re-lays out and replays the tail) / no draw
     int lane = threadIdx.x;
     int32_t u = res->ext_u, v = res->ext_v;
@@ -148,12 +178,18 @@ __global__ void __launch_bounds__(64) k_remove_if_above(int2 *rowinfo, int32_t *
         }
         return;
     }
+    __shared__ int removed;
     int st = 0;
     dev_remove_edge(rowinfo, col, curv, u, v, lane, &st, res);
     if (lane == 0) {
         res->removed_u = u;
         res->removed_v = v;
+        removed = st == 0;
     }
+    if (!weight) return;
+    __threadfence_block();
+    __syncthreads();
+    if (removed) dev_weight_edit(rowinfo, col, weight, u, v, -1, lane, 64);
 }
 
 // Incremental curvature: the per-node flags behind edge_dirty() (dcr_bfc_common.h).  Edit number `edit` (0..2) of the
@@ -207,7 +243,8 @@ __global__ void __launch_bounds__(256) k_mark_dirty_ext(const int2 *rowinfo, con
 // arg-max edge iff above the bound.  Four launches of one or four waves each cost their launch gaps, not their work.
 __global__ void __launch_bounds__(256) k_sdrf_tail(int2 *rowinfo, const int32_t *rowcap, int32_t *col, double *curv, uint8_t *dirty,
                                                     DevResult *res, int32_t u, int32_t v, int edit_add, int do_remove, double bound,
-                                                    int edit_rem, int32_t *touched, int32_t tcap) {
+                                                    int edit_rem, int32_t *touched, int32_t tcap, int32_t *weight) {
+    __shared__ int removed;
     const int tid = threadIdx.x;
     if (tid < 64) dev_add_edge(rowinfo, rowcap, col, u, v, res, tid);
     __threadfence_block();   // (one workgroup: its waves share the CU's cache, nothing has to reach the L2 before the barrier;
@@ -220,27 +257,38 @@ __global__ void __launch_bounds__(256) k_sdrf_tail(int2 *rowinfo, const int32_t 
         av = res->cand_j;
     }
     if (mark) dev_mark_dirty(rowinfo, col, dirty, au, av, edit_add, tid, 256, touched, tcap, res);
-    if (!do_remove) return;
     const int st_add = res->add_status;
+    // (the weights: all four waves, next to the flags — the rows are the ones just walked)
+    if (weight && mark && au >= 0 && st_add == 0) dev_weight_edit(rowinfo, col, weight, au, av, +1, tid, 256);
+    if (!do_remove) return;
     if (st_add == 1 || st_add == 3) return;  // (uniform) add overflowed: replayed after a re-layout / no draw
     const bool doit = res->ext_slot >= 0 && res->ext_val > bound;
     if (doit) dev_mark_dirty(rowinfo, col, dirty, res->ext_u, res->ext_v, edit_rem, tid, 256, touched, tcap, res);
     __threadfence_block();
     __syncthreads();
-    if (tid >= 64) return;
-    if (!doit) {
+    if (!doit) {  // (uniform)
         if (tid == 0) {
             res->removed_u = -1;
             res->removed_v = -1;
         }
         return;
     }
-    int st = 0;
-    dev_remove_edge(rowinfo, col, curv, res->ext_u, res->ext_v, tid, &st, res);
-    if (tid == 0) {
-        res->removed_u = res->ext_u;
-        res->removed_v = res->ext_v;
+    if (tid >= 64 && !weight) return;
+    const int32_t xu = res->ext_u, xv = res->ext_v;
+    if (tid < 64) {
+        int st = 0;
+        dev_remove_edge(rowinfo, col, curv, xu, xv, tid, &st, res);
+        if (tid == 0) {
+            res->removed_u = xu;
+            res->removed_v = xv;
+            removed = st == 0;
+        }
     }
+    if (!weight) return;
+    // (waves 1-3 stayed for this: the two rows once more, four waves wide, behind the removal)
+    __threadfence_block();
+    __syncthreads();
+    if (removed) dev_weight_edit(rowinfo, col, weight, xu, xv, -1, tid, 256);
 }
 
 __global__ void __launch_bounds__(64) k_has_edge(const int2 *rowinfo, const int32_t *col, int32_t u, int32_t v,
@@ -280,14 +328,15 @@ __global__ void k_relayout(const int2 *old_info, const int32_t *old_col, const d
 void launch_add_edge(dcr_graph *g, int32_t u, int32_t v) {
     g->h2_eset_pending += 1;
     g->ext_part_valid = false;
-    hipLaunchKernelGGL(k_add_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->rowcap, g->col, u, v, g->dres);
+    hipLaunchKernelGGL(k_add_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->rowcap, g->col, u, v, g->dres,
+                       h2_kept_weight(g));
 }
 
 void launch_sdrf_tail(dcr_graph *g, int32_t u, int32_t v, int edit_add, int do_remove, double bound, int edit_rem) {
     g->h2_eset_pending += 2;
     g->ext_part_valid = false;
     hipLaunchKernelGGL(k_sdrf_tail, dim3(1), dim3(256), 0, g->stream, g->rowinfo, g->rowcap, g->col, g->curv, g->dirty, g->dres, u, v,
-                       edit_add, do_remove, bound, edit_rem, g->touched, (int32_t)g->n);
+                       edit_add, do_remove, bound, edit_rem, g->touched, (int32_t)g->n, h2_kept_weight(g));
 }
 
 void launch_remove_if_above(dcr_graph *g, double bound, int edit) {
@@ -296,7 +345,8 @@ void launch_remove_if_above(dcr_graph *g, double bound, int edit) {
     // flag the neighbourhood while the edge is still there, then remove it
     hipLaunchKernelGGL(k_mark_dirty_ext, dim3(1), dim3(256), 0, g->stream, g->rowinfo, g->col, g->dirty, g->dres, bound,
                        edit, g->touched, (int32_t)g->n);
-    hipLaunchKernelGGL(k_remove_if_above, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, g->dres, bound);
+    hipLaunchKernelGGL(k_remove_if_above, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, g->dres, bound,
+                       h2_kept_weight(g));
 }
 
 void launch_mark_dirty(dcr_graph *g, int32_t u, int32_t v, int edit) {
@@ -502,7 +552,7 @@ int dcr_graph_destroy(dcr_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *dev_ptrs[] = {g->rowinfo, g->rowcap, g->col, g->slot_row, g->curv, g->dres, g->dirty, g->nc_units[0], g->nc_units[1], g->nc_units[2],
                         g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_queues, g->giant_list,
-                        g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight,
+                        g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight, g->h2_weight_chk,
                         g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
                         g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists};
     for (void *p : dev_ptrs)
@@ -577,7 +627,8 @@ int dcr_graph_remove_edge(dcr_graph *g, int32_t u, int32_t v) {
     launch_mark_dirty(g, u, v, g->pending_edits++);
     g->h2_eset_pending += 1;
     g->ext_part_valid = false;
-    hipLaunchKernelGGL(k_remove_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, u, v, g->dres);
+    hipLaunchKernelGGL(k_remove_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, u, v, g->dres,
+                       h2_kept_weight(g));
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
     if (g->hres->misc[0] != 0) DCR_FAIL(DCR_ENOTFOUND, "edge not in graph");

@@ -73,9 +73,11 @@ struct DevResult {
     int32_t draw_status;
     int32_t draw_pad;
     int32_t misc[8];  // scratch: has_edge/remove status, and the kernels' invariant guard record
-    // two-hop pass (dcr_bfc_h2.hip): units per (class, weight bucket), placement cursors, units per class
-    int32_t h2_bucket[24];
-    int32_t h2_fill[24];
+    // two-hop pass (dcr_bfc_h2.hip): units per (class, weight bucket), placement cursors, units per class.  Two halves, used in turn
+    // (the parity of the pass, dcr_graph::h2_parity): the plan kernels count and place in one half, the first of them leaves the
+    // other half zero for the next pass
+    int32_t h2_bucket[2][24];
+    int32_t h2_fill[2][24];
     int32_t h2_count[5];
     int32_t h2_failed[6];  // diagnostic: nodes whose tables filled up, per class (5: on the retry list itself)
     // triangle step, one pool per block class (0: the split class and the retry launch, 1: class M), so that the candidates of
@@ -274,6 +276,17 @@ struct dcr_graph {
     uint4 *h2_rec = nullptr;          // [cap_total] per directed slot {|sq| on the far side, max count, triangles, reverse slot}
     int64_t h2_rec_cap = 0;
     int64_t h2_weight_cap = 0;
+    // h2_weight holds W of the CURRENT rows (bit 31 aside): k_h2_weight has filled this array and every writer of a degree since
+    // has kept it (dev_add_edge / dev_remove_edge, the only writers behind dcr_graph_create; relayout() moves rows and changes no
+    // degree).  False for a new graph and whenever the array is (re)allocated; a pass then runs k_h2_weight.
+    bool h2_weight_valid = false;
+    // the head of the last two-hop launch left the result block ready for a head without k_h2_clear: the bucket half of the other
+    // parity is zero.  False for a new graph (fresh DevResult) and behind a pass that reported a status or an invariant.
+    bool h2_head_clean = false;
+    int h2_parity = 0;                 // the bucket half the next pass counts in
+    int h2_weight_launches = 0, h2_clear_launches = 0;  // of the h2_launches: those that ran k_h2_weight / the stand-alone k_h2_clear
+    int32_t *h2_weight_chk = nullptr;  // dcr_h2_weight_check: W recomputed (diagnostic, allocated on first use)
+    int64_t h2_weight_chk_cap = 0;
     unsigned long long *h2_eset = nullptr;  // every undirected edge as one 64-bit key (open addressing), rebuilt per pass
     int h2_eset_bits = 0;
     bool h2_expect_retry = false;      // some pass of this graph had nodes on the retry list: the retry stage is launched with every pass
@@ -364,7 +377,10 @@ int launch_curvature_pass(dcr_graph *g, int curv_type, bool incremental, bool no
 int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental, bool edge_by_edge, bool list_by_rows);
 // dcr_bfc_h2.hip
 int launch_curvature_pass_h2(dcr_graph *g);
+// what the edit kernels get: the weights they keep current, or null while there are none to keep
+inline int32_t *h2_kept_weight(dcr_graph *g) { return g->h2_weight_valid ? g->h2_weight : nullptr; }
 bool h2_grow_pools(dcr_graph *g);
+int h2_weight_check(dcr_graph *g, int64_t *mismatches);  // -1: no kept weights; else the nodes whose kept W differs from the rows' 
 
 // dcr_analysis.hip
 void analysis_destroy(dcr_graph *g);  // frees g->analysis and what it holds

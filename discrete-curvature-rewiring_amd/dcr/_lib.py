@@ -105,6 +105,7 @@ SIGNATURES = {
     'dcr_pass_engine': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     'dcr_h2_stats': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
     'dcr_h2_launch_info': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
+    'dcr_h2_weight_check': (ctypes.c_int, [_vp, _i64p]),
     'dcr_pass_plan': (ctypes.c_int, [_i64, _i64, _i64, _f64, _i32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                      ctypes.POINTER(ctypes.c_int), _f64p]),

@@ -708,9 +708,22 @@ class DcrGraph:
     def h2_launch_info(self):
         """How the last curvature pass call ran the two-hop pass: times it was launched (0: another engine ran), and whether
         the last launch carried the retry stage and the triangle stage."""
-        out = (ctypes.c_int32 * 3)()
+        out = (ctypes.c_int32 * 5)()
         check(lib().dcr_h2_launch_info(self._h, out))
         return {'launches': out[0], 'retry_stage': bool(out[1]), 'triangle_stage': bool(out[2])}
+
+    def h2_head_info(self):
+        """The heads of the two-hop launches ``h2_launch_info`` counts: how many of them ran the weight kernel (the node weights
+        were not kept from the last pass) and the stand-alone clear (the full head, not the two plan kernels alone)."""
+        out = (ctypes.c_int32 * 5)()
+        check(lib().dcr_h2_launch_info(self._h, out))
+        return {'weight_kernels': out[3], 'clear_kernels': out[4]}
+
+    def h2_weight_check(self):
+        """Nodes whose kept two-hop weight differs from a recomputation from the rows (-1: no weights are kept yet)."""
+        out = ctypes.c_int64()
+        check(lib().dcr_h2_weight_check(self._h, ctypes.byref(out)))
+        return out.value
 
     def bfc_algorithmic_bytes(self, one_sided=False):
         """SURVEY §8(d) bytes of one BFC pass; ``one_sided``: only the cheaper difference set's rows per edge."""

@@ -135,8 +135,14 @@ int dcr_h2_stats(dcr_graph *g, int32_t out[6]);
 /* How the last dcr_curvature_pass* call ran the two-hop pass: how many times it was launched (0: another engine; more than 1: a
  * launch found that it needed a stage it was launched without, or larger pools, and was run again), and whether the last of the
  * launches carried the retry stage and the triangle stage (k_h2_triangles).  Both stages are left out until a pass of the graph
- * needs them and go with every pass from then on. */
-int dcr_h2_launch_info(dcr_graph *g, int32_t out[3]);
+ * needs them and go with every pass from then on.  out[3], out[4]: how many of the launches ran k_h2_weight (the node weights
+ * were computed from the rows, not kept by the edit kernels) and the stand-alone k_h2_clear (the full head, not the two plan
+ * kernels alone). */
+int dcr_h2_launch_info(dcr_graph *g, int32_t out[5]);
+/* Diagnostic: recomputes the two-hop pass's node weights from the rows and counts the nodes whose kept weight (maintained by the
+ * edit kernels since the last pass that computed them) differs.  *mismatches = -1 while no weights are kept (no two-hop pass
+ * has run on the graph).  Synchronises; no part of a pass. */
+int dcr_h2_weight_check(dcr_graph *g, int64_t *mismatches);
 /* The route a pass with these facts and switches takes (csrc/dcr_pass_route.h: plan_pass, the function every pass calls): no
  * handle, no environment, no GPU.  Facts: nodes, undirected edges, adjacency slots, sum of squared degrees, upper bound on the
  * degrees, edits since the last pass.  Switches: pass_impl 0 automatic / 1 edge / 2 nc / 3 h2 (DCR_PASS), fine_on (DCR_NC_FINE),
