@@ -6,30 +6,23 @@
 // that were written for it, on dense N x N arrays, and they are restated here per column: keep the k largest entries, or the
 // entries >= eps, then divide the kept entries by their sum.
 //
-// The solve: DIF_B columns at a time as DIF_B independent conjugate-gradient iterations in step (not a block CG), from x = 0, in
-// the layout of dcr_resistance.hip: every vector node-major [n][DIF_B], a lane owns two adjacent columns (16-byte loads and
-// stores), DIF_B / 2 lanes cover a node.  Each column has its own step length, beta, |r|^2, step count and frozen flag in device
-// memory (DifCtl).  A column freezes, on the device, in the step where |r| <= tol α (α = |α e_j|), or where p^T M p is not a positive
-// finite number; a frozen column's x, r and p are no longer written.  Every sum runs over rows or nodes in an order that the graph
-// alone fixes and treats all columns alike, so a column's bits depend on its own source node only: not on its column index, not
-// on what else shares the batch (padding included), not on when the others freeze.
+// The solve: COL_B columns at a time by the batched column CG of dcr_analysis.h (the layout, the freeze rule and why a column's bits
+// depend on its own source only, padding and neighbours in the batch notwithstanding, are described there).  DifProblem below
+// is all this file adds to it: the operator's row entry, α e_j as the right-hand side, the stop threshold tol α (α = |α e_j|) and the
+// true residual the close writes.
 //
-// The selection runs on the batch's [n][DIF_B] result where it lies, a workgroup a column.  Values go through the order-preserving
+// The selection runs on the batch's [n][COL_B] result where it lies, a workgroup a column.  Values go through the order-preserving
 // map of fp64 onto uint64 (negative: all bits flipped, else the sign bit set): entries of S are positive, but an entry below the
 // solve's error can come out negative, and the order has to be that of the values whatever the solve left.  Larger value first;
 // among equal bits, the smaller node id first.
 //
 // Kernels (all fp64, no floating-point atomics: per-workgroup partials through the L2, closed in index order by the last arriver):
 //   k_dif_scale      s̃ = 1 / sqrt(deg + 1)
-//   k_dif_start      r = p = α e_j, z = s̃ ⊙ p, x = 0 for all columns
-//   k_dif_matvec<0>  q = M p = p - (1 - α) s̃ ⊙ ((A + I) z) for all columns in one sweep of the rows, through walk_rows in the three
-//                    degree classes with the geometry of the resistance mat-vec (32 lanes a short row, 8 turns, 8 lanes across a
-//                    node); the per-column partials of p^T q; the last arriver sets the step length |r|^2 / p^T q or freezes
-//   k_dif_update     x += a p, r -= a q, partials of the new |r|^2; the last arriver sets beta, counts the step and freezes the
-//                    columns that have converged
-//   k_dif_direction  p = r + beta p, z = s̃ ⊙ p
-//   k_dif_scale_x    z = s̃ ⊙ x, then
-//   k_dif_matvec<1>  w = M x (not stored), partials of |α e_j - w|^2; the last arriver writes the true residual per column
+//   k_col_start<DifProblem>      r = p = α e_j, z = s̃ ⊙ p, x = 0 for all columns
+//   k_col_matvec<DifProblem, 0>  q = M p = p - (1 - α) s̃ ⊙ ((A + I) z): the row's neighbours summed over the scope, the row's own z
+//                    added by the owner lanes; the last arriver sets the step length |r|^2 / p^T q or freezes the column
+//   k_col_update<DifCtl>, k_col_direction<DifCtl>, k_col_scale   as they are in dcr_analysis.h, then
+//   k_col_matvec<DifProblem, 1>  w = M x (not stored), partials of |α e_j - w|^2; the last arriver writes the true residual per column
 //   k_dif_select     top-k: a radix select per column, 8-bit digit histograms in LDS from the top digit down over the keys that
 //                    share the digits chosen so far, until the k-th key and the count above it are known (or a whole bucket is
 //                    kept and no tie is left to break); threshold: the count of keys >= key(eps)
@@ -49,7 +42,7 @@
 // read-back between terms.  The recurrence v_0 = e^-t e_j, v_{k+1} = t / (k + 1) s̃ ⊙ ((A + I)(s̃ ⊙ v_k)), x += v_{k+1} keeps only
 // z = s̃ ⊙ v between terms, in two buffers by turns (z and p of the PageRank layout): other rows read z_in during the sweep.
 //   k_heat_start     x = e^-t e_j, z = s̃ ⊙ x for all columns (padding columns are zero and stay zero)
-//   k_heat_term      one launch a term, the row walk of k_dif_matvec: v = c (s̃_u (Σ z_in[col] + z_in[u])), x[u] += v,
+//   k_heat_term      one launch a term, the row walk and gather of k_col_matvec: v = c (s̃_u (Σ z_in[col] + z_in[u])), x[u] += v,
 //                    z_out[u] = s̃_u v, with c = t / (k + 1) an argument
 //   k_heat_mass      partials of Σ_i r_i x_i per column; the last arriver writes deficit_j = r_j - Σ_i r_i x_i
 // K + 2 launches a batch, then k_dif_select / k_dif_fill as they are.  A column's bits depend on its source, t and K only.
@@ -60,257 +53,59 @@
 
 namespace dcr {
 
-constexpr int DIF_B = 16;                // columns of a batch
-constexpr int DIF_CP = DIF_B / 2;        // lanes across a node: two columns each
-constexpr int DIF_SHORT_LANES = 32;      // lanes of a short row's group
-constexpr int DIF_SHORT_ROWS = 64;       // short rows a workgroup takes: 8 groups x 8 turns
-using DifRows = RowGeom<DIF_SHORT_LANES, DIF_SHORT_ROWS / 8, DIF_CP>;   // the numbers of ResRows (tests/test_diffusion_cpu.py)
-constexpr int DIF_UPDATE_BLOCKS = 1024;  // most workgroups of the element-wise kernels with a reduction
 constexpr int DIF_MAX_GROUPS = 8;        // batches solved side by side in the same launches (blockIdx.y), each on its own
 constexpr int64_t DIF_GROUP_NODES = 65536;  // vectors and control block: as many as keep groups x nodes within this
 
 struct DifCtl {
-    double rr[DIF_B];      // |r|^2 of the recurrence
-    double gain[DIF_B];    // the step length of CG (its "alpha"; α is the teleport probability here)
-    double beta[DIF_B];
-    double resid[DIF_B];   // the closing mat-vec's |α e_j - M x|_2; heat: the deficit r_j - Σ_i r_i x_i
+    ColCg cg;
+    double resid[COL_B];   // the closing mat-vec's |α e_j - M x|_2; heat: the deficit r_j - Σ_i r_i x_i
     double teleport, damp; // α, 1 - α
-    double stop;           // tol α
-    uint64_t thr[DIF_B];   // selection: the threshold key
-    int64_t base[DIF_B];   // where the column's kept entries start in the batch's output
-    int32_t src[DIF_B];    // the source node of each column; -1: padding
-    int32_t frozen[DIF_B];
-    int32_t steps[DIF_B];
-    int32_t take[DIF_B];   // how many of the keys equal to thr are kept, in node order
-    int32_t count[DIF_B];  // kept entries
-    int32_t active;        // columns not frozen
-    unsigned ticket;
+    uint64_t thr[COL_B];   // selection: the threshold key
+    int64_t base[COL_B];   // where the column's kept entries start in the batch's output
+    int32_t src[COL_B];    // the source node of each column; -1: padding
+    int32_t take[COL_B];   // how many of the keys equal to thr are kept, in node order
+    int32_t count[COL_B];  // kept entries
 };
-
-__device__ inline double2 dif_ld2(const double *base, int64_t node, int cp) {
-    return *reinterpret_cast<const double2 *>(base + node * DIF_B + 2 * cp);
-}
-__device__ inline void dif_st2(double *base, int64_t node, int cp, double2 x) {
-    *reinterpret_cast<double2 *>(base + node * DIF_B + 2 * cp) = x;
-}
 
 // the entry of α e_src at `node`
 __device__ inline double dif_rhs(int32_t node, int32_t src, double teleport) { return node == src ? teleport : 0.0; }
 
-// partials part[workgroup][DIF_B] of `count` workgroups: thread t adds those of workgroups t / DIF_CP, + 256 / DIF_CP, ... for its
-// column pair in order, then the workgroup's sum per column pair
-__device__ inline double2 dif_close_partials(const double *part, int count, double2 *sh) {
-    const int cp = threadIdx.x % DIF_CP;
-    double2 acc = make_double2(0.0, 0.0);
-    for (int i = threadIdx.x / DIF_CP; i < count; i += 256 / DIF_CP) {
-        acc.x += ld_agent(part + (int64_t)i * DIF_B + 2 * cp);
-        acc.y += ld_agent(part + (int64_t)i * DIF_B + 2 * cp + 1);
+struct DifProblem {  // M x = α e_j for the column CG of dcr_analysis.h; the host sets the stop threshold tol α
+    using Ctl = DifCtl;
+    static constexpr bool closing_dot = false;  // the close needs |α e_j - M x|^2 only
+    DifCtl *ctl;
+    __device__ auto rhs(int cp) const {
+        const int32_t j0 = ctl->src[2 * cp], j1 = ctl->src[2 * cp + 1];
+        const double teleport = ctl->teleport;
+        return [=](int32_t node, double) { return make_double2(dif_rhs(node, j0, teleport), dif_rhs(node, j1, teleport)); };
     }
-    return block_sum<DIF_CP>(acc, sh);
-}
+    __device__ auto entry() const {  // the row's own z is the I of A + I
+        const double damp = ctl->damp;
+        return [=](int, double v, double su, double acc, double zu) { return v - damp * (su * (acc + zu)); };
+    }
+    __device__ void start(int k, const double *) const { ctl->cg.rr[k] = ctl->src[k] >= 0 ? ctl->teleport * ctl->teleport : 0.0; }
+    __device__ void close(int k, const double *, const double *, double, double dev) const { ctl->resid[k] = ctl->src[k] >= 0 ? sqrt(dev) : 0.0; }
+};
 
-__device__ inline void dif_store_partial(double *part, int block, double2 x) {  // threads 0 .. DIF_CP - 1
-    st_agent(part + (int64_t)block * DIF_B + 2 * threadIdx.x, x.x);
-    st_agent(part + (int64_t)block * DIF_B + 2 * threadIdx.x + 1, x.y);
-}
-
-// ---- scale, start ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dif_scale(const int2 *__restrict__ rowinfo, double *__restrict__ s, int64_t n) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v < n) s[v] = 1.0 / sqrt((double)rowinfo[v].y + 1.0);
 }
 
-__global__ void __launch_bounds__(256) k_dif_start(const double *__restrict__ s, int64_t n, DifCtl *ctl, double *__restrict__ z,
-                                                    double *__restrict__ p, double *__restrict__ r, double *__restrict__ x, int64_t gstride) {
-    const int cp = threadIdx.x % DIF_CP;
-    const int64_t go = (int64_t)blockIdx.y * gstride;  // this group's vectors and control block
-    ctl += blockIdx.y, z += go, p += go, r += go, x += go;
-    const int32_t j0 = ctl->src[2 * cp], j1 = ctl->src[2 * cp + 1];
-    const double teleport = ctl->teleport;
-    const int64_t total = n * DIF_CP;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t node = e / DIF_CP;
-        const double sn = s[node];
-        const double2 c = make_double2(dif_rhs((int32_t)node, j0, teleport), dif_rhs((int32_t)node, j1, teleport));
-        dif_st2(p, node, cp, c);
-        dif_st2(r, node, cp, c);
-        dif_st2(z, node, cp, make_double2(sn * c.x, sn * c.y));
-        dif_st2(x, node, cp, make_double2(0.0, 0.0));
-    }
-    if (blockIdx.x == 0 && threadIdx.x < DIF_B) ctl->rr[threadIdx.x] = ctl->src[threadIdx.x] >= 0 ? teleport * teleport : 0.0;
-}
-
-// ---- mat-vec -----------------------------------------------------------------------------------------------------------------------
-// MODE 0: v = p, q = M p stored, partials of p^T q.  MODE 1: v = x, w = M x not stored, partials of |α e_j - w|^2.
-template <int MODE>
-__global__ void __launch_bounds__(256) k_dif_matvec(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
-                                                     const double *__restrict__ v, const double *__restrict__ z,
-                                                     const double *__restrict__ s, double *__restrict__ q, DifCtl *ctl, double *part,
-                                                     int64_t gstride, int64_t pstride) {
-    __shared__ double2 sh[4 * DIF_CP];
-    const int t = threadIdx.x, cp = t % DIF_CP;
-    const int64_t go = (int64_t)blockIdx.y * gstride;
-    ctl += blockIdx.y, v += go, z += go, q += go, part += (int64_t)blockIdx.y * pstride;
-    const double damp = ctl->damp, teleport = ctl->teleport;
-    int32_t j0 = -1, j1 = -1;
-    if (MODE == 1) {
-        j0 = ctl->src[2 * cp];
-        j1 = ctl->src[2 * cp + 1];
-    }
-    double2 red = make_double2(0.0, 0.0);
-    walk_rows<DifRows>(plan, rowinfo, sh, [=](auto scope, int32_t row, int2 ri, double2 &out) {
-        double2 acc = make_double2(0.0, 0.0);  // (A z)_row
-        for (int j = scope.first(); j < ri.y; j += scope.stride) {
-            const double2 zv = dif_ld2(z, col[ri.x + j], cp);
-            acc.x += zv.x;
-            acc.y += zv.y;
-        }
-        acc = scope.sum(acc);
-        if (!scope.owner()) return;
-        // the row's entry of M v, by the DIF_CP lanes that own the row
-        const double2 vu = dif_ld2(v, row, cp), zu = dif_ld2(z, row, cp);
-        const double su = s[row];
-        double2 w;
-        w.x = vu.x - damp * (su * (acc.x + zu.x));
-        w.y = vu.y - damp * (su * (acc.y + zu.y));
-        if (MODE == 0) {
-            out.x += vu.x * w.x;
-            out.y += vu.y * w.y;
-            dif_st2(q, row, cp, w);
-        } else {
-            const double e0 = dif_rhs(row, j0, teleport) - w.x, e1 = dif_rhs(row, j1, teleport) - w.y;
-            out.x += e0 * e0;
-            out.y += e1 * e1;
-        }
-    }, red);
-    red = block_sum<DIF_CP>(red, sh);
-    if (t < DIF_CP) dif_store_partial(part, blockIdx.x, red);
-    if (!last_arriver(&ctl->ticket, (unsigned)gridDim.x)) return;
-    const double2 a = dif_close_partials(part, gridDim.x, sh);
-    if (t < DIF_CP) {
-        for (int h = 0; h < 2; ++h) {
-            const int k = 2 * t + h;
-            const double sum = h ? a.y : a.x;
-            if (MODE == 0) {
-                if (ctl->frozen[k]) continue;
-                if (sum > 0.0 && sum <= 1.79769313486231570815e308) {
-                    ctl->gain[k] = ctl->rr[k] / sum;
-                } else {  // p^T M p zero, negative or not finite: nothing more to gain along p
-                    ctl->gain[k] = 0.0;
-                    ctl->frozen[k] = 1;
-                }
-            } else {
-                ctl->resid[k] = ctl->src[k] >= 0 ? sqrt(sum) : 0.0;
-            }
-        }
-    }
-    if (t == 0) __hip_atomic_store(&ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- update, direction -------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_dif_update(int64_t n, DifCtl *ctl, const double *__restrict__ p, const double *__restrict__ q,
-                                                     double *__restrict__ x, double *__restrict__ r, double *part, int64_t gstride,
-                                                     int64_t pstride) {
-    __shared__ double2 sh[4 * DIF_CP];
-    const int t = threadIdx.x, cp = t % DIF_CP;
-    const int64_t go = (int64_t)blockIdx.y * gstride;
-    ctl += blockIdx.y, p += go, q += go, x += go, r += go, part += (int64_t)blockIdx.y * pstride;
-    const double a0 = ctl->gain[2 * cp], a1 = ctl->gain[2 * cp + 1];
-    const bool f0 = ctl->frozen[2 * cp] != 0, f1 = ctl->frozen[2 * cp + 1] != 0;
-    double2 acc = make_double2(0.0, 0.0);
-    if (!(f0 && f1)) {
-        const int64_t total = n * DIF_CP;
-        for (int64_t e = (int64_t)blockIdx.x * 256 + t; e < total; e += (int64_t)gridDim.x * 256) {
-            const int64_t node = e / DIF_CP;
-            const double2 pv = dif_ld2(p, node, cp), qv = dif_ld2(q, node, cp);
-            double2 xv = dif_ld2(x, node, cp), rv = dif_ld2(r, node, cp);
-            if (!f0) {
-                xv.x += a0 * pv.x;
-                rv.x -= a0 * qv.x;
-            }
-            if (!f1) {
-                xv.y += a1 * pv.y;
-                rv.y -= a1 * qv.y;
-            }
-            dif_st2(x, node, cp, xv);
-            dif_st2(r, node, cp, rv);
-            acc.x += rv.x * rv.x;
-            acc.y += rv.y * rv.y;
-        }
-    }
-    acc = block_sum<DIF_CP>(acc, sh);
-    if (t < DIF_CP) dif_store_partial(part, blockIdx.x, acc);
-    if (!last_arriver(&ctl->ticket, (unsigned)gridDim.x)) return;
-    const double2 a = dif_close_partials(part, gridDim.x, sh);
-    if (t < DIF_CP) {
-        for (int h = 0; h < 2; ++h) {
-            const int k = 2 * t + h;
-            if (ctl->frozen[k]) continue;
-            const double rr = h ? a.y : a.x;
-            ctl->beta[k] = rr / ctl->rr[k];
-            ctl->rr[k] = rr;
-            ctl->steps[k] += 1;
-            if (!(rr <= 1.79769313486231570815e308) || sqrt(rr) <= ctl->stop) ctl->frozen[k] = 1;
-        }
-    }
-    __syncthreads();
-    if (t == 0) {
-        int active = 0;
-        for (int k = 0; k < DIF_B; ++k) active += ctl->frozen[k] == 0;
-        ctl->active = active;
-        __hip_atomic_store(&ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_dif_direction(int64_t n, const DifCtl *__restrict__ ctl, const double *__restrict__ s,
-                                                        const double *__restrict__ r, double *__restrict__ p, double *__restrict__ z,
-                                                        int64_t gstride) {
-    const int cp = threadIdx.x % DIF_CP;
-    const int64_t go = (int64_t)blockIdx.y * gstride;
-    ctl += blockIdx.y, r += go, p += go, z += go;
-    const double b0 = ctl->beta[2 * cp], b1 = ctl->beta[2 * cp + 1];
-    const bool f0 = ctl->frozen[2 * cp] != 0, f1 = ctl->frozen[2 * cp + 1] != 0;
-    if (f0 && f1) return;
-    const int64_t total = n * DIF_CP;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t node = e / DIF_CP;
-        const double2 rv = dif_ld2(r, node, cp);
-        double2 pv = dif_ld2(p, node, cp);
-        if (!f0) pv.x = rv.x + b0 * pv.x;
-        if (!f1) pv.y = rv.y + b1 * pv.y;
-        const double sn = s[node];
-        dif_st2(p, node, cp, pv);
-        dif_st2(z, node, cp, make_double2(sn * pv.x, sn * pv.y));
-    }
-}
-
-__global__ void __launch_bounds__(256) k_dif_scale_x(int64_t n, const double *__restrict__ s, const double *__restrict__ x,
-                                                      double *__restrict__ z, int64_t gstride) {
-    const int cp = threadIdx.x % DIF_CP;
-    x += (int64_t)blockIdx.y * gstride, z += (int64_t)blockIdx.y * gstride;
-    const int64_t total = n * DIF_CP;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t node = e / DIF_CP;
-        const double sn = s[node];
-        const double2 xv = dif_ld2(x, node, cp);
-        dif_st2(z, node, cp, make_double2(sn * xv.x, sn * xv.y));
-    }
-}
-
 // ---- heat kernel -------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_heat_start(const double *__restrict__ s, int64_t n, const DifCtl *__restrict__ ctl, double start,
                                                      double *__restrict__ z, double *__restrict__ x, int64_t gstride) {
-    const int cp = threadIdx.x % DIF_CP;
+    const int cp = threadIdx.x % COL_CP;
     const int64_t go = (int64_t)blockIdx.y * gstride;
     ctl += blockIdx.y, z += go, x += go;
     const int32_t j0 = ctl->src[2 * cp], j1 = ctl->src[2 * cp + 1];
-    const int64_t total = n * DIF_CP;
+    const int64_t total = n * COL_CP;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t node = e / DIF_CP;
+        const int64_t node = e / COL_CP;
         const double sn = s[node];
         const double2 c = make_double2(dif_rhs((int32_t)node, j0, start), dif_rhs((int32_t)node, j1, start));  // e^-t e_src
-        dif_st2(x, node, cp, c);
-        dif_st2(z, node, cp, make_double2(sn * c.x, sn * c.y));
+        st2(x, node, cp, c);
+        st2(z, node, cp, make_double2(sn * c.x, sn * c.y));
     }
 }
 
@@ -319,56 +114,50 @@ __global__ void __launch_bounds__(256) k_heat_start(const double *__restrict__ s
 __global__ void __launch_bounds__(256) k_heat_term(RowPlan plan, const int2 *__restrict__ rowinfo, const int32_t *__restrict__ col,
                                                     const double *__restrict__ z_in, const double *__restrict__ s, double c,
                                                     double *__restrict__ z_out, double *__restrict__ x, int64_t gstride) {
-    __shared__ double2 sh[4 * DIF_CP];
-    const int cp = threadIdx.x % DIF_CP;
+    __shared__ double2 sh[4 * COL_CP];
+    const int cp = threadIdx.x % COL_CP;
     const int64_t go = (int64_t)blockIdx.y * gstride;
     z_in += go, z_out += go, x += go;
-    walk_rows<DifRows>(plan, rowinfo, sh, [=](auto scope, int32_t row, int2 ri) {
-        double2 acc = make_double2(0.0, 0.0);  // (A z)_row
-        for (int j = scope.first(); j < ri.y; j += scope.stride) {
-            const double2 zv = dif_ld2(z_in, col[ri.x + j], cp);
-            acc.x += zv.x;
-            acc.y += zv.y;
-        }
-        acc = scope.sum(acc);
+    walk_rows<ColRows>(plan, rowinfo, sh, [=](auto scope, int32_t row, int2 ri) {
+        const double2 acc = gather(scope, col, ri, z_in, cp);
         if (!scope.owner()) return;
-        const double2 zu = dif_ld2(z_in, row, cp);
+        const double2 zu = ld2(z_in, row, cp);
         const double su = s[row];
         const double2 v = make_double2(c * (su * (acc.x + zu.x)), c * (su * (acc.y + zu.y)));
-        double2 xu = dif_ld2(x, row, cp);
+        double2 xu = ld2(x, row, cp);
         xu.x += v.x;
         xu.y += v.y;
-        dif_st2(x, row, cp, xu);
-        dif_st2(z_out, row, cp, make_double2(su * v.x, su * v.y));
+        st2(x, row, cp, xu);
+        st2(z_out, row, cp, make_double2(su * v.x, su * v.y));
     });
 }
 
 __global__ void __launch_bounds__(256) k_heat_mass(const int2 *__restrict__ rowinfo, int64_t n, DifCtl *ctl, const double *__restrict__ x,
                                                     double *part, int64_t gstride, int64_t pstride) {
-    __shared__ double2 sh[4 * DIF_CP];
-    const int t = threadIdx.x, cp = t % DIF_CP;
+    __shared__ double2 sh[4 * COL_CP];
+    const int t = threadIdx.x, cp = t % COL_CP;
     ctl += blockIdx.y, x += (int64_t)blockIdx.y * gstride, part += (int64_t)blockIdx.y * pstride;
     double2 acc = make_double2(0.0, 0.0);
-    const int64_t total = n * DIF_CP;
+    const int64_t total = n * COL_CP;
     for (int64_t e = (int64_t)blockIdx.x * 256 + t; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t node = e / DIF_CP;
+        const int64_t node = e / COL_CP;
         const double rn = sqrt((double)rowinfo[node].y + 1.0);
-        const double2 xv = dif_ld2(x, node, cp);
+        const double2 xv = ld2(x, node, cp);
         acc.x += rn * xv.x;
         acc.y += rn * xv.y;
     }
-    acc = block_sum<DIF_CP>(acc, sh);
-    if (t < DIF_CP) dif_store_partial(part, blockIdx.x, acc);
-    if (!last_arriver(&ctl->ticket, (unsigned)gridDim.x)) return;
-    const double2 a = dif_close_partials(part, gridDim.x, sh);
-    if (t < DIF_CP) {
+    acc = block_sum<COL_CP>(acc, sh);
+    if (t < COL_CP) store_partial(part, blockIdx.x, acc);
+    if (!last_arriver(&ctl->cg.ticket, (unsigned)gridDim.x)) return;
+    const double2 a = close_partials(part, gridDim.x, sh);
+    if (t < COL_CP) {
         for (int h = 0; h < 2; ++h) {
             const int k = 2 * t + h;
             const int32_t j = ctl->src[k];
             ctl->resid[k] = j >= 0 ? sqrt((double)rowinfo[j].y + 1.0) - (h ? a.y : a.x) : 0.0;
         }
     }
-    if (t == 0) __hip_atomic_store(&ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) __hip_atomic_store(&ctl->cg.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- selection ---------------------------------------------------------------------------------------------------------------------
@@ -412,7 +201,7 @@ __global__ void __launch_bounds__(256) k_dif_select(const double *__restrict__ x
     if (mode == 1) {
         const uint64_t thr = ctl->thr[c];
         int mine = 0, total;
-        for (int64_t i = t; i < n; i += 256) mine += dif_key(x[i * DIF_B + c]) >= thr;
+        for (int64_t i = t; i < n; i += 256) mine += dif_key(x[i * COL_B + c]) >= thr;
         dif_excl_scan(mine, sh, total);
         if (t == 0) {
             ctl->count[c] = total;
@@ -426,7 +215,7 @@ __global__ void __launch_bounds__(256) k_dif_select(const double *__restrict__ x
         hist[t] = 0;
         __syncthreads();
         for (int64_t i = t; i < n; i += 256) {
-            const uint64_t key = dif_key(x[i * DIF_B + c]);
+            const uint64_t key = dif_key(x[i * COL_B + c]);
             if ((key & mask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
         }
         __syncthreads();
@@ -476,7 +265,7 @@ __global__ void __launch_bounds__(256) k_dif_fill(const double *__restrict__ x, 
     for (int64_t first = 0; first < n; first += 256) {
         const int64_t i = first + t;
         const bool valid = i < n;
-        const double v = valid ? x[i * DIF_B + c] : 0.0;
+        const double v = valid ? x[i * COL_B + c] : 0.0;
         const uint64_t key = dif_key(v);
         const bool eq = valid && key == thr;
         int n_eq, n_keep;
@@ -538,47 +327,48 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
     const int64_t n = g->n;
     RowPlan plan;
     DCR_TRY(build_row_plan(g, &plan, nullptr));
-    const int nb_mv = (int)row_grid<DifRows>(plan);
-    const int nb_el = (int)std::min<int64_t>(DIF_UPDATE_BLOCKS, blocks_of(n * DIF_CP));
+    const int nb_mv = (int)row_grid<ColRows>(plan);
+    const int nb_el = (int)std::min<int64_t>(COL_UPDATE_BLOCKS, blocks_of(n * COL_CP));
     // batches of a launch: a small graph does not fill the device with one
-    const int64_t batches = (P + DIF_B - 1) / DIF_B;
+    const int64_t batches = (P + COL_B - 1) / COL_B;
     const int groups = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(DIF_MAX_GROUPS, batches), DIF_GROUP_NODES / std::max<int64_t>(n, 1)));
-    const int64_t gstride = 5 * n * DIF_B, pstride = (int64_t)DIF_B * std::max(nb_mv, nb_el);
+    const int64_t gstride = 5 * n * COL_B, pstride = (int64_t)COL_B * std::max(nb_mv, nb_el);
 
     AnalysisState &A = analysis_of(g);
     DCR_TRY(dev_regrow(&A.dif_vec, &A.dif_vec_cap, n + groups * gstride));
     DCR_TRY(dev_regrow(&A.dif_part, &A.dif_part_cap, groups * pstride));
     DCR_TRY(dev_regrow(&A.dif_ctl, &A.dif_ctl_cap, (int64_t)sizeof(DifCtl) * groups));
     // per group z, p, r, x, q (16-byte aligned each), then the scale once; the heat kernel has z by turns in z and p, and x
-    double *z = A.dif_vec, *p = z + n * DIF_B, *r = p + n * DIF_B, *x = r + n * DIF_B, *q = x + n * DIF_B;
+    double *z = A.dif_vec, *p = z + n * COL_B, *r = p + n * COL_B, *x = r + n * COL_B, *q = x + n * COL_B;
     double *s = A.dif_vec + groups * gstride;
     DifCtl *ctl = reinterpret_cast<DifCtl *>(A.dif_ctl);
+    const ColLayout L = {z, p, r, x, q, s, A.dif_part, gstride, pstride, nb_mv, nb_el};
     hipLaunchKernelGGL(k_dif_scale, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, s, n);
     DCR_HIP(hipGetLastError());
 
     const int kk = sp ? (int)std::min<int64_t>(sp->k, n) : 0;
     std::vector<double> host_x;
-    if (dense) host_x.resize((size_t)(n * DIF_B));
+    if (dense) host_x.resize((size_t)(n * COL_B));
     if (sp) {
         sp->nnz = 0;
         sp->ptr[0] = 0;
     }
     bool fits = true;
     std::vector<DifCtl> h((size_t)groups);
-    for (int64_t first = 0; first < P; first += (int64_t)groups * DIF_B) {
-        const int ng = (int)std::min<int64_t>(groups, (P - first + DIF_B - 1) / DIF_B);  // groups of this launch
-        const dim3 grid_mv((unsigned)nb_mv, (unsigned)ng), grid_el((unsigned)nb_el, (unsigned)ng), grid_col(DIF_B, (unsigned)ng);
+    for (int64_t first = 0; first < P; first += (int64_t)groups * COL_B) {
+        const int ng = (int)std::min<int64_t>(groups, (P - first + COL_B - 1) / COL_B);  // groups of this launch
+        const dim3 grid_mv((unsigned)nb_mv, (unsigned)ng), grid_el((unsigned)nb_el, (unsigned)ng), grid_col(COL_B, (unsigned)ng);
         std::memset(h.data(), 0, sizeof(DifCtl) * (size_t)ng);
-        for (int64_t c = 0; c < (int64_t)ng * DIF_B; ++c) {
-            DifCtl &hc = h[(size_t)(c / DIF_B)];
-            const int k = (int)(c % DIF_B);
+        for (int64_t c = 0; c < (int64_t)ng * COL_B; ++c) {
+            DifCtl &hc = h[(size_t)(c / COL_B)];
+            const int k = (int)(c % COL_B);
             const bool pad = first + c >= P;
             hc.teleport = o.alpha;
             hc.damp = 1.0 - o.alpha;
-            hc.stop = o.tol * o.alpha;
+            hc.cg.stop[k] = o.tol * o.alpha;
             hc.src[k] = pad ? -1 : sources ? sources[first + c] : (int32_t)(first + c);
-            hc.frozen[k] = pad ? 1 : 0;  // padding columns start frozen
-            hc.active += pad ? 0 : 1;
+            hc.cg.frozen[k] = pad ? 1 : 0;  // padding columns start frozen
+            hc.cg.active += pad ? 0 : 1;
             if (sp && sp->mode == 1) hc.thr[k] = dif_key(sp->eps + 0.0);
         }
         DCR_HIP(hipMemcpyAsync(ctl, h.data(), sizeof(DifCtl) * (size_t)ng, hipMemcpyHostToDevice, g->stream));
@@ -591,45 +381,29 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
                                    z_out, x, gstride);
             hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo, n, ctl, x, A.dif_part, gstride, pstride);
         } else {
-            hipLaunchKernelGGL(k_dif_start, grid_el, dim3(256), 0, g->stream, s, n, ctl, z, p, r, x, gstride);
-            for (int64_t step = 0; step < o.max_steps; ++step) {
-                hipLaunchKernelGGL(k_dif_matvec<0>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, p, z, s, q, ctl, A.dif_part, gstride,
-                                   pstride);
-                hipLaunchKernelGGL(k_dif_update, grid_el, dim3(256), 0, g->stream, n, ctl, p, q, x, r, A.dif_part, gstride, pstride);
-                hipLaunchKernelGGL(k_dif_direction, grid_el, dim3(256), 0, g->stream, n, ctl, s, r, p, z, gstride);
-                if ((step + 1) % SP_CHECK_EVERY != 0 && step + 1 != o.max_steps) continue;
-                DCR_HIP(hipGetLastError());
-                DCR_HIP(hipMemcpyAsync(h.data(), ctl, sizeof(DifCtl) * (size_t)ng, hipMemcpyDeviceToHost, g->stream));
-                DCR_HIP(hipStreamSynchronize(g->stream));
-                int active = 0;
-                for (int i = 0; i < ng; ++i) active += h[(size_t)i].active;
-                if (active == 0) break;
-            }
-            hipLaunchKernelGGL(k_dif_scale_x, grid_el, dim3(256), 0, g->stream, n, s, x, z, gstride);
-            hipLaunchKernelGGL(k_dif_matvec<1>, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, x, z, s, q, ctl, A.dif_part, gstride,
-                               pstride);
+            DCR_TRY(col_cg_solve(g, plan, L, ng, DifProblem{ctl}, h.data(), o.max_steps));
         }
         if (sp) hipLaunchKernelGGL(k_dif_select, grid_col, dim3(256), 0, g->stream, x, n, ctl, sp->mode, kk, gstride);
         DCR_HIP(hipGetLastError());
         DCR_HIP(hipMemcpyAsync(h.data(), ctl, sizeof(DifCtl) * (size_t)ng, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
         int64_t batch = 0;  // entries the columns of this launch keep
-        for (int64_t c = 0; c < (int64_t)ng * DIF_B; ++c) {
-            DifCtl &hc = h[(size_t)(c / DIF_B)];
-            const int k = (int)(c % DIF_B);
+        for (int64_t c = 0; c < (int64_t)ng * COL_B; ++c) {
+            DifCtl &hc = h[(size_t)(c / COL_B)];
+            const int k = (int)(c % COL_B);
             hc.base[k] = batch;
             batch += hc.count[k];
             if (first + c >= P) continue;
             out_residual[first + c] = hc.resid[k];
-            if (out_steps) out_steps[first + c] = hc.steps[k];
+            if (out_steps) out_steps[first + c] = hc.cg.steps[k];
             if (sp) sp->ptr[first + c + 1] = sp->ptr[first + c] + hc.count[k];
         }
         if (dense) {
             for (int i = 0; i < ng; ++i) {
-                DCR_HIP(hipMemcpyAsync(host_x.data(), x + i * gstride, sizeof(double) * (size_t)(n * DIF_B), hipMemcpyDeviceToHost, g->stream));
+                DCR_HIP(hipMemcpyAsync(host_x.data(), x + i * gstride, sizeof(double) * (size_t)(n * COL_B), hipMemcpyDeviceToHost, g->stream));
                 DCR_HIP(hipStreamSynchronize(g->stream));
-                for (int k = 0; k < DIF_B && first + (int64_t)i * DIF_B + k < P; ++k)
-                    for (int64_t v = 0; v < n; ++v) dense[(first + (int64_t)i * DIF_B + k) * n + v] = host_x[(size_t)(v * DIF_B + k)];
+                for (int k = 0; k < COL_B && first + (int64_t)i * COL_B + k < P; ++k)
+                    for (int64_t v = 0; v < n; ++v) dense[(first + (int64_t)i * COL_B + k) * n + v] = host_x[(size_t)(v * COL_B + k)];
             }
             continue;
         }

@@ -41,9 +41,9 @@ SpectralGap = namedtuple('SpectralGap', ['lambda1', 'residual', 'steps', 'restar
 SweepCut = namedtuple('SweepCut', ['value', 'size', 'counts', 'order', 'profile'])
 
 
-# pairs of one batch of DcrGraph.effective_resistance: DCR_RES_B of csrc/dcr_resistance.hip
+# pairs of one batch of DcrGraph.effective_resistance: COL_B (DCR_COL_B) of the column CG in csrc/dcr_analysis.h
 RESISTANCE_BATCH = 16
-# columns of one batch of DcrGraph.ppr and DcrGraph.diffusion: DIF_B of csrc/dcr_diffusion.hip
+# columns of one batch of DcrGraph.ppr, DcrGraph.heat and DcrGraph.diffusion: the same COL_B
 DIFFUSION_BATCH = 16
 # ranks one LDS window of the FoSR pick covers on a row above 2,048 neighbours: FSR_WINDOW of csrc/dcr_fosr.hip
 FOSR_WINDOW = 4096

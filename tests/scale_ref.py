@@ -40,10 +40,10 @@ def constants():
     assert re.search(r'k_sweep_value,\s*dim3\(std::min\(blocks_of\(n - 1\),\s*\(unsigned\)SW_VALUE_BLOCKS\)\)', sweep), 'the grid of k_sweep_value'
     assert re.search(r'nb_table\s*=\s*\(int\)blocks_of\(table_len,\s*SW_SCAN_BLOCK\)', sweep) and re.search(r'table_len\s*=\s*\(int64_t\)256\s*\*\s*P->tiles', sweep)
     assert re.search(r'nb_diff\s*=\s*\(int\)blocks_of\(n,\s*SW_SCAN_BLOCK\)', sweep)
-    for name in ('DIF_B', 'DIF_UPDATE_BLOCKS', 'DIF_MAX_GROUPS', 'DIF_GROUP_NODES', 'DIF_SHORT_LANES', 'DIF_SHORT_ROWS'):
+    for name in ('DIF_MAX_GROUPS', 'DIF_GROUP_NODES'):
         c[name] = constant(dif, name)
-    assert re.search(r'DIF_CP\s*=\s*DIF_B\s*/\s*2\s*;', dif)
-    assert re.search(r'nb_el\s*=\s*\(int\)std::min<int64_t>\(DIF_UPDATE_BLOCKS,\s*blocks_of\(n\s*\*\s*DIF_CP\)\)', dif)
+    assert re.search(r'nb_el\s*=\s*\(int\)std::min<int64_t>\(COL_UPDATE_BLOCKS,\s*blocks_of\(n\s*\*\s*COL_CP\)\)', dif), 'nb_el of diffusion_batches'
+    assert re.search(r'nb_mv\s*=\s*\(int\)row_grid<ColRows>\(plan\)', dif)
     assert re.search(r'std::min<int64_t>\(std::min<int64_t>\(DIF_MAX_GROUPS,\s*batches\),\s*DIF_GROUP_NODES\s*/\s*std::max<int64_t>\(n,\s*1\)\)', dif)
     c['FSR_DOT_BLOCKS'] = constant(fosr, 'FSR_DOT_BLOCKS')
     assert re.search(r'k_fosr_dot,\s*dim3\(std::min\(blocks_of\(n\),\s*\(unsigned\)FSR_DOT_BLOCKS\)\)', fosr)
@@ -56,26 +56,26 @@ def constants():
     m = re.search(r'blocks_of\(\s*p\.n_mid\s*,\s*(\d+)\s*\)', header)
     assert m, 'the medium rows of a workgroup in row_grid'
     c['MID_ROWS'] = int(m.group(1))
-    assert re.search(r'using\s+DifRows\s*=\s*RowGeom<DIF_SHORT_LANES,\s*DIF_SHORT_ROWS\s*/\s*8,\s*DIF_CP>\s*;', dif)
-    c.update(resistance_and_hops_constants())
+    c.update(column_and_hops_constants())
     return c
 
 
-def resistance_and_hops_constants():
-    """The constants of csrc/dcr_resistance.hip and csrc/dcr_hops.hip that RESISTANCE_SIZE, HOPS_SMALL and HOPS_LARGE depend on
-    ('DCR_RES_B' is the default of the #define, which is what the library is built with)."""
-    res, hops = source('dcr_resistance.hip'), source('dcr_hops.hip')
-    c = {name: constant(res, name) for name in ('RES_UPDATE_BLOCKS', 'RES_SHORT_LANES', 'RES_SHORT_ROWS')}
-    m = re.search(r'#ifndef\s+DCR_RES_B\s*\n\s*#define\s+DCR_RES_B\s+(\d+)', res)
-    assert m, 'the default of DCR_RES_B not found'
-    c['DCR_RES_B'] = int(m.group(1))
-    assert re.search(r'constexpr\s+int\s+RES_B\s*=\s*DCR_RES_B\s*;', res) and re.search(r'constexpr\s+int\s+RES_CP\s*=\s*RES_B\s*/\s*2\s*;', res)
-    c['RES_CP'] = c['DCR_RES_B'] // 2
-    assert re.search(r'nb_el\s*=\s*\(int\)std::min<int64_t>\(RES_UPDATE_BLOCKS,\s*blocks_of\(n\s*\*\s*RES_CP\)\)', res), 'nb_el of resistance_batches'
-    assert re.search(r'nb_mv\s*=\s*\(int\)row_grid<ResRows>\(plan\)', res)
-    assert re.search(r'using\s+ResRows\s*=\s*RowGeom<RES_SHORT_LANES,\s*RES_SHORT_ROWS\s*/\s*8,\s*RES_CP>\s*;', res)
-    assert len(re.findall(r'e\s*<\s*total;\s*e\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*256\)', res)) == 4, 'the four grid-stride loops over n * RES_CP'
-    assert re.search(r'i\s*<\s*count;\s*i\s*\+=\s*256\s*/\s*RES_CP\)', res), 'the stride of cols_close_partials'
+def column_and_hops_constants():
+    """The constants of the column CG in csrc/dcr_analysis.h, which the resistance and diffusion solves share, and of
+    csrc/dcr_hops.hip, that DIFFUSION_SIDE, RESISTANCE_SIZE, HOPS_SMALL and HOPS_LARGE depend on ('COL_B' is the default of
+    '#define DCR_COL_B', which is what the library is built with)."""
+    header, res, hops = source('dcr_analysis.h'), source('dcr_resistance.hip'), source('dcr_hops.hip')
+    c = {name: constant(header, name) for name in ('COL_UPDATE_BLOCKS', 'COL_SHORT_LANES', 'COL_SHORT_ROWS')}
+    m = re.search(r'#ifndef\s+DCR_COL_B\s*\n\s*#define\s+DCR_COL_B\s+(\d+)', header)
+    assert m, 'the default of DCR_COL_B not found'
+    c['COL_B'] = int(m.group(1))
+    assert re.search(r'constexpr\s+int\s+COL_B\s*=\s*DCR_COL_B\s*;', header) and re.search(r'constexpr\s+int\s+COL_CP\s*=\s*COL_B\s*/\s*2\s*;', header)
+    c['COL_CP'] = c['COL_B'] // 2
+    assert re.search(r'nb_el\s*=\s*\(int\)std::min<int64_t>\(COL_UPDATE_BLOCKS,\s*blocks_of\(n\s*\*\s*COL_CP\)\)', res), 'nb_el of resistance_batches'
+    assert re.search(r'nb_mv\s*=\s*\(int\)row_grid<ColRows>\(plan\)', res)
+    assert re.search(r'using\s+ColRows\s*=\s*RowGeom<COL_SHORT_LANES,\s*COL_SHORT_ROWS\s*/\s*8,\s*COL_CP>\s*;', header)
+    assert len(re.findall(r'e\s*<\s*total;\s*e\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*256\)', header)) == 4, 'the four grid-stride loops over n * COL_CP'
+    assert re.search(r'i\s*<\s*count;\s*i\s*\+=\s*256\s*/\s*COL_CP\)', header), 'the stride of the column close_partials'
     c['HOP_COUNT_BLOCKS'] = constant(hops, 'HOP_COUNT_BLOCKS')
     assert re.search(r'k_hop_count<W>,\s*dim3\(std::min\(blocks_of\(\(n\s*\+\s*63\)\s*/\s*64,\s*4\),\s*\(unsigned\)HOP_COUNT_BLOCKS\)\)', hops), 'the grid of k_hop_count'
     assert re.search(r'c\s*=\s*\(int64_t\)blockIdx\.x\s*\*\s*4\s*\+\s*wave;\s*c\s*<\s*chunks;\s*c\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*4\)', hops), 'the chunk loop of k_hop_count'
@@ -111,11 +111,10 @@ def keys_trips(n, c):
 
 def diffusion_batches(n, P, c):
     """(groups, nb_el, grid-stride trips of the element-wise kernels) of csrc/dcr_diffusion.hip::diffusion_batches."""
-    cp = c['DIF_B'] // 2
-    nb_el = min(c['DIF_UPDATE_BLOCKS'], blocks_of(n * cp))
-    batches = blocks_of(P, c['DIF_B'])
+    nb_el = min(c['COL_UPDATE_BLOCKS'], blocks_of(n * c['COL_CP']))
+    batches = blocks_of(P, c['COL_B'])
     groups = max(1, min(c['DIF_MAX_GROUPS'], batches, c['DIF_GROUP_NODES'] // max(n, 1)))
-    return groups, nb_el, blocks_of(n * cp, nb_el * 256)
+    return groups, nb_el, blocks_of(n * c['COL_CP'], nb_el * 256)
 
 
 def row_grid(counts, c, short_rows=None):
@@ -125,9 +124,9 @@ def row_grid(counts, c, short_rows=None):
 
 
 def resistance_elementwise(n, c):
-    """(nb_el, grid-stride trips, elements of the last trip) of k_res_start / update / direction / scale_y over n * RES_CP elements."""
-    total = n * c['RES_CP']
-    nb_el = min(c['RES_UPDATE_BLOCKS'], blocks_of(total))
+    """(nb_el, grid-stride trips, elements of the last trip) of k_col_start / update / direction / scale over n * COL_CP elements."""
+    total = n * c['COL_CP']
+    nb_el = min(c['COL_UPDATE_BLOCKS'], blocks_of(total))
     trips = blocks_of(total, nb_el * 256)
     return nb_el, trips, total - (trips - 1) * nb_el * 256
 

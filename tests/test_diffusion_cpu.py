@@ -1,6 +1,6 @@
 """The dense restatement tests/diffusion_ref.py, pinned on the CPU: against the reference's two sparsifiers as recorded in
 tests/golden/diffusion_reference.json (tools/make_golden_diffusion.py ran them), against closed forms of the personalised-PageRank
-matrix, and the constants of csrc/dcr_diffusion.hip against those the row-plan family was built for."""
+matrix, and the constants of the column CG in csrc/dcr_analysis.h against those the row-plan family was built for."""
 import os
 import re
 
@@ -105,17 +105,19 @@ def test_geometry_is_that_of_the_resistance_mat_vec():
     dif = open(os.path.join(CSRC, 'dcr_diffusion.hip')).read()
     res = open(os.path.join(CSRC, 'dcr_resistance.hip')).read()
     header = open(os.path.join(CSRC, 'dcr_analysis.h')).read()
-    assert constant(dif, 'DIF_SHORT_LANES') == constant(res, 'RES_SHORT_LANES') == 32
-    assert constant(dif, 'DIF_SHORT_ROWS') == constant(res, 'RES_SHORT_ROWS') == 64
-    m = re.search(r'#\s*define\s+DCR_RES_B\s+(\d+)', res)
-    assert m and constant(dif, 'DIF_B') == int(m.group(1)) == 16
-    assert re.search(r'constexpr\s+int\s+DIF_CP\s*=\s*DIF_B\s*/\s*2\s*;', dif)
-    assert re.search(r'using\s+DifRows\s*=\s*RowGeom<\s*DIF_SHORT_LANES\s*,\s*DIF_SHORT_ROWS\s*/\s*8\s*,\s*DIF_CP\s*>', dif)
-    assert re.search(r'using\s+ResRows\s*=\s*RowGeom<\s*RES_SHORT_LANES\s*,\s*RES_SHORT_ROWS\s*/\s*8\s*,\s*RES_CP\s*>', res)
-    assert 'walk_rows<DifRows>' in dif and 'row_grid<DifRows>' in dif
-    assert constant(header, 'SP_CHECK_EVERY') >= 1 and 'SP_CHECK_EVERY' in dif
+    # one geometry and one batch width, in the header; neither file keeps a copy of its own
+    assert constant(header, 'COL_SHORT_LANES') == 32 and constant(header, 'COL_SHORT_ROWS') == 64
+    m = re.search(r'#\s*define\s+DCR_COL_B\s+(\d+)', header)
+    assert m and int(m.group(1)) == 16 and re.search(r'constexpr\s+int\s+COL_B\s*=\s*DCR_COL_B\s*;', header)
+    assert re.search(r'constexpr\s+int\s+COL_CP\s*=\s*COL_B\s*/\s*2\s*;', header)
+    assert re.search(r'using\s+ColRows\s*=\s*RowGeom<\s*COL_SHORT_LANES\s*,\s*COL_SHORT_ROWS\s*/\s*8\s*,\s*COL_CP\s*>', header)
+    for text in (dif, res):
+        assert not re.search(r'RowGeom\s*<|_SHORT_LANES\s*=|_SHORT_ROWS\s*=|#\s*define\s+DCR_\w*_B\b', text)
+        assert 'row_grid<ColRows>' in text and 'col_cg_solve' in text
+    assert 'walk_rows<ColRows>' in header and 'walk_rows<ColRows>' in dif   # the CG mat-vec; k_heat_term
+    assert constant(header, 'SP_CHECK_EVERY') >= 1 and len(re.findall(r'% SP_CHECK_EVERY', header)) == 1
     from dcr import graph
-    assert graph.DIFFUSION_BATCH == constant(dif, 'DIF_B')
+    assert graph.DIFFUSION_BATCH == graph.RESISTANCE_BATCH == int(m.group(1))
 
 
 def test_entry_points_are_declared_and_bound():

@@ -167,7 +167,7 @@ def large_solve(dcr):
 
 
 def test_ppr_past_one_trip_against_the_host_certificate(dcr):
-    """n = 33,133: k_dif_start / update / direction / scale_x take a second grid-stride trip, two launches run at one group.  No
+    """n = 33,133: k_col_start / update / direction / scale take a second grid-stride trip, two launches run at one group.  No
     dense matrix exists here, so the reference is a certificate, derived and not measured.  With rho the residual of the device's
     column computed on the host in np.longdouble:
       |rho - reported residual| <= (d_max + 4) 2^-52 | |M| |x| |_2     the forward error of the float64 mat-vec the device performs

@@ -312,9 +312,9 @@ def test_scale_s100k_one_batch(dcr):
 # ---- 10. past the cap of the element-wise kernels --------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def past_cap(dcr):
-    """scale_ref.diffusion_large(), 33,133 nodes: n RES_CP elements are more than 256 RES_UPDATE_BLOCKS, so k_res_start, update,
-    direction and scale_y take a second, ragged grid-stride trip (the lattice's last 356 nodes, every hub, the isolated nodes)
-    and k_res_update closes a full 1,024 partials, 32 a thread group (tests/test_scale_thresholds_cpu.py).  The reference is
+    """scale_ref.diffusion_large(), 33,133 nodes: n COL_CP elements are more than 256 COL_UPDATE_BLOCKS, so k_col_start, update,
+    direction and scale take a second, ragged grid-stride trip (the lattice's last 356 nodes, every hub, the isolated nodes)
+    and k_col_update closes a full 1,024 partials, 32 a thread group (tests/test_scale_thresholds_cpu.py).  The reference is
     resistance_ref.sparse_resistance, measured against itself by a second grounding (e_ref), and lam_lo is a certified lower
     bound of lambda_1 (tests/test_resistance_cpu.py pins both on the CPU); neither comes from the device.  One 19-pair call,
     shared by the tests below: 17 pairs take a column (the second batch has 15 padding columns), two are decided on the host."""

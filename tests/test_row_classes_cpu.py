@@ -13,7 +13,8 @@ from conftest import PKG
 
 CSRC = os.path.join(PKG, 'csrc')
 
-# (short_lanes, turns, NODE): RowGeom<> of the spectral mat-vec and the sweep, ResRows of the resistance mat-vec
+# (short_lanes, turns, NODE): RowGeom<> of the spectral mat-vec and the sweep; ColRows of the column CG, which the resistance and
+# diffusion mat-vecs share (under the key 'ResRows', which the ids of the parametrised tests carry)
 GEOMETRIES = {'RowGeom<>': (8, 1, 1), 'ResRows': (32, 8, 8)}
 MID_ROWS = 4   # medium rows a workgroup takes: a wave each
 
@@ -83,7 +84,6 @@ def constant(text, name):
 
 def test_limits_and_geometries_are_those_of_the_sources():
     header = open(os.path.join(CSRC, 'dcr_analysis.h')).read()
-    res = open(os.path.join(CSRC, 'dcr_resistance.hip')).read()
     assert constant(header, 'SP_SHORT_DEG') == spectral_ref.SHORT_DEG
     assert constant(header, 'SP_LONG_DEG') == spectral_ref.LONG_DEG
     m = re.search(r'int\s+SHORT_LANES\s*=\s*(\d+)\s*,\s*int\s+TURNS\s*=\s*(\d+)\s*,\s*int\s+NODE\s*=\s*(\d+)', header)
@@ -92,10 +92,11 @@ def test_limits_and_geometries_are_those_of_the_sources():
     m = re.search(r'blocks_of\(\s*p\.n_mid\s*,\s*(\d+)\s*\)', header)
     assert m and int(m.group(1)) == MID_ROWS, 'the medium rows of a workgroup in row_grid'
     lanes, turns, node = GEOMETRIES['ResRows']
-    assert constant(res, 'RES_SHORT_LANES') == lanes and constant(res, 'RES_SHORT_ROWS') == short_rows('ResRows')
-    m = re.search(r'#\s*define\s+DCR_RES_B\s+(\d+)', res)
-    assert m, 'DCR_RES_B not found'
-    assert int(m.group(1)) == 2 * node   # a lane takes two columns: RES_B / 2 lanes across a node
+    assert constant(header, 'COL_SHORT_LANES') == lanes and constant(header, 'COL_SHORT_ROWS') == short_rows('ResRows')
+    assert re.search(r'using\s+ColRows\s*=\s*RowGeom<\s*COL_SHORT_LANES\s*,\s*COL_SHORT_ROWS\s*/\s*8\s*,\s*COL_CP\s*>', header) and turns == 8
+    m = re.search(r'#\s*define\s+DCR_COL_B\s+(\d+)', header)
+    assert m, 'DCR_COL_B not found'
+    assert int(m.group(1)) == 2 * node   # a lane takes two columns: COL_B / 2 lanes across a node
 
 
 # ---- 3. the walker's formula against the grid ------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ def test_constants_are_those_the_sizes_were_chosen_for(c):
     print('  ' + ', '.join(f'{k} = {v}' for k, v in c.items()))
     assert sc.CLOSING_STRIDE == 256
     assert c['SP_SHORT_DEG'] == spectral_ref.SHORT_DEG and c['SP_LONG_DEG'] == spectral_ref.LONG_DEG
-    assert c['DIF_B'] % 2 == 0 and c['SW_SCAN_BLOCK'] == 8 * 256   # eight elements a thread
+    assert c['COL_B'] % 2 == 0 and c['SW_SCAN_BLOCK'] == 8 * 256   # eight elements a thread
 
 
 # ---- the sweep -----------------------------------------------------------------------------------------------------------------------
@@ -99,29 +99,29 @@ def test_sort_tiles_beyond_the_tile_limit(c):
 
 # ---- diffusion -----------------------------------------------------------------------------------------------------------------------
 def test_diffusion_elementwise_second_trip(c):
-    stale = 'stale GPU size: scale_ref.DIFFUSION_SIDE (second grid-stride trip of k_dif_start / update / direction / scale_x)'
+    stale = 'stale GPU size: scale_ref.DIFFUSION_SIDE (second grid-stride trip of k_col_start / update / direction / scale in diffusion_batches)'
     ei, n, names = sc.diffusion_large()
-    at = c['DIF_UPDATE_BLOCKS'] * 256 // (c['DIF_B'] // 2)   # 32,768: the largest n of one trip
-    assert sc.diffusion_batches(at, sc.DIFFUSION_P, c)[1:] == (c['DIF_UPDATE_BLOCKS'], 1), stale
-    assert sc.diffusion_batches(at + 1, sc.DIFFUSION_P, c)[1:] == (c['DIF_UPDATE_BLOCKS'], 2), stale
+    at = c['COL_UPDATE_BLOCKS'] * 256 // c['COL_CP']   # 32,768: the largest n of one trip
+    assert sc.diffusion_batches(at, sc.DIFFUSION_P, c)[1:] == (c['COL_UPDATE_BLOCKS'], 1), stale
+    assert sc.diffusion_batches(at + 1, sc.DIFFUSION_P, c)[1:] == (c['COL_UPDATE_BLOCKS'], 2), stale
     groups, nb_el, trips = sc.diffusion_batches(n, sc.DIFFUSION_P, c)
-    assert at < n < at + at // 16 and (groups, nb_el, trips) == (1, c['DIF_UPDATE_BLOCKS'], 2), stale
-    assert -(-sc.DIFFUSION_P // (groups * c['DIF_B'])) == 2, stale              # two launches
+    assert at < n < at + at // 16 and (groups, nb_el, trips) == (1, c['COL_UPDATE_BLOCKS'], 2), stale
+    assert -(-sc.DIFFUSION_P // (groups * c['COL_B'])) == 2, stale              # two launches
     # every class of the mat-vec, and the sources the test names
     deg = sc.degrees(ei, n)
     nl, nm, ns = sc.class_counts(deg, c)
     assert nl == 1 and nm == 4 and deg[names['hub0']] == 2100 > c['SP_LONG_DEG'] and deg[names['hub1']] == c['SP_SHORT_DEG'] + 1, stale
     assert deg[names['isolated']] == 0 and deg[names['last']] == 0 and 2 <= deg[names['corner']] <= c['SP_SHORT_DEG'] and (deg == 0).sum() == 4
-    mv_grid = nl + sc.blocks_of(nm, c['MID_ROWS']) + sc.blocks_of(ns, c['DIF_SHORT_ROWS'])
-    assert mv_grid > 2 * (256 // (c['DIF_B'] // 2)), stale                      # dif_close_partials: more than one trip of 32 partials
+    mv_grid = nl + sc.blocks_of(nm, c['MID_ROWS']) + sc.blocks_of(ns, c['COL_SHORT_ROWS'])
+    assert mv_grid > 2 * (256 // c['COL_CP']), stale                      # the column close_partials: more than one trip of 32 partials
 
 
 def test_diffusion_groups_limited_by_n(c):
     stale = 'stale GPU size: scale_ref.GROUPS_SIDE / GROUPS_P (group count limited by n)'
     ei, n, names = sc.diffusion_groups()
     groups = sc.diffusion_batches(n, sc.GROUPS_P, c)[0]
-    assert groups == c['DIF_GROUP_NODES'] // n == 6 < min(c['DIF_MAX_GROUPS'], sc.blocks_of(sc.GROUPS_P, c['DIF_B'])), stale
-    assert sc.GROUPS_P == groups * c['DIF_B'] + 5, stale                         # a full launch of six groups, then five columns
+    assert groups == c['DIF_GROUP_NODES'] // n == 6 < min(c['DIF_MAX_GROUPS'], sc.blocks_of(sc.GROUPS_P, c['COL_B'])), stale
+    assert sc.GROUPS_P == groups * c['COL_B'] + 5, stale                         # a full launch of six groups, then five columns
     assert c['DIF_GROUP_NODES'] // c['DIF_MAX_GROUPS'] < n, stale
     deg = sc.degrees(ei, n)
     assert sc.class_counts(deg, c)[:2] == (1, 2) and deg[names['last']] == 0
@@ -131,7 +131,7 @@ def test_diffusion_all_eight_groups_at_small_n(c):
     stale = 'stale GPU size: scale_ref.SMALL_GROUPS_P (groups 2 .. 7 of one launch)'
     n = next(m for name, e, m in spectral_ref.plan_family() if name == 'long3_mid9_short63')
     assert sc.diffusion_batches(n, sc.SMALL_GROUPS_P, c)[0] == c['DIF_MAX_GROUPS'] == 8, stale
-    assert sc.SMALL_GROUPS_P == c['DIF_MAX_GROUPS'] * c['DIF_B'] and n <= c['DIF_GROUP_NODES'] // c['DIF_MAX_GROUPS'], stale
+    assert sc.SMALL_GROUPS_P == c['DIF_MAX_GROUPS'] * c['COL_B'] and n <= c['DIF_GROUP_NODES'] // c['DIF_MAX_GROUPS'], stale
     assert sc.diffusion_batches(n, 17, c)[0] == 2      # what the batch-independence test of the plan family reaches
 
 
@@ -173,19 +173,19 @@ def test_whole_call_graphs_are_what_the_gpu_tests_rely_on(c):
 
 # ---- effective resistance ------------------------------------------------------------------------------------------------------------
 def test_resistance_elementwise_second_trip(c):
-    stale = ('stale GPU size: scale_ref.RESISTANCE_SIZE (RES_UPDATE_BLOCKS / DCR_RES_B: second grid-stride trip of k_res_start / update / '
-             'direction / scale_y, tests/test_resistance_gpu.py::test_past_the_cap_*)')
+    stale = ('stale GPU size: scale_ref.RESISTANCE_SIZE (COL_UPDATE_BLOCKS / DCR_COL_B: second grid-stride trip of k_col_start / update / '
+             'direction / scale in resistance_batches, tests/test_resistance_gpu.py::test_past_the_cap_*)')
     ei, n, names = sc.diffusion_large()
     assert n == sc.RESISTANCE_SIZE
-    at = 256 * c['RES_UPDATE_BLOCKS'] // c['RES_CP']                              # 32,768: the largest n of one trip
+    at = 256 * c['COL_UPDATE_BLOCKS'] // c['COL_CP']                              # 32,768: the largest n of one trip
     assert at == sc.SECOND_TRIP, stale
-    assert sc.resistance_elementwise(at, c)[:2] == (c['RES_UPDATE_BLOCKS'], 1), stale
-    assert sc.resistance_elementwise(at + 1, c)[:2] == (c['RES_UPDATE_BLOCKS'], 2), stale
+    assert sc.resistance_elementwise(at, c)[:2] == (c['COL_UPDATE_BLOCKS'], 1), stale
+    assert sc.resistance_elementwise(at + 1, c)[:2] == (c['COL_UPDATE_BLOCKS'], 2), stale
     nb_el, trips, last = sc.resistance_elementwise(n, c)
-    assert n * c['RES_CP'] > 256 * c['RES_UPDATE_BLOCKS'] and (nb_el, trips) == (c['RES_UPDATE_BLOCKS'], 2), stale
-    assert 0 < last < nb_el * 256 and last == (n - at) * c['RES_CP'], stale       # ragged: fewer elements than one full grid
+    assert n * c['COL_CP'] > 256 * c['COL_UPDATE_BLOCKS'] and (nb_el, trips) == (c['COL_UPDATE_BLOCKS'], 2), stale
+    assert 0 < last < nb_el * 256 and last == (n - at) * c['COL_CP'], stale       # ragged: fewer elements than one full grid
     assert last % 256 != 0, stale                                                 # and its last workgroup is partly filled
-    assert nb_el == 32 * (256 // c['RES_CP']), stale                              # cols_close_partials: 32 partials a thread group
+    assert nb_el == 32 * (256 // c['COL_CP']), stale                              # the column close_partials: 32 partials a thread group
     # what lies in the second trip: the lattice's tail, every hub and every isolated node; every pair the GPU test names
     deg = sc.degrees(ei, n)
     assert names['hub0'] >= at and deg[names['hub0']] > c['SP_LONG_DEG'], stale
@@ -193,25 +193,25 @@ def test_resistance_elementwise_second_trip(c):
     assert (deg[-4:] == 0).all() and (deg[:-4] > 0).all() and names['isolated'] == n - 4 >= at, stale
     assert sc.DIFFUSION_SIDE ** 2 - at >= 256, stale                               # a few hundred lattice nodes past the boundary
     pairs, solved, _ = sc.resistance_pairs()
-    assert len(solved) == c['DCR_RES_B'] + 1 and len(pairs) == len(solved) + 2, stale   # the second batch: one column, 15 padded
+    assert len(solved) == c['COL_B'] + 1 and len(pairs) == len(solved) + 2, stale   # the second batch: one column, 15 padded
     assert (pairs[solved][:, 0] != pairs[solved][:, 1]).all() and (deg[pairs[solved]] > 0).all()
     assert (pairs[2] >= at).all() and (pairs[7] >= at).all() and pairs[1, 0] >= at > pairs[1, 1] and (pairs[18] >= at).all(), stale
     assert pairs[8, 0] == at - 1 and pairs[8, 1] == at, stale
     edge = set(map(tuple, ei.T.tolist()))
     assert all(tuple(pairs[i]) in edge for i in (3, 7, 8))                          # lattice edges
     assert deg[pairs[5, 0]] == 0 and pairs[6, 0] == pairs[6, 1]
-    # the mat-vec's grid: more than one step a thread group of cols_close_partials, here and on the 70,001-node graph
-    grid = sc.row_grid(sc.class_counts(deg, c), c, c['RES_SHORT_ROWS'])
-    assert grid > 2 * (256 // c['RES_CP']), stale
+    # the mat-vec's grid: more than one step a thread group of the column close_partials, here and on the 70,001-node graph
+    grid = sc.row_grid(sc.class_counts(deg, c), c, c['COL_SHORT_ROWS'])
+    assert grid > 2 * (256 // c['COL_CP']), stale
 
 
 def test_resistance_and_hop_matvec_grids_past_256_workgroups(c):
     ei, n = sc.whole_small()
     counts = sc.class_counts(sc.degrees(ei, n), c)
-    assert c['RES_SHORT_ROWS'] == 256 // c['RES_SHORT_LANES'] * 8                   # RowGeom<RES_SHORT_LANES, RES_SHORT_ROWS / 8, ..>
-    res_grid, hop_grid = sc.row_grid(counts, c, c['RES_SHORT_ROWS']), sc.row_grid(counts, c)
-    print(f'  n = {n}: row_grid<ResRows> {res_grid}, row_grid<HopRows> {hop_grid}')
-    assert res_grid > sc.CLOSING_STRIDE, 'stale GPU size: scale_ref.WHOLE_SMALL (RES_SHORT_ROWS: row_grid<ResRows> past 256 workgroups)'
+    assert c['COL_SHORT_ROWS'] == 256 // c['COL_SHORT_LANES'] * 8                   # RowGeom<COL_SHORT_LANES, COL_SHORT_ROWS / 8, ..>
+    res_grid, hop_grid = sc.row_grid(counts, c, c['COL_SHORT_ROWS']), sc.row_grid(counts, c)
+    print(f'  n = {n}: row_grid<ColRows> {res_grid}, row_grid<HopRows> {hop_grid}')
+    assert res_grid > sc.CLOSING_STRIDE, 'stale GPU size: scale_ref.WHOLE_SMALL (COL_SHORT_ROWS: row_grid<ColRows> past 256 workgroups)'
     assert hop_grid > sc.CLOSING_STRIDE, ('stale GPU size: scale_ref.HOPS_SMALL (RowGeom<>: row_grid<HopRows> past 256 workgroups, '
                                           'tests/test_hops_gpu.py::test_rows_and_summary_at_70001_nodes)')
 
