@@ -96,13 +96,22 @@ def allow(K, d_max):
     in exact arithmetic, entry by entry.
 
     Every quantity of the recurrence is non-negative, so nothing cancels and each rounding is a relative error of at most
-    u = 2^-53 of a quantity that only grows into the result: the errors add, componentwise and relative.  One term, at a row of
-    degree deg: deg + 1 additions form (A + I) z (in any order: each entry passes through at most deg + 1 of them); s~ carries two
-    roundings of its own (the square root and the division) and is used twice, in v and in the z handed on, four in all; c = t /
-    (k + 1) is one rounding and each of the two scalings by c and s~ one more; the addition into x is one.  That is
-    deg + 1 + 4 + 3 + 1 = deg + 9 <= d_max + 9 roundings for the new term on top of those of the term it came from, and the start
-    e^-t is one.  Term k therefore carries at most k (d_max + 9) + 1 relative roundings, x after K terms at most
-    K (d_max + 9) + 1 + K <= (K + 1)(d_max + 10) of them, times u (1 + O(K d_max u)); and the entries of x are at most those of S,
-    which are at most 1 because |S|_2 <= 1.  Stated with 2^-52 and d_max + 12 it has more than a factor of two in hand, which
-    covers the second-order terms and a libm whose exp is a little more than half an ulp off."""
+    u = 2^-53 of a quantity that only grows into the result: the errors add, componentwise and relative, so the bound is
+    |x_i - X_i| <= allow X_i entry by entry (tests/heat_steps_ref.py::compare applies it so; as an absolute number it is only the
+    weaker statement that follows from X_i <= 1).  It assumes that nothing underflows.
+
+    One term, at a row of degree deg, counted from the z it reads to the z it writes.  The row's sum (A + I) z is a tree of
+    additions over deg + 1 leaves, whatever its shape: the lanes of the row's scope add their slots one after the other, a
+    butterfly adds the lanes of a wave, a long row's four wave sums are added in wave order, and the row's own z comes last.  An
+    addition one of whose operands is 0.0 (a lane with no slot, a leaf outside the support) is exact, and a tree has at most
+    (leaves - 1) additions both of whose operands hold a leaf, so an entry passes through at most deg of them that round; deg + 1
+    is counted.  s~ carries two roundings of its own (the square root and the division) and is used twice, in v and in the z
+    handed on, four in all; c = t / (k + 1) is one rounding; the scalings by s~ and by c in v are one each and the scaling by s~
+    in z_out one more, three.  That is deg + 1 + 4 + 1 + 3 = deg + 9 <= d_max + 9 roundings from z to z, of which v has taken
+    deg + 6 and z_out adds three; the first z = s~ e^-t carries one for e^-t, two for s~ and one for the product.  Term k
+    therefore carries at most 4 + (k - 1)(d_max + 9) + d_max + 6 = k (d_max + 9) + 1 relative roundings, and x after K terms, with
+    the K additions into x, at most K (d_max + 9) + 1 + K <= (K + 1)(d_max + 10) of them, times u (1 + O(K d_max u)).  Stated with
+    2^-52 and d_max + 12 it has more than a factor of two in hand, which covers the second-order terms, a libm whose exp is a
+    little more than half an ulp off, a device square root that is within one ulp and not half of one (two more roundings a
+    term), and the np.longdouble arithmetic of the oracle it is compared with (2^-11 of it)."""
     return (K + 1) * (d_max + 12) * EPS

@@ -25,6 +25,7 @@ import diffusion_ref
 import heat_ref as ref
 import scale_ref
 from conftest import load_golden
+from heat_steps_ref import accept   # the acceptance rule of the head of this file; tests/test_heat_steps_cpu.py shows what it lets through
 
 pytestmark = pytest.mark.gpu
 
@@ -59,26 +60,6 @@ def sparse(G, t, **kw):
     assert info['ptr'][0] == 0 and info['ptr'][-1] == w.size and info['converged'].all() and info['terms'] == ref.terms(t, TOL)
     assert 'residual' not in info and 'steps' not in info
     return ei, w, info
-
-
-def accept(x, info, want, oracle, ei, n, src, t, label):
-    """The acceptance rule of the head of this file for the columns `src`, and the two statements about the deficit."""
-    _, _, r, deg = ref.operator_long(ei, n)
-    K, d_max = info['terms'], int(deg.max()) if n else 0
-    a = ref.allow(K, d_max)
-    src = np.asarray(src, dtype=np.int64)
-    diff = np.asarray(want, dtype=L) - x
-    hi = info['deficit'].astype(L)[:, None] / r[None, :]   # deficit_j / r_i
-    print(f'  {label}: {len(x)} columns, K {K}, want - x in [{float(diff.min()):.3e}, {float(diff.max()):.3e}], allow {a:.3e}, '
-          f'oracle {float(oracle):.3e}, deficit {info["deficit"].min():.3e} .. {info["deficit"].max():.3e}')
-    assert np.all(x >= 0.0)
-    assert np.all(diff >= -a), (label, 'above the oracle', float(diff.min()))
-    assert np.all(diff <= hi + a + oracle), (label, 'below the bound', float((diff - hi).max()))
-    own = r[src] - x.astype(L) @ r                       # the deficit of the device's own column
-    slack = (n + 2) * ref.EPS * r[src]
-    got = info['deficit'].astype(L)
-    assert np.all(np.abs(got - own) <= slack), (label, 'deficit of the own column', float(np.abs(got - own).max()))
-    assert np.all(np.abs(got - r[src] * ref.tail(t, K)) <= slack + a * r[src]), (label, 'deficit against r rho_K')
 
 
 def against_taylor(G, ei, n, src, t, label, **kw):
