@@ -185,6 +185,13 @@ __device__ inline unsigned h2_eq4(const unsigned kk[4], unsigned u) {
     return (kk[0] == u ? 1u : 0u) | (kk[1] == u ? 2u : 0u) | (kk[2] == u ? 4u : 0u) | (kk[3] == u ? 8u : 0u);
 }
 
+// the entry of a piece that the one-hot 4-bit `b` names: three selects (written as a chain of b == 1, b == 2, ... it is
+// compiled into a switch: three branches per entry)
+__device__ inline unsigned h2_pick4(const int4 w, unsigned b) {
+    const int lo = (b & 1u) ? w.x : w.y, hi = (b & 4u) ? w.z : w.w;
+    return (unsigned)((b & 3u) ? lo : hi);
+}
+
 __device__ inline unsigned h2_piece_mask(int a, int lo, int hi) {
     const int s = lo - a, t = hi - a;
     const unsigned head = s > 0 ? (0xFu << s) & 0xFu : 0xFu;
@@ -321,6 +328,21 @@ __device__ inline int h2_prefix(int np, int &excl) {
     }
     excl = incl - np;
     return __shfl(incl, 63);
+}
+
+// The same for the exact-path queue's per-lane counts, in registers alone (h2_prefix goes six times through ds_bpermute, and
+// the queue wants its prefix once per node and sweep): shifts by 1, 2, 4, 8 inside each row of 16 lanes, then lane 15 of
+// rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3.
+__device__ inline int h2_prefix_dpp(int np, int &excl) {
+    int incl = np;
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);  // row_shr:1 (lanes without a source add 0)
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);  // row_shr:2
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);  // row_shr:4
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);  // row_shr:8
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);  // row_bcast:15, rows 1 and 3
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);  // row_bcast:31, rows 2 and 3
+    excl = incl - np;
+    return __builtin_amdgcn_readlane(incl, 63);
 }
 
 // ---- the retry list: nodes whose tables filled up in their class -------------------------------------------------------
@@ -535,6 +557,7 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         qn = 0;
     };
     unsigned fl[NP];
+    int nfl = 0;  // this lane's flagged entries
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         fl[q] = 0u;
@@ -544,36 +567,33 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         const unsigned isu = h2_eq4(kk, (unsigned)u) & vm;
         if (isu) s->b.rev[(int)((meta[q] >> 4) & 0xFFull)] = (int)(meta[q] >> 12) + __ffs((int)isu) - 1;  // where u sits in that row
         fl[q] = h2_again4<L1>(s->b2, kk, vm & ~isu);
+        nfl += __popc(fl[q]);
     }
-    // the flagged entries are queued; the drain has ONE call site (inlined per entry position the kernels outgrew the
-    // instruction cache)
+    // The flagged entries are queued by LANE, not by entry position (one ballot, count and branch per position cost the
+    // same 4 x NP times per node whether one entry in twenty is flagged, as on the bench graph, or all of them): one prefix
+    // over the lanes' flag counts gives each lane the queue indices of its own entries, which it writes walking the set bits
+    // of its flags.  The queue's ORDER is all this changes (lane by lane instead of position by position).  More than H2_QCAP
+    // entries go in rounds cut by queue index: round r takes the indices [r x H2_QCAP, (r + 1) x H2_QCAP), and a lane whose
+    // run of indices crosses the cut goes on in the next round where it stopped.  The drain has ONE call site (inlined per
+    // entry position the kernels outgrew the instruction cache).
+    int qi;  // queue index of this lane's next entry, counted from the start of the round; all before it are queued
+    const int qtotal = h2_prefix_dpp(nfl, qi);
 #pragma unroll 1
-    while (true) {
-        bool stop = false;  // uniform: the queue is full, the rest waits for the drain
+    for (int left = qtotal; left > 0; left -= H2_QCAP) {  // uniform
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
             if (64 * q >= P) continue;  // uniform
-            const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const bool p = (fl[q] >> jj) & 1u;
-                const unsigned long long m = __ballot(p);
-                if (m == 0ull) continue;  // uniform
-                if (stop || qn + __popcll(m) > H2_QCAP) {
-                    stop = true;
-                    continue;
-                }
-                if (p) {
-                    const int idx = qn + __popcll(m & below);
-                    s->b.qk[idx] = kk[jj];
-                    s->b.qr[idx] = (unsigned char)((meta[q] >> 4) & 0xFFull);
-                    fl[q] &= ~(1u << jj);
-                }
-                qn += __popcll(m);
+            while (fl[q] != 0u && qi < H2_QCAP) {
+                const unsigned b = fl[q] & (0u - fl[q]);  // the lowest flagged entry of the piece
+                s->b.qk[qi] = h2_pick4(w[q], b);
+                s->b.qr[qi] = (unsigned char)((meta[q] >> 4) & 0xFFull);
+                fl[q] ^= b;
+                ++qi;
             }
         }
-        if (qn > 0) drain();
-        if (!stop) break;
+        qn = left < H2_QCAP ? left : H2_QCAP;
+        drain();
+        qi -= H2_QCAP;  // (a lane with entries left stands at H2_QCAP or beyond: never below 0 while it has any)
     }
     h2_wave_sync();
     if (__ballot(full) != 0ull) {  // a table or the list filled up: nothing is published, the node is redone elsewhere
