@@ -1,5 +1,5 @@
 // What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
-// dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip, dcr_betweenness.hip) and the
+// dcr_resistance_sketch.hip, dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip, dcr_betweenness.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // the batched column CG that the resistance and diffusion solves share, and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
 // dcr_graph.hip stay as they are.
@@ -138,7 +138,7 @@ __device__ __forceinline__ void walk_rows(const RowPlan &plan, const int2 *__res
     }
 }
 
-// ---- batched column conjugate gradients (dcr_resistance.hip, dcr_diffusion.hip) ----------------------------------------------------
+// ---- batched column conjugate gradients (dcr_resistance.hip, dcr_resistance_sketch.hip, dcr_diffusion.hip) ----------------------------------------------------
 // COL_B right-hand sides are solved at a time as COL_B independent CGs in step (not a block CG), from the iterate x = 0.  Every
 // vector is node-major [n][COL_B]: the gather of one neighbour reads COL_B contiguous doubles (a whole 128-byte line at 16 columns).
 // A lane owns two adjacent columns (16-byte loads and stores); COL_CP lanes cover a node.  Each column has its own step length,
@@ -525,6 +525,20 @@ struct AnalysisState {
     int64_t btw_slot_cap = 0;
     unsigned char *btw_ctl = nullptr;  // the batch's control block (BtwCtl of dcr_betweenness.hip)
     int64_t btw_ctl_cap = 0;
+
+    // resistance sketch (dcr_resistance_sketch.hip): O(n B) per group of a launch; O(adjacency slots) only where edge values are asked for
+    double *skt_vec = nullptr;      // per group z, p, r, y, q and the right-hand side s ⊙ b as [n][B] each, then s [n]
+    int64_t skt_vec_cap = 0;
+    double *skt_part = nullptr;     // per-workgroup partial sums, B per workgroup, per group
+    int64_t skt_part_cap = 0;
+    unsigned char *skt_ctl = nullptr;  // the groups' control blocks (SktCtl of dcr_resistance_sketch.hip)
+    int64_t skt_ctl_cap = 0;
+    double *skt_slot = nullptr;     // [cap_total] the sum over the columns per adjacency slot
+    int64_t skt_slot_cap = 0;
+    double *skt_pair = nullptr;     // [P] the same per given pair
+    int64_t skt_pair_cap = 0;
+    int32_t *skt_pair_idx = nullptr;  // [2][P] the pairs' endpoints
+    int64_t skt_pair_idx_cap = 0;
 
     void release();  // frees every buffer
 };

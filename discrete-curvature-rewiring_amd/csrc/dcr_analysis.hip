@@ -130,7 +130,8 @@ void AnalysisState::release() {
     void *ptrs[] = {rows,      chg_members, chg_counts, chg_values, spc_label, spc_ctl,  spc_vec,   spc_basis, spc_rows, spc_chunks,
                     spc_part,  spc_small,   res_vec,    res_part,   res_ctl,   swp_keys, swp_idx,   swp_table, swp_f64,  swp_ctl,
                     dif_vec,   dif_part,    dif_ctl,    dif_row,    dif_val,   fsr_vec,  fsr_part,  fsr_ctl,
-                    hop_bits,  hop_ctl,     hop_dist,   btw_dist,   btw_f64,   btw_slot, btw_ctl};
+                    hop_bits,  hop_ctl,     hop_dist,   btw_dist,   btw_f64,   btw_slot, btw_ctl,   skt_vec,   skt_part, skt_ctl,
+                    skt_slot,  skt_pair,    skt_pair_idx};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     *this = AnalysisState();

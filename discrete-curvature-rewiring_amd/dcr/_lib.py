@@ -42,6 +42,16 @@ class ResistanceOpts(ctypes.Structure):
     _fields_ = [('tol', _f64), ('max_steps', _i64)]
 
 
+class SketchOpts(ctypes.Structure):
+    """dcr_sketch_opts of include/dcr.h."""
+    _fields_ = [('columns', _i32), ('seed', ctypes.c_uint64), ('tol', _f64), ('max_steps', _i64)]
+
+
+class SketchInfo(ctypes.Structure):
+    """dcr_sketch_info of include/dcr.h."""
+    _fields_ = [('columns', _i32), ('batches', _i32), ('steps_total', _i64), ('residual_max', _f64)]
+
+
 class DiffusionOpts(ctypes.Structure):
     """dcr_diffusion_opts of include/dcr.h."""
     _fields_ = [('alpha', _f64), ('tol', _f64), ('max_steps', _i64)]
@@ -119,6 +129,9 @@ SIGNATURES = {
     'dcr_fiedler_sweep': (ctypes.c_int, [_vp, ctypes.POINTER(SpectralOpts), ctypes.c_int, ctypes.POINTER(SpectralResult),
                                          ctypes.POINTER(SweepResult), _i32p, _f64p]),
     'dcr_effective_resistance': (ctypes.c_int, [_vp, _i32p, _i32p, _i64, ctypes.POINTER(ResistanceOpts), _f64p, _f64p, _i32p]),
+    'dcr_resistance_sketch': (ctypes.c_int, [_vp, ctypes.POINTER(SketchOpts), _f64p, _i32p, _i32p, _i64, _f64p, _f64p,
+                                             ctypes.POINTER(SketchInfo)]),
+    'dcr_resistance_sketch_rhs': (ctypes.c_int, [_vp, ctypes.c_uint64, _i64, _f64p]),
     'dcr_ppr_columns': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), _f64p, _f64p, _i32p]),
     'dcr_diffusion_sparsify': (ctypes.c_int, [_vp, _i32p, _i64, ctypes.POINTER(DiffusionOpts), ctypes.c_int, _i64, _f64, _i64p, _i64, _i32p,
                                               _f64p, _f64p, _f64p, _i32p, _i64p]),

@@ -441,6 +441,70 @@ class DcrGraph:
             return lower, {'residual': residual, 'steps': steps, 'converged': converged}
         return lower
 
+    # ---- sketched effective resistance (csrc/dcr_resistance_sketch.hip) -------------------------------------------------
+    def resistance_sketch(self, columns=256, seed=0, pairs=None, edges=True, tol=1e-6, max_steps=20000, return_info=False):
+        """The sketched effective resistance ``R~(u, v) = 1/k sum_j (z_j[u] - z_j[v])^2``, ``L z_j = B^T q_j`` for ``k = columns``
+        Rademacher sign vectors q_j drawn from ``seed`` (include/dcr.h has the rule): unbiased, with a relative standard deviation
+        of at most ``sketch_relative_std(columns) = sqrt(2 / columns)`` for every edge and pair at once, from one set of ``columns``
+        conjugate-gradient solves, ``RESISTANCE_BATCH`` a batch, read-only on the live graph.  With ``edges=True`` returns
+        ``(eu, ev, R)``, ``eu, ev`` being ``self.edges()`` and ``R`` float64 ``[E]`` in that order; with ``pairs`` (array-like
+        ``[P, 2]``) float64 ``[P]``, 0.0 for u == v and inf across components; with both ``((eu, ev, R), pair_values)``.
+        ``return_info``: a dict is appended with ``residual`` (float64 ``[columns]``, the true residual of each column's solve),
+        ``columns``, ``batches``, ``steps_total``, ``residual_max`` and ``converged`` (bool ``[columns]``: ``residual <= 2 tol
+        sqrt(2 E)``.  A column stops at ``tol |s * b_j|`` and ``|s * b_j|^2 = sum_w b_j[w]^2 / deg w <= 2 E``, so a column that
+        fails this has not converged; the norms themselves are not returned).  ``RuntimeWarning`` when a column fails it;
+        ``ValueError`` on an endpoint outside the graph."""
+        if not edges and pairs is None:
+            raise ValueError('nothing asked for: edges=False and no pairs')
+        P = 0
+        u = v = pair_out = None
+        if pairs is not None:
+            pr = np.asarray(pairs)
+            if pr.size == 0:
+                pr = pr.reshape(0, 2)
+            if pr.ndim != 2 or pr.shape[1] != 2:
+                raise ValueError('pairs must have shape [P, 2]')
+            if pr.size and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+                raise ValueError('pair endpoint outside 0 .. num_nodes - 1')
+            u = np.ascontiguousarray(pr[:, 0], dtype=np.int32)
+            v = np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+            P = u.shape[0]
+            pair_out = np.empty(max(P, 1), dtype=np.float64)
+        if not -2 ** 31 <= int(columns) < 2 ** 31:
+            raise ValueError('columns must be >= 1')
+        opts = _lib.SketchOpts(int(columns), int(seed) & (2 ** 64 - 1), float(tol), int(max_steps))
+        eu = ev = edge = None
+        if edges:
+            eu, ev = self.edges()
+            edge = np.empty(max(eu.shape[0], 1), dtype=np.float64)
+        residual = np.empty(max(int(columns), 1), dtype=np.float64)
+        info = _lib.SketchInfo()
+        check(lib().dcr_resistance_sketch(self._h, ctypes.byref(opts), edge.ctypes.data_as(_lib._f64p) if edges else None,
+                                          u.ctypes.data_as(_lib._i32p) if P else None, v.ctypes.data_as(_lib._i32p) if P else None, P,
+                                          pair_out.ctypes.data_as(_lib._f64p) if P else None, residual.ctypes.data_as(_lib._f64p),
+                                          ctypes.byref(info)))
+        residual = residual[:int(columns)]
+        converged = residual <= 2.0 * float(tol) * np.sqrt(2.0 * self.number_of_edges())   # False for a NaN
+        if not converged.all():
+            warnings.warn(f'resistance_sketch: {int((~converged).sum())} of {int(columns)} columns above tol {float(tol):.3e} after '
+                          f'{int(max_steps)} steps (largest residual {info.residual_max:.3e})', RuntimeWarning, stacklevel=2)
+        out = ()
+        if edges:
+            out += ((eu, ev, edge[:eu.shape[0]]),)
+        if pairs is not None:
+            out += (pair_out[:P],)
+        if return_info:
+            out += ({'residual': residual, 'converged': converged, 'columns': int(info.columns), 'batches': int(info.batches),
+                     'steps_total': int(info.steps_total), 'residual_max': float(info.residual_max)},)
+        return out[0] if len(out) == 1 else out
+
+    def resistance_sketch_rhs(self, seed, batch):
+        """The device-drawn right-hand sides ``b_j = B^T q_j`` of the 16 columns of batch ``batch``, as float64 ``[n, 16]`` of
+        integers (for the tests)."""
+        out = np.empty((self.num_nodes, RESISTANCE_BATCH), dtype=np.float64)
+        check(lib().dcr_resistance_sketch_rhs(self._h, int(seed) & (2 ** 64 - 1), int(batch), out.ctypes.data_as(_lib._f64p)))
+        return out
+
     # ---- PageRank diffusion (csrc/dcr_diffusion.hip) ----------------------------------
     def _sources(self, sources):
         src = np.asarray(sources)

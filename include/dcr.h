@@ -297,6 +297,45 @@ int dcr_effective_resistance(dcr_graph *g, const int32_t *u, const int32_t *v, i
                              double *out_lower /* host [P] */, double *out_residual /* host [P] */,
                              int32_t *out_steps /* host [P] or NULL */);
 
+/* ---- sketched effective resistance of every edge (csrc/dcr_resistance_sketch.hip; no counterpart in the reference) -----------
+ * With B the incidence matrix of the live graph, an edge oriented from its smaller to its larger endpoint, R(u, v) =
+ * |B L^+ (e_u - e_v)|^2.  For k = opts.columns sign vectors q_j in {-1, +1}^E (Spielman and Srivastava, with Rademacher signs):
+ *     b_j = B^T q_j,  b_j[w] = sum over the neighbours x of w of q_j({w, x}) (w < x ? +1 : -1),      L z_j = b_j,
+ *     R~(u, v) = 1/k sum_j (z_j[u] - z_j[v])^2.
+ * R~ is unbiased with Var R~(u, v) <= 2 R(u, v)^2 / k, so its relative standard deviation is at most sqrt(2 / k) for every pair at
+ * once; the sum over the edges has mean n - c and variance <= 2 (n - c) / k, c the connected components; on a bridge R~ = 1 for
+ * any signs.  One set of k solves serves every edge and every pair: 16 columns a batch in the column CG of
+ * dcr_effective_resistance, on L' y_j = s ⊙ b_j with z_j = s ⊙ y_j, from y = 0.
+ * Signs: the sign of edge {lo, hi}, lo < hi, in column 16 b + i is bit i of output word 0 of Philox-4x32-10 with counter
+ * {lo, hi, b low, 0x52530000 | b high} and key {seed low, seed high}; a bit of 0 means +1.  Keyed by the endpoints: the signs
+ * of an edge do not depend on the order of the rows or on edits elsewhere in the graph.
+ *   out_edge      host double [num_edges] or NULL: R~ of every edge in the order of dcr_graph_edges.  Without it no per-slot
+ *                 buffer exists.
+ *   u, v, out_pair   P pairs and host double [P], or NULL with P = 0: R~ of each pair; 0 for u == v and +inf across components
+ *                 (an isolated node included), both decided from the connected components.
+ *   out_residual  host double [columns] or NULL: the true residual |s ⊙ b_j - L' y_j|_2 of each column from a mat-vec of its own
+ *                 at the end of its batch.  The error a column's solve leaves in sqrt(R~) is at most residual_j / sqrt(lambda_1).
+ *   out_info      or NULL: columns; batches of 16 that ran; steps_total, the CG steps of all columns; residual_max.
+ * A column stops in the step where the recurrence's |r| <= tol |s ⊙ b_j|, or where p^T L' p is not a positive finite number; an
+ * all-zero b_j takes no step.  opts NULL = defaults: columns 256, seed 0, tol 1e-6 (the solve error only has to sit well below
+ * the sketch's own sqrt(2 / k)), max_steps 20000.  columns need not be a multiple of 16: the padding columns of the last batch
+ * are zero and add nothing.  A column that ran out of steps is still DCR_OK; its residual says so.
+ * All arithmetic is fp64 without floating-point atomics and every sum has an order that the graph and the call fix: a column's
+ * residual depends on (seed, j) and the graph alone, and two calls return the same bits.
+ * READ-ONLY on the graph, runs on the graph's stream and is synchronous on return; work buffers of 768 bytes per node and group
+ * of a launch (at most 4 groups, and 1 above 65,536 nodes), and 8 bytes per adjacency slot where out_edge is given, stay on the
+ * handle until dcr_graph_destroy.  The k x n matrix Z is never stored.
+ * Null g; columns < 1; tol negative or NaN; max_steps < 1; P < 0; P > 0 with a null u, v or out_pair; an endpoint outside
+ * 0 .. num_nodes - 1: DCR_EINVAL before any device call.
+ *   dcr_resistance_sketch_rhs   for the tests: the integers b_j[w] of the 16 columns of batch `batch`, host double [num_nodes][16]. */
+typedef struct { int32_t columns; uint64_t seed; double tol; int64_t max_steps; } dcr_sketch_opts;   /* NULL: 256, 0, 1e-6, 20000 */
+typedef struct { int32_t columns, batches; int64_t steps_total; double residual_max; } dcr_sketch_info;
+int dcr_resistance_sketch(dcr_graph *g, const dcr_sketch_opts *opts,
+                          double *out_edge /* host [n_edges], G.edges() order, or NULL */,
+                          const int32_t *u, const int32_t *v, int64_t P, double *out_pair /* host [P], or NULL with P = 0 */,
+                          double *out_residual /* host [columns] true residual per column, or NULL */, dcr_sketch_info *out_info);
+int dcr_resistance_sketch_rhs(dcr_graph *g, uint64_t seed, int64_t batch, double *out /* host [n][16], the integer b */);
+
 /* ---- PageRank diffusion rewiring, DIGL / GDC (csrc/dcr_diffusion.hip) -------------------------------------------------------
  * With A~ = A + I, d~ = deg + 1, H = D~^-1/2 A~ D~^-1/2 of the live graph and 0 < alpha < 1:  M = I - (1 - alpha) H, symmetric
  * positive definite with spectrum in [alpha, 2 - alpha], and S = alpha M^-1, the personalised-PageRank matrix.  Column j of S
