@@ -870,7 +870,7 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
                 g->h2_expect_retry = true;
             } else if (st == 4 && want_tri) {
                 // launched without its triangle stage, see above: nothing was written.  Like a 3, a 4 stands only where nothing
-                // else went wrong, so k_h2_eset_apply has applied the whole journal (a failure there leaves 1): the launch that
+                // else went wrong, so k_h2_plan<1> has applied the whole journal (a failure there leaves 1): the launch that
                 // follows finds a valid edge set with no edit pending and patches nothing
             } else if (st == 2 && h2_grow_pools(g)) {
                 // the pools of its triangle step were too small (dense neighbourhoods): run it again with what it asked for
@@ -881,7 +881,7 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
             DCR_TRY(pass_again(false));
         }
         if (g->hres->h2_status != 0) g->ext_part_valid = false;  // (the closing kernel wrote nothing)
-        // (advisor, round 4) a two-hop pass that ended with a status may have left its edge set partly patched (k_h2_eset_apply
+        // (advisor, round 4) a two-hop pass that ended with a status may have left its edge set partly patched (h2_eset_apply
         // clears the journal before it applies it): the next two-hop pass rebuilds the set instead of trusting it
         if (g->hres->h2_status != 0) g->h2_eset_valid = false;
         if (g->hres->h2_status != 0 && g->hres->misc[0] == 0) {

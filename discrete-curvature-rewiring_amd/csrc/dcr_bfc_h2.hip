@@ -399,13 +399,14 @@ struct __attribute__((aligned(16))) H2Small {
             unsigned exkey[EXS];            // candidate key, or a member of N(u) | H2_NBR
             unsigned exlo[EXS], exhi[EXS];  // candidate: the rows that hold it (64-bit mask); member of N(u): its position in row u
             unsigned adjlo[64], adjhi[64];  // per row i: the rows adjacent to it = triangle partners of edge {u, v_i}
-            int pos[64], mx[64], rev[64];
+            int pos[64], mx[64];
             unsigned qk[H2_QCAP];
             unsigned short cls[CLCAP];     // candidate occurrences: EX slot ...
             unsigned char qr[H2_QCAP];
             unsigned char clr[CLCAP];      // ... and row
         } b;
     };
+    int rev[64];  // per row i: the slot of u in it (found in sweep A, published at the end of the node: outside the phases)
 };
 
 template <int EXS>
@@ -454,6 +455,7 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         using Lds = H2Small<L1, EXS, CLCAP>;
         static_assert(__builtin_offsetof(Lds, a) == sizeof(unsigned) * ((1 << (L1 - 2)) / 32), "b1 directly behind b2");
         for (int i = lane; i < NZ; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
+        s->rev[lane] = -1;  // (written in sweep A, read when the node is published: no clear in between resets it)
     }
     h2_wave_sync();
     // the members of N(u): seeded into both bitmaps (into the exact table between the sweeps)
@@ -473,14 +475,16 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
     if (lane == 0) s->a.poff[64] = P;
     h2_wave_sync();
     if (P > 64 * NP) full = true;  // (cannot happen: the class bounds the weight; such a node would be redone elsewhere)
-    // every piece of the node is requested at once and kept: meta = valid-entry mask | row << 4 | first slot of the piece << 12
+    // every piece of the node is requested at once and kept: meta = valid-entry mask | row << 4.  (The piece's first slot is
+    // wanted once per ROW, where u sits in it: sweep A works it out again from the descriptors, still in LDS then, instead of
+    // every piece carrying it through both sweeps and the queue loop in a register of its own.)
     int4 w[NP];
-    unsigned long long meta[NP];
+    unsigned meta[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         const int j = 64 * q + lane;
         w[q] = make_int4(0, 0, 0, 0);
-        meta[q] = 0ull;
+        meta[q] = 0u;
         const int jf = 64 * q, jl = jf + 63 < P ? jf + 63 : P - 1;
         if (jf >= P) continue;  // uniform
         const int r = h2_piece_row(s->a.poff, poff_lane, j < P ? j : jl, jf, jl);
@@ -488,16 +492,21 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
             const int2 d = s->a.desc[r];
             const int a = (d.x & ~3) + 4 * (j - s->a.poff[r]);
             w[q] = load_piece(g.col, a);
-            meta[q] = (unsigned long long)h2_piece_mask(a, d.x, d.x + d.y) | ((unsigned long long)r << 4) | ((unsigned long long)(unsigned)a << 12);
+            meta[q] = h2_piece_mask(a, d.x, d.x + d.y) | ((unsigned)r << 4);
         }
     }
-    // sweep A
+    // sweep A (and, once per row, where u sits in it: the reverse slot of edge {u, v_row})
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         if (64 * q >= P) continue;  // uniform
         const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
-        const unsigned vm = (unsigned)meta[q] & 0xFu;
-        h2_mark4<L1>(s->a.b1, s->b2, kk, vm & ~h2_eq4(kk, (unsigned)u));
+        const unsigned vm = meta[q] & 0xFu;
+        const unsigned isu = h2_eq4(kk, (unsigned)u) & vm;
+        if (isu) {  // (vm != 0: the lane has piece 64 q + lane of row meta >> 4)
+            const int r = (int)(meta[q] >> 4);
+            s->rev[r] = (s->a.desc[r].x & ~3) + 4 * (64 * q + lane - s->a.poff[r]) + __ffs((int)isu) - 1;
+        }
+        h2_mark4<L1>(s->a.b1, s->b2, kk, vm & ~isu);
     }
     mid();
     h2_wave_sync();  // sweep A is through: b1 and the descriptors are dead, their space becomes the second phase's arrays
@@ -510,7 +519,6 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         s->b.adjhi[lane] = 0u;
         s->b.pos[lane] = 0;
         s->b.mx[lane] = 0;
-        s->b.rev[lane] = -1;
     }
     h2_wave_sync();
     if (k >= 0) {  // the members of N(u) into the exact table, flagged, with their position in row u
@@ -563,10 +571,8 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         fl[q] = 0u;
         if (64 * q >= P) continue;  // uniform
         const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
-        const unsigned vm = (unsigned)meta[q] & 0xFu;
-        const unsigned isu = h2_eq4(kk, (unsigned)u) & vm;
-        if (isu) s->b.rev[(int)((meta[q] >> 4) & 0xFFull)] = (int)(meta[q] >> 12) + __ffs((int)isu) - 1;  // where u sits in that row
-        fl[q] = h2_again4<L1>(s->b2, kk, vm & ~isu);
+        const unsigned vm = meta[q] & 0xFu;
+        fl[q] = h2_again4<L1>(s->b2, kk, vm & ~h2_eq4(kk, (unsigned)u));
         nfl += __popc(fl[q]);
     }
     // The flagged entries are queued by LANE, not by entry position (one ballot, count and branch per position cost the
@@ -586,7 +592,7 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
             while (fl[q] != 0u && qi < H2_QCAP) {
                 const unsigned b = fl[q] & (0u - fl[q]);  // the lowest flagged entry of the piece
                 s->b.qk[qi] = h2_pick4(w[q], b);
-                s->b.qr[qi] = (unsigned char)((meta[q] >> 4) & 0xFFull);
+                s->b.qr[qi] = (unsigned char)(meta[q] >> 4);
                 fl[q] ^= b;
                 ++qi;
             }
@@ -613,7 +619,7 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
     }
     h2_wave_sync();
     if (k >= 0) {
-        const int rev = s->b.rev[lane];
+        const int rev = s->rev[lane];
         if (rev < 0 || rev >= g.cap_total) {
             row_ok(g, make_int2(-1, rev), 33, u, k);  // adjacency not symmetric: report, never publish
         } else {
@@ -645,7 +651,10 @@ template <int L1, int EXS, int CLCAP, int WPB, int NP>
 __global__ void __launch_bounds__(64 * WPB, (L1 == 14 ? H2_OCC0 : L1 == 15 ? H2_OCC1 : H2_OCC2)) k_h2_small(View g, const int4 *units, const int32_t *count, int64_t unit_cap,
                                                        uint4 *rec, H2Retry rt) {
     __shared__ H2Small<L1, EXS, CLCAP> sm[WPB];
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave's index as a scalar in the two lighter classes: the unit walk — `it`, the units two nodes ahead — then lives in
+    //  scalar registers instead of vector registers spilled around every node; the heaviest class spilled one more with it)
+    const int wid = L1 == 16 ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
     const int total = *count;
     if (total < 0 || total > unit_cap) {
         row_ok(g, make_int2(-1, total), 34, 0, 0);
@@ -773,7 +782,7 @@ __device__ inline int h2_query(const H2Tab t, unsigned w, bool &nbr) {
 // ---- the edge set: every undirected edge as one 64-bit key in an open-addressing table in device memory -------------------
 // The triangle step asks it "is w adjacent to t?" a few times per edge with triangles.  Built once (one CAS per edge) and
 // then KEPT across passes (round 4): the SDRF loop changes one or two edges between two passes, the edit kernels journal them
-// (DevResult::edit_log) and k_h2_eset_apply brings the set up to date — an insertion, or a tombstone in place of a removed
+// (DevResult::edit_log) and h2_eset_apply, one thread of k_h2_plan<1>, brings the set up to date — an insertion, or a tombstone in place of a removed
 // key (probes walk over tombstones; the bitmap in front of the table keeps the removed edge's bit: a false positive the
 // table then answers).  Rebuilt when the journal overflowed, the table was re-sized, or tombstones have piled up.
 constexpr unsigned long long H2_ESET_EMPTY = ~0ull;
@@ -805,9 +814,8 @@ __device__ inline bool h2_eset_has(const H2EdgeSet es, int a, int b) {
     }
     return false;
 }
-// the journaled edits, in order, by one thread (a handful per SDRF iteration)
-__global__ void k_h2_eset_apply(H2EdgeSet es, DevResult *res, int32_t *status) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// the journaled edits, in order, by ONE thread of the pass (a handful per SDRF iteration): see k_h2_plan
+__device__ inline void h2_eset_apply(const H2EdgeSet es, DevResult *res, int32_t *status) {
     const int n = res->edit_n;
     res->edit_n = 0;
     if (n < 0 || n > EDIT_LOG_CAP) {  // (the host counts the edit launches and rebuilds instead: cannot happen)
@@ -1925,13 +1933,19 @@ __device__ inline void h2_classify(int d, int S, int &cls, int &wb, int &nparts)
 // zeroes the node flags of the incremental pass, and its workgroup 0 the bucket half of the NEXT pass and the per-pass fields of
 // the result block (none is read or written before PHASE 1; this half was left zero by the pass before, or by k_h2_clear);
 // PHASE 1 zeroes the records of the nodes it puts into the split class (their partitions add into them), a wave per row.
+// `journal` != 0 (PHASE 1 only, with either head): the edge set is kept and edits are pending.  The launch then has ONE
+// workgroup more than the nodes need — none of its threads has a node to place — and that workgroup's first thread applies the
+// journal before anything else.  No plan kernel reads the edge set, the block classes that probe it are launched behind this
+// kernel on every stream, and the per-pass fields of the result block (the status among them) were cleared by the kernel before.
 template <int PHASE>
 __global__ void __launch_bounds__(H2_PLAN_THREADS) k_h2_plan(View g, int32_t *weight, H2Lists L, DevResult *res, int parity, int head,
-                                                             unsigned *dirty_words, int64_t n_dirty_words, uint4 *rec) {
+                                                             unsigned *dirty_words, int64_t n_dirty_words, uint4 *rec, H2EdgeSet es,
+                                                             int journal) {
     __shared__ int blk_count[H2_NB];
     __shared__ int blk_base[H2_NB];
     const int u = blockIdx.x * H2_PLAN_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
+    if (PHASE == 1 && journal && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) h2_eset_apply(es, res, &res->h2_status);
     if (threadIdx.x < H2_NB) blk_count[threadIdx.x] = 0;
     __syncthreads();
     int bkt = -1, cls = -1, wb = 0, nparts = 0;
@@ -2313,11 +2327,17 @@ int launch_curvature_pass_h2(dcr_graph *g) {
         g->h2_weight_valid = true;  // (from here on the edit kernels keep them)
     }
     g->h2_cleared_dirty = whole;
+    // the edge set (probed by the block classes only): kept from the last pass and patched with the journaled edits by one
+    // thread of k_h2_plan<1>, ahead of the fork, or rebuilt on the aux stream beside the class kernels (32 MB of fill and a
+    // million atomics: 0.17 ms of chip time per pass on the bench graph).  (No plan kernel, no nodes: nothing to patch with.)
+    const bool patch = pblocks > 0 && g->h2_eset_valid && g->h2_eset_pending <= EDIT_LOG_CAP &&
+                       g->h2_eset_tombs + g->h2_eset_pending <= ((int64_t)1 << g->h2_eset_bits) / 16;
+    const bool journal = patch && g->h2_eset_pending > 0;
     if (pblocks > 0) {
         hipLaunchKernelGGL(k_h2_plan<0>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight, L,
-                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec);
-        hipLaunchKernelGGL(k_h2_plan<1>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight, L,
-                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec);
+                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec, es, 0);
+        hipLaunchKernelGGL(k_h2_plan<1>, dim3((unsigned)(pblocks + (journal ? 1 : 0))), dim3(H2_PLAN_THREADS), 0, g->stream, vw,
+                           g->h2_weight, L, g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec, es, journal ? 1 : 0);
     }
     // records of split nodes are accumulated with atomics: start from zero (the fast head: k_h2_plan<1> has done it)
     if (!fast_head)
@@ -2355,18 +2375,9 @@ int launch_curvature_pass_h2(dcr_graph *g) {
         }
         return pool[si];
     };
-    // the edge set (probed by the triangle steps only): kept from the last pass and patched with the journaled edits by one
-    // thread on the main stream ahead of the class kernels, or rebuilt on the aux stream beside them (32 MB of fill and a
-    // million atomics: 0.17 ms of chip time per pass on the bench graph)
-    const bool patch = g->h2_eset_valid && g->h2_eset_pending <= EDIT_LOG_CAP &&
-                       g->h2_eset_tombs + g->h2_eset_pending <= ((int64_t)1 << g->h2_eset_bits) / 16;
     bool eset_on_aux = false;
     if (patch) {
-        if (g->h2_eset_pending > 0) {
-            hipLaunchKernelGGL(k_h2_eset_apply, dim3(1), dim3(64), 0, g->stream, es, g->dres, status);
-            g->h2_eset_tombs += g->h2_eset_pending;
-            DCR_HIP(hipEventRecord(g->ev_fork, g->stream));   // (the side streams start behind it: their triangle steps probe the set)
-        }
+        if (journal) g->h2_eset_tombs += g->h2_eset_pending;  // (applied by k_h2_plan<1> above, ahead of the fork)
     } else {
         DCR_HIP(hipStreamWaitEvent(g->aux, g->ev_fork, 0));
         DCR_HIP(hipMemsetAsync(g->h2_eset, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, g->aux));

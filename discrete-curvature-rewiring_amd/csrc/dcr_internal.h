@@ -88,7 +88,7 @@ struct DevResult {
     int32_t h2_fallback;  // block-class units that listed their triangle work for k_h2_triangles instead of joining it themselves
     // Edit journal (round 4): every edge the device adds or removes since the two-hop pass last brought its edge set up to
     // date: {+1 / -1, u, v} per edit, in order; edit_n keeps counting past the capacity (the host then knows the bound on
-    // its own and rebuilds the set).  Written by dev_add_edge / dev_remove_edge, consumed by k_h2_eset_apply.
+    // its own and rebuilds the set).  Written by dev_add_edge / dev_remove_edge, consumed by k_h2_plan<1> (h2_eset_apply).
     int32_t edit_n;
     int32_t edit_log[3 * 8];
     int32_t touched_n;  // nodes on the graph's touched list (every node whose dirty byte went from zero to non-zero since the flags
