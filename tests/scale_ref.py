@@ -57,6 +57,23 @@ def constants():
     assert m, 'the medium rows of a workgroup in row_grid'
     c['MID_ROWS'] = int(m.group(1))
     c.update(column_and_hops_constants())
+    c.update(sketch_constants())
+    return c
+
+
+def sketch_constants():
+    """The constants of csrc/dcr_resistance_sketch.hip that the sizes of tests/test_resistance_sketch_limits_gpu.py depend on;
+    the group rule and the grid of k_sketch_pairs are asserted to be spelled as sketch_groups and sketch_pair_grid restate them."""
+    skt = source('dcr_resistance_sketch.hip')
+    c = {name: constant(skt, name) for name in ('SKT_MAX_GROUPS', 'SKT_GROUP_NODES', 'SKT_PAIR_BLOCKS')}
+    assert re.search(r'int64_t\s+cap\s*=\s*SKT_MAX_GROUPS\s*;', skt), 'the cap of sketch_groups'
+    assert re.search(r'std::max<int64_t>\(1,\s*std::min<int64_t>\(std::min<int64_t>\(cap,\s*batches\),\s*SKT_GROUP_NODES\s*/\s*'
+                     r'std::max<int64_t>\(n,\s*1\)\)\)', skt), 'the rule of sketch_groups'
+    assert re.search(r'first\s*<\s*batches;\s*first\s*\+=\s*R\.groups\)', skt) and re.search(
+        r'ng\s*=\s*\(int\)std::min<int64_t>\(R\.groups,\s*batches\s*-\s*first\)', skt), 'the launches of dcr_resistance_sketch'
+    assert re.search(r'k_sketch_pairs,\s*dim3\(std::min\(blocks_of\(P\s*\*\s*COL_CP\),\s*\(unsigned\)SKT_PAIR_BLOCKS\)\)', skt), 'the grid of k_sketch_pairs'
+    assert re.search(r'e\s*=\s*\(int64_t\)blockIdx\.x\s*\*\s*256\s*\+\s*threadIdx\.x;\s*e\s*<\s*total;\s*e\s*\+=\s*\(int64_t\)gridDim\.x\s*\*\s*256\)', skt) \
+        and re.search(r'total\s*=\s*P\s*\*\s*COL_CP\s*;', skt) and re.search(r'i\s*=\s*e\s*/\s*COL_CP\s*;', skt), 'the loop of k_sketch_pairs'
     return c
 
 
@@ -300,6 +317,77 @@ def resistance_pairs():
     ], dtype=np.int64)
     solved = np.array([i for i in range(len(pairs)) if i not in (5, 6)])
     return pairs, solved, names
+
+
+# ---- the resistance sketch at its group counts and past the grid of k_sketch_pairs (tests/test_resistance_sketch_limits_gpu.py) -----
+def sketch_groups(n, batches, c, env=None):
+    """sketch_groups of csrc/dcr_resistance_sketch.hip; env: the value of DCR_SKETCH_GROUPS, honoured in 1 .. SKT_MAX_GROUPS."""
+    cap = env if env is not None and 1 <= env <= c['SKT_MAX_GROUPS'] else c['SKT_MAX_GROUPS']
+    return max(1, min(cap, batches, c['SKT_GROUP_NODES'] // max(n, 1)))
+
+
+def sketch_launches(n, columns, c, env=None):
+    """The group count of every launch of one dcr_resistance_sketch call, in order."""
+    batches = blocks_of(columns, c['COL_B'])
+    groups = sketch_groups(n, batches, c, env)
+    return [min(groups, batches - first) for first in range(0, batches, groups)]
+
+
+def sketch_pair_grid(P, c):
+    """(workgroups of k_sketch_pairs, trips of its loop, pairs of the last trip)."""
+    grid = min(blocks_of(P * c['COL_CP']), c['SKT_PAIR_BLOCKS'])
+    per_trip = grid * 256 // c['COL_CP']
+    trips = blocks_of(P, per_trip)
+    return grid, trips, P - (trips - 1) * per_trip
+
+
+def sketch_three_groups():
+    """16,900 lattice nodes, a hub of 2,100, two medium rows, three isolated nodes: 65,536 // 16,906 = 3 groups."""
+    if 'skt3' not in _GRAPHS:
+        _GRAPHS['skt3'] = lattice_graph(130, [2100, 40, 300], 3)
+    return _GRAPHS['skt3']
+
+
+def sketch_two_groups():
+    """22,500 lattice nodes and the same hubs and isolated nodes: 65,536 // 22,506 = 2 groups."""
+    if 'skt2' not in _GRAPHS:
+        _GRAPHS['skt2'] = lattice_graph(150, [2100, 40, 300], 3)
+    return _GRAPHS['skt2']
+
+
+# name -> (graph, columns, launches): the large graphs of the sketch's limit tests
+SKETCH_LARGE = {'sketch_three_groups': (sketch_three_groups, 80, [3, 2]), 'sketch_two_groups': (sketch_two_groups, 48, [2, 1]),
+                'diffusion_large': (diffusion_large, 20, [1, 1])}
+SKETCH_SMALL_COLUMNS = {48: [3], 112: [4, 3]}     # on random300 and barbell_20_4: a launch of three groups alone, and four then three
+
+PAIRS_EXTRA = 37       # pairs past SKT_PAIR_BLOCKS workgroups
+FIXED_PAIR_AT = 5      # the fixed pair sits at 0, at FIXED_PAIR_AT and at the same offset into the second trip
+
+
+def sketch_pairs_past_cap(n, names, c, side, seed=77):
+    """(pairs int64 [P, 2], marks) with P = SKT_PAIR_BLOCKS * 256 / COL_CP + PAIRS_EXTRA on a lattice_graph of ``side`` with
+    ``names``: seeded pairs of connected nodes, and at indices of the first trip of k_sketch_pairs and of the second (marks: name
+    -> the two indices, first trip then second) a pair u == v ('same'), one with an isolated node ('isolated', 'isolated_last'),
+    the hub with a lattice node ('hub'), and the pair marks['fixed'] at 0 as well ('fixed': 0, first trip, second trip)."""
+    per_trip = c['SKT_PAIR_BLOCKS'] * 256 // c['COL_CP']
+    P = per_trip + PAIRS_EXTRA
+    rng = np.random.Generator(np.random.PCG64(seed))
+    pairs = rng.integers(0, names['isolated'], size=(P, 2))      # lattice nodes and hubs: one component
+    hub, iso, last = names['hub0'], names['isolated'], names['last']
+    fixed = (hub, side * side // 2 + 7)
+    marks = {'fixed': (0, FIXED_PAIR_AT, per_trip + FIXED_PAIR_AT), 'same': (100, per_trip + 1), 'isolated': (1_000, per_trip + 2),
+             'isolated_last': (20_000, P - 1), 'hub': (per_trip - 1, per_trip), 'pair': fixed}
+    for i in marks['fixed']:
+        pairs[i] = fixed
+    pairs[marks['same'][0]] = (4_321, 4_321)
+    pairs[marks['same'][1]] = (hub, hub)
+    pairs[marks['isolated'][0]] = (iso, 9)
+    pairs[marks['isolated'][1]] = (11, iso + 1)
+    pairs[marks['isolated_last'][0]] = (last, hub)
+    pairs[marks['isolated_last'][1]] = (iso, last)               # two isolated nodes: two components
+    pairs[marks['hub'][0]] = (hub, 0)
+    pairs[marks['hub'][1]] = (side * side - 1, hub)
+    return pairs.astype(np.int64), marks
 
 
 def hop_sources_small():

@@ -95,6 +95,106 @@ def test_cg_replica_is_within_the_residual_bound_of_pinv_and_the_rounding_term_c
     assert skref.ROUNDING_ALLOW == 16.0 * skref.ROUNDING_MEASURED
 
 
+def pinv_error(d, sk):
+    """float64 [k]: a bound on |z_j - z_j*| of Sketch(solver='pinv'), entry by entry: the residual |L z_j - b_j| over the smallest
+    non-zero eigenvalue of L = D - A.  A difference of two entries is within twice that."""
+    lap = np.diag(d.deg) - d.a
+    lam = np.linalg.eigvalsh(lap)[d.count]
+    return np.linalg.norm(sk.z @ lap - sk.b, axis=1) / lam
+
+
+def test_windmill_closed_form_against_pinv():
+    """Every kind of blade on both centres, 143 nodes: all edges, pairs inside a blade, across blades of one centre and across the
+    bridge.  The bound is the pseudo-inverse's own (pinv_error) plus 64 roundings of the largest difference for the closed form."""
+    ei, n, parts = skref.windmill(skref.WINDMILL_SMALL, seed=3)
+    assert n == 143 and len(parts) == 1 + 2 * len(skref.BLADES)
+    d = ref.Dense(ei, n)
+    assert d.count == 1
+    c0, c1 = skref.windmill_centres(parts)
+    assert d.deg[c0] == 1 + 2 * sum(sum(1 for e in loc if 0 in e) for loc in skref.BLADES.values()) and d.a[c0, c1] == 1.0
+    pairs = np.concatenate([ref.edges(ei), np.random.default_rng(4).integers(0, n, size=(400, 2)), [(c0, c1)]])
+    for k, seed in ((20, 0), (48, 0x9E3779B97F4A7C15)):
+        sk = skref.Sketch(ei, n, k, seed=seed, dense=d)
+        got, want = skref.windmill_diffs(n, parts, seed, k, pairs), sk.diffs(pairs)
+        tol = 2.0 * pinv_error(d, sk)[:, None] + 64 * ref.EPS * np.abs(want).max()
+        print(f'  windmill of 143 nodes, k = {k}: max |a_closed - a_pinv| = {np.abs(got - want).max():.3e}, bound >= {tol.min():.3e}, '
+              f'max |a| = {np.abs(want).max():.3f}')
+        assert np.all(np.abs(got - want) <= tol)
+
+
+def test_sparse_diffs_against_pinv_and_its_two_grounds():
+    for name in ('random300', 'triangle_star_isolated', 'barbell_20_4'):
+        ei, n = skref.GENERAL[name]()
+        d = ref.Dense(ei, n)
+        sk = skref.Sketch(ei, n, 20, seed=0, dense=d)
+        pairs = np.concatenate([ref.edges(ei), skref.pairs_of(n)])
+        inside = d.labels[pairs[:, 0]] == d.labels[pairs[:, 1]]
+        a0, a1 = (skref.sparse_diffs(ei, n, sk.b, pairs, g) for g in ('smallest', 'largest'))
+        assert np.isnan(a0[:, ~inside]).all() and np.isnan(a1[:, ~inside]).all() and np.isfinite(a0[:, inside]).all()
+        want = sk.diffs(pairs)
+        tol = 2.0 * pinv_error(d, sk)[:, None] + 64 * ref.EPS * np.abs(want).max()
+        e_a = skref.ground_error(a0[:, inside], a1[:, inside])
+        print(f'  {name}: max |a_splu - a_pinv| = {np.abs(a0 - want)[:, inside].max():.3e}, bound >= {tol.min():.3e}, e_a = {e_a:.3e}')
+        assert np.all(np.abs(a0 - want)[:, inside] <= tol) and e_a <= 64 * ref.EPS * np.abs(want).max()
+        assert not a0[:, pairs[:, 0] == pairs[:, 1]].any()
+
+
+def test_sparse_cg_is_the_dense_iteration():
+    ei, n = ref.random_graph(300)
+    d, op = ref.Dense(ei, n), skref.SparseOperator(ei, n)
+    assert np.abs(op.lap.toarray() - d.lap).max() <= 4 * ref.EPS and np.array_equal(op.s, d.s)
+    sk = skref.Sketch(ei, n, 4, seed=0, dense=d, solver='cg', tol=1e-12)
+    z, resid, steps = skref.cg_sparse(op, sk.b, tol=1e-12)
+    assert np.array_equal(steps, sk.steps) and np.abs(z - sk.z).max() <= 1e-12 and np.abs(resid - sk.residual).max() <= 1e-14
+
+
+def test_replica_converges_on_the_windmill_and_rounding_at_scale_is_covered():
+    """The measurement behind SCALE_ROUNDING_MEASURED and E_A_MEASURED.  The windmill's normalised Laplacian has few distinct
+    eigenvalues, so the replica takes 47 to 49 steps there at tol 1e-12 on 4,081 nodes."""
+    import scale_ref
+    worst = -np.inf
+    for name in skref.LARGE_CASES:
+        case = skref.large_case(name)
+        got, resid, steps = case.replica()
+        ceiling = 2.0 * 1e-12 * np.sqrt(2.0 * len(case.e))                  # what DcrGraph.resistance_sketch calls converged
+        assert (resid <= ceiling).all() and steps.max() < 1000, (name, resid.max(), steps.max())
+        r_ref = (case.a ** 2).mean(axis=0)
+        gap = np.abs(got - r_ref)
+        bound = case.bound(resid)
+        excess = ((gap - bound) / np.maximum(1.0, r_ref)).max()
+        print(f'  {name}, n = {case.n}, k = {case.k}, seed {case.seed}: steps {steps.min()} .. {steps.max()}, residual <= {resid.max():.3e}, '
+              f'lam_lo = {case.lam_lo:.4e}, e_a = {case.e_a:.3e}, max gap {gap.max():.3e}, max gap / bound {(gap / bound).max():.3e}, '
+              f'excess {excess:.3e}')
+        worst = max(worst, excess)
+        if name == 'windmill':
+            assert steps.max() <= 64 and case.e_a == 0.0
+        else:
+            assert case.e_a <= 16.0 * skref.E_A_MEASURED[name]                  # the rule uses the e_a of this run
+            assert scale_ref.SKETCH_LARGE[name][1] == case.k
+    print(f'  largest excess {worst:.3e}; recorded {skref.SCALE_ROUNDING_MEASURED:.3e}')
+    assert worst <= skref.SCALE_ROUNDING_MEASURED and skref.SCALE_ROUNDING_ALLOW == 16.0 * max(0.0, skref.SCALE_ROUNDING_MEASURED)
+
+
+def test_rounding_term_covers_the_small_graphs_at_the_limit_tests_column_counts():
+    """tests/test_resistance_sketch_limits_gpu.py runs random300 and barbell_20_4 at k = 48 and 112, tol 1e-12, under ROUNDING_ALLOW."""
+    import scale_ref
+    for name in ('random300', 'barbell_20_4'):
+        ei, n = skref.GENERAL[name]()
+        d = ref.Dense(ei, n)
+        lam_lo = ref.lambda1_lower(ei, n, 0)[0]
+        assert 0.0 < lam_lo <= d.lambda1 and d.lambda1 - lam_lo <= 1e-9
+        pairs = np.concatenate([ref.edges(ei), skref.pairs_of(n)])
+        pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+        for k in scale_ref.SKETCH_SMALL_COLUMNS:
+            want = skref.Sketch(ei, n, k, seed=0, dense=d)
+            a = want.diffs(pairs)
+            r_ref = (a ** 2).mean(axis=0)
+            got = skref.Sketch(ei, n, k, seed=0, dense=d, solver='cg', tol=1e-12)
+            excess = ((np.abs(got.values(pairs) - r_ref) - skref.residual_bound(a, got.residual, lam_lo)) / np.maximum(1.0, r_ref)).max()
+            print(f'  {name}, k = {k}, tol 1e-12: excess over the residual bound {excess:.3e}')
+            assert excess <= skref.ROUNDING_MEASURED
+
+
 def test_call_surface():
     from dcr import _lib
     from dcr.graph import DcrGraph

@@ -216,6 +216,95 @@ def test_resistance_and_hop_matvec_grids_past_256_workgroups(c):
                                           'tests/test_hops_gpu.py::test_rows_and_summary_at_70001_nodes)')
 
 
+# ---- the resistance sketch -----------------------------------------------------------------------------------------------------------
+def test_sketch_group_counts_and_launches(c):
+    stale = 'stale GPU size: scale_ref.SKETCH_LARGE / SKETCH_SMALL_COLUMNS (SKT_MAX_GROUPS, SKT_GROUP_NODES: the groups of a launch)'
+    import resistance_sketch_ref as skref
+    assert c['SKT_MAX_GROUPS'] == 4 and skref.BATCH == c['COL_B'], stale
+    at3, at2 = c['SKT_GROUP_NODES'] // 4, c['SKT_GROUP_NODES'] // 3                     # 16,384 and 21,845: the last n of 4 and of 3 groups
+    assert [sc.sketch_groups(n, 9, c) for n in (at3, at3 + 1, at2, at2 + 1, c['SKT_GROUP_NODES'] // 2, c['SKT_GROUP_NODES'] // 2 + 1)] == [4, 3, 3, 2, 2, 1], stale
+    want_n = {'sketch_three_groups': 16_906, 'sketch_two_groups': 22_506, 'diffusion_large': 33_133}
+    for groups, (name, (build, k, launches)) in zip((3, 2, 1), sc.SKETCH_LARGE.items()):
+        ei, n, names = build()
+        assert n == want_n[name] and sc.sketch_groups(n, sc.blocks_of(k, c['COL_B']), c) == groups, stale
+        assert sc.sketch_launches(n, k, c) == launches and sum(launches) == sc.blocks_of(k, c['COL_B']), stale
+        deg = sc.degrees(ei, n)
+        assert (deg > c['SP_LONG_DEG']).sum() == 1 and deg[names['hub0']] == 2100, stale   # exactly one long row
+        assert deg[names['isolated']] == 0 and deg[names['last']] == 0
+    assert sc.SKETCH_LARGE['diffusion_large'][1] % c['COL_B'] == 4                          # twelve padding columns in the second launch
+    for name in ('random300', 'barbell_20_4'):
+        n = skref.GENERAL[name]()[1]
+        assert n <= 300
+        for k, launches in sc.SKETCH_SMALL_COLUMNS.items():
+            assert sc.sketch_launches(n, k, c) == launches, stale
+        assert [sc.sketch_launches(n, 112, c, env) for env in (1, 2, 3, 4, 5)] == [[1] * 7, [2, 2, 2, 1], [3, 3, 1], [4, 3], [4, 3]], stale
+    n = skref.large_case('windmill').n
+    assert sc.sketch_launches(n, skref.WINDMILL_COLUMNS, c) == [4, 3], stale
+    assert sc.sketch_launches(want_n['sketch_three_groups'], 16, c) == [1]              # the one-group call the k = 80 call is compared with
+    assert sc.WHOLE_SMALL > 2 ** 16 and sc.sketch_groups(sc.WHOLE_SMALL, 1, c) == 1      # node ids past 16 bits in the Philox key
+
+
+def test_sketch_pairs_past_the_cap(c):
+    stale = 'stale GPU size: scale_ref.sketch_pairs_past_cap (SKT_PAIR_BLOCKS: second trip of k_sketch_pairs)'
+    ei, n, names = sc.sketch_three_groups()
+    pairs, marks = sc.sketch_pairs_past_cap(n, names, c, 130)
+    per_trip = c['SKT_PAIR_BLOCKS'] * 256 // c['COL_CP']
+    assert per_trip == 32_768 and len(pairs) == per_trip + sc.PAIRS_EXTRA == 32_805, stale
+    assert sc.sketch_pair_grid(per_trip, c) == (c['SKT_PAIR_BLOCKS'], 1, per_trip), stale
+    assert sc.sketch_pair_grid(per_trip + 1, c) == (c['SKT_PAIR_BLOCKS'], 2, 1), stale
+    grid, trips, last = sc.sketch_pair_grid(len(pairs), c)
+    assert (grid, trips) == (c['SKT_PAIR_BLOCKS'], 2) and 0 < last == sc.PAIRS_EXTRA < per_trip, stale   # ragged and not empty
+    assert last * c['COL_CP'] % 256 != 0 and last * c['COL_CP'] > 256, stale            # more than one workgroup, the last partly filled
+    assert sc.sketch_pair_grid(15, c) == (1, 1, 15)                                     # what the other tests pass: one workgroup
+    assert pairs.min() >= 0 and pairs.max() < n
+    deg = sc.degrees(ei, n)
+    for key in ('same', 'isolated', 'isolated_last', 'hub'):
+        first, second = marks[key]
+        assert first < per_trip <= second < len(pairs), (key, stale)
+    f0, f1, f2 = marks['fixed']
+    assert f0 == 0 < f1 < per_trip <= f2 and all(tuple(pairs[i]) == marks['pair'] for i in marks['fixed'])
+    assert deg[marks['pair'][0]] == 2100 and 0 < deg[marks['pair'][1]] <= 5
+    assert all(pairs[i, 0] == pairs[i, 1] for i in marks['same'])
+    assert all((deg[pairs[i]] == 0).sum() >= 1 for i in marks['isolated'] + marks['isolated_last'])
+    assert (deg[pairs[marks['isolated_last'][1]]] == 0).all() and pairs[marks['isolated_last'][1], 0] != pairs[marks['isolated_last'][1], 1]
+    assert all(names['hub0'] in pairs[i] and (pairs[i] < 130 * 130).any() for i in marks['hub'])
+    across = (deg[pairs] == 0).any(axis=1) & (pairs[:, 0] != pairs[:, 1])
+    assert across.sum() == 4 and (pairs[:, 0] == pairs[:, 1]).sum() >= 2
+    again, _ = sc.sketch_pairs_past_cap(n, names, c, 130)
+    assert np.array_equal(pairs, again)
+
+
+def test_no_two_slots_of_the_long_row_can_be_exchanged_unseen(c):
+    """On each large graph the reference values of the long row's edges differ pairwise by more than 100 times the largest
+    acceptance bound among them, the bound taken with the residuals of the float64 CG replica at tol 1e-12 (the device's are the
+    same iteration's): a value written to another slot of the row misses its bound by a factor of 99 at least.  On the windmill
+    the row holds 100 bridges, all 1, and blades of few kinds; there at least 1,000 values lie more than 100 bounds apart."""
+    import resistance_sketch_ref as skref
+    for name in sc.SKETCH_LARGE:
+        case = skref.large_case(name)
+        assert len(case.hub_edges) == 2100 > c['SP_LONG_DEG']
+        want = (case.a[:, case.hub_edges] ** 2).mean(axis=0)
+        bound = case.bound(case.replica()[1])[case.hub_edges].max() + skref.SCALE_ROUNDING_ALLOW * max(1.0, want.max())
+        gap = np.diff(np.sort(want)).min()
+        print(f'  {name}, seed {case.seed}: smallest difference of two values of the long row {gap:.3e}, largest bound {bound:.3e}, ratio {gap / bound:.1f}')
+        assert gap > 100.0 * bound, f'stale seed: resistance_sketch_ref.LARGE_SEEDS[{name!r}]'
+    case = skref.large_case('windmill')
+    want = (case.a[:, case.hub_edges] ** 2).mean(axis=0)
+    bound = case.bound(case.replica()[1])[case.hub_edges].max()
+    distinct = skref.distinct_values(want, 100.0 * bound)
+    kept = skref.distinct_values((case.a[:, case.hub_kept] ** 2).mean(axis=0), 100.0 * bound)
+    print(f'  windmill: {len(case.hub_edges)} slots in the long row, {distinct} values more than 100 bounds apart, largest bound {bound:.3e}; '
+          f'{len(case.hub_kept)} of the slots lead to a larger id and are summed in the row itself, {kept} such values among them')
+    assert len(case.hub_edges) > c['SP_LONG_DEG'] and distinct >= 1000
+    # On the lattice graphs the hub's id is above all its neighbours': k_sketch_accumulate keeps an edge at its smaller endpoint, so
+    # the long row there is walked and writes nothing, and its edges' values come from short rows.  The windmill's first centre has
+    # a low id: its row writes most of its own slots, and at least 1,000 different values among those too.
+    assert all(len(skref.large_case(name).hub_kept) == 0 for name in sc.SKETCH_LARGE)
+    assert len(case.hub_kept) > c['SP_LONG_DEG'] and len(case.hub_edges) - len(case.hub_kept) >= 64 and kept >= 1000
+    mid = skref.windmill_centres(case.parts)[1]
+    assert c['SP_SHORT_DEG'] < sc.degrees(case.ei, case.n)[mid] <= c['SP_LONG_DEG'] and len(skref.WINDMILL_MID) * 3 >= 33
+
+
 # ---- hop distances -------------------------------------------------------------------------------------------------------------------
 def test_hop_count_second_trip(c):
     stale = ('stale GPU size: scale_ref.HOPS_LARGE (HOP_COUNT_BLOCKS: second trip of the chunk loop of k_hop_count, '
