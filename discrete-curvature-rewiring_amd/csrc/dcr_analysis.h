@@ -1,8 +1,9 @@
 // What the graph-analysis translation units share (dcr_cheeger.hip, dcr_spectral.hip, dcr_sweep.hip, dcr_resistance.hip,
 // dcr_resistance_sketch.hip, dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip, dcr_betweenness.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
-// the batched column CG that the resistance and diffusion solves share, and the analysis buffers of a graph.  A new analysis feature adds its buffers and declarations here; dcr_internal.h and
-// dcr_graph.hip stay as they are.
+// the analysis buffers of a graph, and the batched column CG that the resistance and diffusion solves share.  A new analysis
+// feature adds its buffers (one DevBuf line each in AnalysisState) and declarations here; dcr_internal.h and dcr_graph.hip stay
+// as they are.
 #pragma once
 #include "dcr_internal.h"
 
@@ -137,6 +138,99 @@ __device__ __forceinline__ void walk_rows(const RowPlan &plan, const int2 *__res
         }
     }
 }
+
+// ---- the analysis buffers of a graph, grown on demand; dcr_graph::analysis, created on first use (analysis_of) ----------------------
+// A device array that owns its memory.  It is never copied: a copy handed to a kernel launch or a helper would free the memory at
+// the end of the call, with the kernel still queued.  Kernels and helpers take the raw pointer p, which holds until the next grow().
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    int64_t cap = 0;  // elements
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { free(); }
+
+    void free() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // room for `need` elements: what is there when it is enough, else a new array of need + need / 4 + 64; the contents are lost
+    int grow(int64_t need) {
+        if (need <= cap) return DCR_OK;
+        free();
+        const int64_t nc = need + need / 4 + 64;
+        DCR_TRY(dev_alloc(&p, nc));
+        cap = nc;
+        return DCR_OK;
+    }
+};
+
+struct AnalysisState {
+    DevBuf<int32_t> rows;         // [n] rows by degree class (build_row_plan)
+
+    // Monte-Carlo Cheeger estimate (dcr_cheeger.hip): membership words [n][W], counts [3][64 W], ratios [64 W]
+    DevBuf<uint64_t> chg_members;
+    DevBuf<unsigned long long> chg_counts;
+    DevBuf<double> chg_values;
+
+    // connected components (dcr_analysis.hip) and the spectral gap (dcr_spectral.hip)
+    DevBuf<int32_t> spc_label;    // [n] smallest node id of the node's component
+    DevBuf<unsigned> spc_ctl;     // {a sweep of the components changed a label, reduction ticket, -, -}
+    DevBuf<double> spc_vec;       // [4][n]: scale s, null-space weights k, z = s ⊙ v of the newest column, work vector w
+    DevBuf<double> spc_basis;     // [columns][n] Lanczos basis
+    DevBuf<int32_t> spc_rows;     // [n]: nodes by component
+    DevBuf<int4> spc_chunks;      // deflation chunks
+    DevBuf<double> spc_part;      // per-workgroup (per-wave) partial sums
+    DevBuf<double> spc_small;     // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
+
+    // effective resistance (dcr_resistance.hip): O(n B), B the columns of a batch
+    DevBuf<double> res_vec;       // z, p, r, y, q as [n][B] each, then s [n]
+    DevBuf<double> res_part;      // per-workgroup partial sums, B per workgroup (2 B in the closing mat-vec)
+    DevBuf<unsigned char> res_ctl;  // the batch's control block (ResCtl of dcr_resistance.hip)
+
+    // sweep cut (dcr_sweep.hip): all O(n)
+    DevBuf<uint64_t> swp_keys;    // [2][n] sort keys, ping and pong
+    DevBuf<int32_t> swp_idx;      // [6][n]: node ids ping and pong, rank, the three difference arrays (in, lo, hi)
+    DevBuf<int32_t> swp_table;    // [256][tiles] digit counts of a sort pass, then the scans' per-block sums and offsets
+    DevBuf<double> swp_f64;       // [2][n]: the score, the profile
+    DevBuf<unsigned> swp_ctl;     // tickets, NaN flag, the [8][256] digit histogram of the keys, the result block, arg-min partials
+
+    // PageRank diffusion (dcr_diffusion.hip): O(n B) for the solve, O(entries kept by one batch) for the selection
+    DevBuf<double> dif_vec;       // z, p, r, x, q as [n][B] each, then the scale [n]
+    DevBuf<double> dif_part;      // per-workgroup partial sums, B per workgroup
+    DevBuf<unsigned char> dif_ctl;  // the batch's control block (DifCtl of dcr_diffusion.hip)
+    DevBuf<int32_t> dif_row;     // the node ids a batch keeps, column after column
+    DevBuf<double> dif_val;       // their values, then their weights
+
+    // FoSR (dcr_fosr.hip): all O(n)
+    DevBuf<double> fsr_vec;       // [4][n]: the iterate x, its projection, s ⊙ projection, z
+    DevBuf<double> fsr_part;      // per-workgroup partials: sums, or (product, {u, partner}) pairs of the pick
+    DevBuf<unsigned char> fsr_ctl;  // tickets and the result block (FsrCtl of dcr_fosr.hip)
+
+    // hop distances (dcr_hops.hip): O(n W) words, W <= 4 the words of a batch of 64 W sources; O(64 W n) only where rows are asked for
+    DevBuf<uint64_t> hop_bits;    // visited, frontier, next as [n][W] each
+    DevBuf<unsigned char> hop_ctl;  // the batch's running totals [256] (64-bit), then its sources [256]
+    DevBuf<int32_t> hop_dist;     // [64 W][n] distance rows of a batch
+
+    // betweenness (dcr_betweenness.hip): O(16 n) for a batch of 16 sources; O(adjacency slots) only where edge values are asked for
+    DevBuf<int32_t> btw_dist;     // [n][16] the level of the node for each source of the batch, -1: not reached
+    DevBuf<double> btw_f64;       // sigma, delta as [n][16] each, then the sum over the batches [n]
+    DevBuf<double> btw_slot;      // [cap_total] the sum over the batches per adjacency slot
+    DevBuf<unsigned char> btw_ctl;  // the batch's control block (BtwCtl of dcr_betweenness.hip)
+
+    // resistance sketch (dcr_resistance_sketch.hip): O(n B) per group of a launch; O(adjacency slots) only where edge values are asked for
+    DevBuf<double> skt_vec;       // per group z, p, r, y, q and the right-hand side s ⊙ b as [n][B] each, then s [n]
+    DevBuf<double> skt_part;      // per-workgroup partial sums, B per workgroup, per group
+    DevBuf<unsigned char> skt_ctl;  // the groups' control blocks (SktCtl of dcr_resistance_sketch.hip)
+    DevBuf<double> skt_slot;     // [cap_total] the sum over the columns per adjacency slot
+    DevBuf<double> skt_pair;      // [P] the same per given pair
+    DevBuf<int32_t> skt_pair_idx;  // [2][P] the pairs' endpoints
+};
+
+AnalysisState &analysis_of(dcr_graph *g);  // dcr_analysis.hip: the graph's state, created on first use
 
 // ---- batched column conjugate gradients (dcr_resistance.hip, dcr_resistance_sketch.hip, dcr_diffusion.hip) ----------------------------------------------------
 // COL_B right-hand sides are solved at a time as COL_B independent CGs in step (not a block CG), from the iterate x = 0.  Every
@@ -437,114 +531,7 @@ int col_cg_solve(dcr_graph *g, const RowPlan &plan, const ColLayout &L, int ng, 
     return DCR_OK;
 }
 
-// ---- the analysis buffers of a graph, grown on demand; dcr_graph::analysis, created on first use (analysis_of) ----------------------
-struct AnalysisState {
-    int32_t *rows = nullptr;        // [n] rows by degree class (build_row_plan)
-    int64_t rows_cap = 0;
-
-    // Monte-Carlo Cheeger estimate (dcr_cheeger.hip): membership words [n][W], counts [3][64 W], ratios [64 W]
-    uint64_t *chg_members = nullptr;
-    int64_t chg_members_cap = 0;
-    unsigned long long *chg_counts = nullptr;
-    int64_t chg_counts_cap = 0;
-    double *chg_values = nullptr;
-    int64_t chg_values_cap = 0;
-
-    // connected components (dcr_analysis.hip) and the spectral gap (dcr_spectral.hip)
-    int32_t *spc_label = nullptr;   // [n] smallest node id of the node's component
-    int64_t spc_label_cap = 0;
-    unsigned *spc_ctl = nullptr;    // {a sweep of the components changed a label, reduction ticket, -, -}
-    int64_t spc_ctl_cap = 0;
-    double *spc_vec = nullptr;      // [4][n]: scale s, null-space weights k, z = s ⊙ v of the newest column, work vector w
-    int64_t spc_vec_cap = 0;
-    double *spc_basis = nullptr;    // [columns][n] Lanczos basis
-    int64_t spc_basis_cap = 0;
-    int32_t *spc_rows = nullptr;    // [n]: nodes by component
-    int64_t spc_rows_cap = 0;
-    int4 *spc_chunks = nullptr;     // deflation chunks
-    int64_t spc_chunks_cap = 0;
-    double *spc_part = nullptr;     // per-workgroup (per-wave) partial sums
-    int64_t spc_part_cap = 0;
-    double *spc_small = nullptr;    // alpha [m], beta [m], 8 scalars, Gram-Schmidt coefficients [m], Ritz coefficients [m]
-    int64_t spc_small_cap = 0;
-
-    // effective resistance (dcr_resistance.hip): O(n B), B the columns of a batch
-    double *res_vec = nullptr;      // z, p, r, y, q as [n][B] each, then s [n]
-    int64_t res_vec_cap = 0;
-    double *res_part = nullptr;     // per-workgroup partial sums, B per workgroup (2 B in the closing mat-vec)
-    int64_t res_part_cap = 0;
-    unsigned char *res_ctl = nullptr;  // the batch's control block (ResCtl of dcr_resistance.hip)
-    int64_t res_ctl_cap = 0;
-
-    // sweep cut (dcr_sweep.hip): all O(n)
-    uint64_t *swp_keys = nullptr;   // [2][n] sort keys, ping and pong
-    int64_t swp_keys_cap = 0;
-    int32_t *swp_idx = nullptr;     // [6][n]: node ids ping and pong, rank, the three difference arrays (in, lo, hi)
-    int64_t swp_idx_cap = 0;
-    int32_t *swp_table = nullptr;   // [256][tiles] digit counts of a sort pass, then the scans' per-block sums and offsets
-    int64_t swp_table_cap = 0;
-    double *swp_f64 = nullptr;      // [2][n]: the score, the profile
-    int64_t swp_f64_cap = 0;
-    unsigned *swp_ctl = nullptr;    // tickets, NaN flag, the [8][256] digit histogram of the keys, the result block, arg-min partials
-    int64_t swp_ctl_cap = 0;
-
-    // PageRank diffusion (dcr_diffusion.hip): O(n B) for the solve, O(entries kept by one batch) for the selection
-    double *dif_vec = nullptr;      // z, p, r, x, q as [n][B] each, then the scale [n]
-    int64_t dif_vec_cap = 0;
-    double *dif_part = nullptr;     // per-workgroup partial sums, B per workgroup
-    int64_t dif_part_cap = 0;
-    unsigned char *dif_ctl = nullptr;  // the batch's control block (DifCtl of dcr_diffusion.hip)
-    int64_t dif_ctl_cap = 0;
-    int32_t *dif_row = nullptr;     // the node ids a batch keeps, column after column
-    int64_t dif_row_cap = 0;
-    double *dif_val = nullptr;      // their values, then their weights
-    int64_t dif_val_cap = 0;
-
-    // FoSR (dcr_fosr.hip): all O(n)
-    double *fsr_vec = nullptr;      // [4][n]: the iterate x, its projection, s ⊙ projection, z
-    int64_t fsr_vec_cap = 0;
-    double *fsr_part = nullptr;     // per-workgroup partials: sums, or (product, {u, partner}) pairs of the pick
-    int64_t fsr_part_cap = 0;
-    unsigned char *fsr_ctl = nullptr;  // tickets and the result block (FsrCtl of dcr_fosr.hip)
-    int64_t fsr_ctl_cap = 0;
-
-    // hop distances (dcr_hops.hip): O(n W) words, W <= 4 the words of a batch of 64 W sources; O(64 W n) only where rows are asked for
-    uint64_t *hop_bits = nullptr;   // visited, frontier, next as [n][W] each
-    int64_t hop_bits_cap = 0;
-    unsigned char *hop_ctl = nullptr;  // the batch's running totals [256] (64-bit), then its sources [256]
-    int64_t hop_ctl_cap = 0;
-    int32_t *hop_dist = nullptr;    // [64 W][n] distance rows of a batch
-    int64_t hop_dist_cap = 0;
-
-    // betweenness (dcr_betweenness.hip): O(16 n) for a batch of 16 sources; O(adjacency slots) only where edge values are asked for
-    int32_t *btw_dist = nullptr;    // [n][16] the level of the node for each source of the batch, -1: not reached
-    int64_t btw_dist_cap = 0;
-    double *btw_f64 = nullptr;      // sigma, delta as [n][16] each, then the sum over the batches [n]
-    int64_t btw_f64_cap = 0;
-    double *btw_slot = nullptr;     // [cap_total] the sum over the batches per adjacency slot
-    int64_t btw_slot_cap = 0;
-    unsigned char *btw_ctl = nullptr;  // the batch's control block (BtwCtl of dcr_betweenness.hip)
-    int64_t btw_ctl_cap = 0;
-
-    // resistance sketch (dcr_resistance_sketch.hip): O(n B) per group of a launch; O(adjacency slots) only where edge values are asked for
-    double *skt_vec = nullptr;      // per group z, p, r, y, q and the right-hand side s ⊙ b as [n][B] each, then s [n]
-    int64_t skt_vec_cap = 0;
-    double *skt_part = nullptr;     // per-workgroup partial sums, B per workgroup, per group
-    int64_t skt_part_cap = 0;
-    unsigned char *skt_ctl = nullptr;  // the groups' control blocks (SktCtl of dcr_resistance_sketch.hip)
-    int64_t skt_ctl_cap = 0;
-    double *skt_slot = nullptr;     // [cap_total] the sum over the columns per adjacency slot
-    int64_t skt_slot_cap = 0;
-    double *skt_pair = nullptr;     // [P] the same per given pair
-    int64_t skt_pair_cap = 0;
-    int32_t *skt_pair_idx = nullptr;  // [2][P] the pairs' endpoints
-    int64_t skt_pair_idx_cap = 0;
-
-    void release();  // frees every buffer
-};
-
 // dcr_analysis.hip
-AnalysisState &analysis_of(dcr_graph *g);  // the graph's state, created on first use
 // one download of rowinfo (into *info_out too when given), the classification, one upload into AnalysisState::rows
 int build_row_plan(dcr_graph *g, RowPlan *plan, std::vector<int2> *info_out);
 int graph_components(dcr_graph *g, std::vector<int32_t> &labels);  // labels (smallest node id of the component) into spc_label and onto the host

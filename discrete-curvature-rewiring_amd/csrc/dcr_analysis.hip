@@ -52,22 +52,23 @@ int graph_components(dcr_graph *g, std::vector<int32_t> &labels) {
     labels.resize((size_t)n);
     if (n == 0) return DCR_OK;
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.spc_label, &A.spc_label_cap, n));
-    DCR_TRY(dev_regrow(&A.spc_ctl, &A.spc_ctl_cap, 4));
-    hipLaunchKernelGGL(k_cc_init, dim3(blocks_of(n)), dim3(256), 0, g->stream, A.spc_label, n);
+    DCR_TRY(A.spc_label.grow(n));
+    DCR_TRY(A.spc_ctl.grow(4));
+    int32_t *const label = A.spc_label.p, *const flag = (int32_t *)A.spc_ctl.p;
+    hipLaunchKernelGGL(k_cc_init, dim3(blocks_of(n)), dim3(256), 0, g->stream, label, n);
     for (int sweep = 0; g->cap_total > 0; ++sweep) {
         if (sweep > 100000) DCR_FAIL(DCR_ESTATE, "connected components did not settle");
-        DCR_HIP(hipMemsetAsync(A.spc_ctl, 0, 4 * sizeof(int32_t), g->stream));
+        DCR_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(int32_t), g->stream));
         hipLaunchKernelGGL(k_cc_hook, dim3(blocks_of(g->cap_total)), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                           g->cap_total, A.spc_label, (int32_t *)A.spc_ctl);
-        hipLaunchKernelGGL(k_cc_compress, dim3(blocks_of(n)), dim3(256), 0, g->stream, A.spc_label, n);
+                           g->cap_total, label, flag);
+        hipLaunchKernelGGL(k_cc_compress, dim3(blocks_of(n)), dim3(256), 0, g->stream, label, n);
         DCR_HIP(hipGetLastError());
         int32_t changed = 0;
-        DCR_HIP(hipMemcpyAsync(&changed, A.spc_ctl, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(&changed, flag, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
         if (!changed) break;
     }
-    DCR_HIP(hipMemcpyAsync(labels.data(), A.spc_label, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(labels.data(), label, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
@@ -113,10 +114,10 @@ int build_row_plan(dcr_graph *g, RowPlan *plan, std::vector<int2> *info_out) {
     std::vector<int32_t> rows;
     classify_rows(info, rows, plan);
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.rows, &A.rows_cap, n));
-    DCR_HIP(hipMemcpyAsync(A.rows, rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+    DCR_TRY(A.rows.grow(n));
+    DCR_HIP(hipMemcpyAsync(A.rows.p, rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));  // `rows` goes out of scope
-    plan->rows = A.rows;
+    plan->rows = A.rows.p;
     return DCR_OK;
 }
 
@@ -126,21 +127,8 @@ AnalysisState &analysis_of(dcr_graph *g) {
     return *g->analysis;
 }
 
-void AnalysisState::release() {
-    void *ptrs[] = {rows,      chg_members, chg_counts, chg_values, spc_label, spc_ctl,  spc_vec,   spc_basis, spc_rows, spc_chunks,
-                    spc_part,  spc_small,   res_vec,    res_part,   res_ctl,   swp_keys, swp_idx,   swp_table, swp_f64,  swp_ctl,
-                    dif_vec,   dif_part,    dif_ctl,    dif_row,    dif_val,   fsr_vec,  fsr_part,  fsr_ctl,
-                    hop_bits,  hop_ctl,     hop_dist,   btw_dist,   btw_f64,   btw_slot, btw_ctl,   skt_vec,   skt_part, skt_ctl,
-                    skt_slot,  skt_pair,    skt_pair_idx};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    *this = AnalysisState();
-}
-
 void analysis_destroy(dcr_graph *g) {
-    if (!g->analysis) return;
-    g->analysis->release();
-    delete g->analysis;
+    delete g->analysis;  // every DevBuf frees its own array
     g->analysis = nullptr;
 }
 

@@ -188,16 +188,16 @@ struct BtwRun {
     int setup(bool want_edges) {
         n = g->n;
         AnalysisState &A = analysis_of(g);
-        DCR_TRY(dev_regrow(&A.btw_dist, &A.btw_dist_cap, n * BTW_B));
-        DCR_TRY(dev_regrow(&A.btw_f64, &A.btw_f64_cap, 2 * n * BTW_B + n));
-        DCR_TRY(dev_regrow(&A.btw_ctl, &A.btw_ctl_cap, (int64_t)sizeof(BtwCtl)));
-        if (want_edges) DCR_TRY(dev_regrow(&A.btw_slot, &A.btw_slot_cap, g->cap_total));
-        dist = A.btw_dist;
-        sigma = A.btw_f64;  // 16-byte aligned each
+        DCR_TRY(A.btw_dist.grow(n * BTW_B));
+        DCR_TRY(A.btw_f64.grow(2 * n * BTW_B + n));
+        DCR_TRY(A.btw_ctl.grow((int64_t)sizeof(BtwCtl)));
+        if (want_edges) DCR_TRY(A.btw_slot.grow(g->cap_total));
+        dist = A.btw_dist.p;
+        sigma = A.btw_f64.p;  // 16-byte aligned each
         delta = sigma + n * BTW_B;
         node_acc = delta + n * BTW_B;
-        slot_acc = want_edges ? A.btw_slot : nullptr;
-        ctl = reinterpret_cast<BtwCtl *>(A.btw_ctl);
+        slot_acc = want_edges ? A.btw_slot.p : nullptr;
+        ctl = reinterpret_cast<BtwCtl *>(A.btw_ctl.p);
         DCR_TRY(build_row_plan(g, &plan, &info));
         hipStream_t st = g->stream;
         DCR_HIP(hipMemsetAsync(node_acc, 0, sizeof(double) * (size_t)n, st));

@@ -208,9 +208,9 @@ static bool cheeger_use_lane() {
 static int cheeger_buffers(dcr_graph *g, int64_t W) {
     DCR_HIP(hipSetDevice(g->device));
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.chg_members, &A.chg_members_cap, g->n * W));
-    DCR_TRY(dev_regrow(&A.chg_counts, &A.chg_counts_cap, 3 * 64 * W));
-    DCR_TRY(dev_regrow(&A.chg_values, &A.chg_values_cap, 64 * W));
+    DCR_TRY(A.chg_members.grow(g->n * W));
+    DCR_TRY(A.chg_counts.grow(3 * 64 * W));
+    DCR_TRY(A.chg_values.grow(64 * W));
     return DCR_OK;
 }
 
@@ -225,13 +225,13 @@ static void launch_sliced(dcr_graph *g, int W) {
     const int64_t chunk = per_round * rounds;
     const unsigned gx = (unsigned)((g->cap_total + chunk - 1) / chunk);
     hipLaunchKernelGGL(k_cheeger_sliced<WL>, dim3(gx, (unsigned)groups), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                       g->cap_total, g->analysis->chg_members, W, (int)rounds, g->analysis->chg_counts, (int64_t)64 * W);
+                       g->cap_total, g->analysis->chg_members.p, W, (int)rounds, g->analysis->chg_counts.p, (int64_t)64 * W);
 }
 
 // counts of the subsets in chg_members [n][W] -> chg_counts [3][64 W] (after cheeger_buffers), on the graph's stream (no synchronisation)
 static int cheeger_run(dcr_graph *g, int W) {
     const int64_t n_sub = (int64_t)64 * W;
-    DCR_HIP(hipMemsetAsync(g->analysis->chg_counts, 0, sizeof(unsigned long long) * 3 * (size_t)n_sub, g->stream));
+    DCR_HIP(hipMemsetAsync(g->analysis->chg_counts.p, 0, sizeof(unsigned long long) * 3 * (size_t)n_sub, g->stream));
     if (g->cap_total <= 0 || g->n <= 0) return DCR_OK;
     if (cheeger_use_lane()) {
         int64_t per = g->cap_total * W / (8 * (g->num_cu > 0 ? g->num_cu : 256)) + 1;
@@ -239,7 +239,7 @@ static int cheeger_run(dcr_graph *g, int W) {
         if (per < 512) per = 512;
         const unsigned gx = (unsigned)((g->cap_total + per - 1) / per);
         hipLaunchKernelGGL(k_cheeger_lane, dim3(gx, (unsigned)W), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
-                           g->cap_total, g->analysis->chg_members, W, per, g->analysis->chg_counts, n_sub);
+                           g->cap_total, g->analysis->chg_members.p, W, per, g->analysis->chg_counts.p, n_sub);
     } else if (W >= 16) {
         launch_sliced<16>(g, W);
     } else if (W > 4) {
@@ -258,7 +258,7 @@ static int cheeger_run(dcr_graph *g, int W) {
 static int cheeger_draw(dcr_graph *g, uint64_t seed, int64_t first, int W) {
     const int64_t total = g->n * W;
     if (total <= 0) return DCR_OK;
-    hipLaunchKernelGGL(k_cheeger_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_members, g->n, W,
+    hipLaunchKernelGGL(k_cheeger_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_members.p, g->n, W,
                        first / 64, seed);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
@@ -267,7 +267,7 @@ static int cheeger_draw(dcr_graph *g, uint64_t seed, int64_t first, int W) {
 // counts [3][n_sub] on the device -> out [B][3] on the host
 static int cheeger_fetch_counts(dcr_graph *g, int64_t n_sub, int64_t B, int64_t *out) {
     std::vector<unsigned long long> h((size_t)(3 * n_sub));
-    DCR_HIP(hipMemcpyAsync(h.data(), g->analysis->chg_counts, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(h.data(), g->analysis->chg_counts.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     for (int64_t j = 0; j < B; ++j)
         for (int c = 0; c < 3; ++c) out[3 * j + c] = (int64_t)h[(size_t)(c * n_sub + j)];
@@ -294,7 +294,7 @@ int dcr_cheeger_counts(dcr_graph *g, const uint64_t *members, int64_t W, int64_t
     if (W <= 0 || W > CHEEGER_MAX_WORDS) DCR_FAIL(DCR_EINVAL, "W out of range");
     DCR_TRY(cheeger_buffers(g, W));
     if (g->n > 0)
-        DCR_HIP(hipMemcpyAsync(g->analysis->chg_members, members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(g->analysis->chg_members.p, members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyHostToDevice, g->stream));
     DCR_TRY(cheeger_run(g, (int)W));
     return cheeger_fetch_counts(g, 64 * W, 64 * W, out_counts);
 }
@@ -306,7 +306,7 @@ int dcr_cheeger_philox_members(dcr_graph *g, uint64_t seed, int64_t first, int64
     DCR_TRY(cheeger_buffers(g, W));
     DCR_TRY(cheeger_draw(g, seed, first, (int)W));
     if (g->n > 0)
-        DCR_HIP(hipMemcpyAsync(out_members, g->analysis->chg_members, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(out_members, g->analysis->chg_members.p, sizeof(uint64_t) * (size_t)(g->n * W), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
@@ -329,10 +329,10 @@ int dcr_cheeger_philox_values(dcr_graph *g, uint64_t seed, int64_t first, int64_
     DCR_TRY(cheeger_buffers(g, W));
     DCR_TRY(cheeger_draw(g, seed, first, (int)W));
     DCR_TRY(cheeger_run(g, (int)W));
-    hipLaunchKernelGGL(k_cheeger_values, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_counts, 64 * W, B,
-                       g->n_edges, definition, g->analysis->chg_values);
+    hipLaunchKernelGGL(k_cheeger_values, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g->stream, g->analysis->chg_counts.p, 64 * W, B,
+                       g->n_edges, definition, g->analysis->chg_values.p);
     DCR_HIP(hipGetLastError());
-    DCR_HIP(hipMemcpyAsync(out_values, g->analysis->chg_values, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_values, g->analysis->chg_values.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }

@@ -335,14 +335,14 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
     const int64_t gstride = 5 * n * COL_B, pstride = (int64_t)COL_B * std::max(nb_mv, nb_el);
 
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.dif_vec, &A.dif_vec_cap, n + groups * gstride));
-    DCR_TRY(dev_regrow(&A.dif_part, &A.dif_part_cap, groups * pstride));
-    DCR_TRY(dev_regrow(&A.dif_ctl, &A.dif_ctl_cap, (int64_t)sizeof(DifCtl) * groups));
+    DCR_TRY(A.dif_vec.grow(n + groups * gstride));
+    DCR_TRY(A.dif_part.grow(groups * pstride));
+    DCR_TRY(A.dif_ctl.grow((int64_t)sizeof(DifCtl) * groups));
     // per group z, p, r, x, q (16-byte aligned each), then the scale once; the heat kernel has z by turns in z and p, and x
-    double *z = A.dif_vec, *p = z + n * COL_B, *r = p + n * COL_B, *x = r + n * COL_B, *q = x + n * COL_B;
-    double *s = A.dif_vec + groups * gstride;
-    DifCtl *ctl = reinterpret_cast<DifCtl *>(A.dif_ctl);
-    const ColLayout L = {z, p, r, x, q, s, A.dif_part, gstride, pstride, nb_mv, nb_el};
+    double *z = A.dif_vec.p, *p = z + n * COL_B, *r = p + n * COL_B, *x = r + n * COL_B, *q = x + n * COL_B;
+    double *s = z + groups * gstride;
+    DifCtl *ctl = reinterpret_cast<DifCtl *>(A.dif_ctl.p);
+    const ColLayout L = {z, p, r, x, q, s, A.dif_part.p, gstride, pstride, nb_mv, nb_el};
     hipLaunchKernelGGL(k_dif_scale, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, s, n);
     DCR_HIP(hipGetLastError());
 
@@ -379,7 +379,7 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
             for (int64_t k = 0; k < heat->K; ++k, std::swap(z_in, z_out))
                 hipLaunchKernelGGL(k_heat_term, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, z_in, s, heat->t / (double)(k + 1),
                                    z_out, x, gstride);
-            hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo, n, ctl, x, A.dif_part, gstride, pstride);
+            hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo, n, ctl, x, L.part, gstride, pstride);
         } else {
             DCR_TRY(col_cg_solve(g, plan, L, ng, DifProblem{ctl}, h.data(), o.max_steps));
         }
@@ -411,14 +411,15 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
         sp->nnz += batch;
         fits = fits && sp->nnz <= sp->cap;
         if (!fits || batch == 0) continue;  // the remaining columns are still counted
-        DCR_TRY(dev_regrow(&A.dif_row, &A.dif_row_cap, batch));
-        DCR_TRY(dev_regrow(&A.dif_val, &A.dif_val_cap, 2 * batch));
-        double *val = A.dif_val, *wgt = val + batch;
+        DCR_TRY(A.dif_row.grow(batch));
+        DCR_TRY(A.dif_val.grow(2 * batch));
+        int32_t *row = A.dif_row.p;  // both taken after this launch's grow
+        double *val = A.dif_val.p, *wgt = val + batch;
         for (int i = 0; i < ng; ++i)
             DCR_HIP(hipMemcpyAsync(ctl[i].base, h[(size_t)i].base, sizeof(h[0].base), hipMemcpyHostToDevice, g->stream));
-        hipLaunchKernelGGL(k_dif_fill, grid_col, dim3(256), 0, g->stream, x, n, ctl, A.dif_row, val, wgt, gstride);
+        hipLaunchKernelGGL(k_dif_fill, grid_col, dim3(256), 0, g->stream, x, n, ctl, row, val, wgt, gstride);
         DCR_HIP(hipGetLastError());
-        DCR_HIP(hipMemcpyAsync(sp->row + at, A.dif_row, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(sp->row + at, row, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipMemcpyAsync(sp->value + at, val, sizeof(double) * (size_t)batch, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipMemcpyAsync(sp->weight + at, wgt, sizeof(double) * (size_t)batch, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));

@@ -273,16 +273,16 @@ struct FsrRun {
     int setup() {
         n = g->n;
         AnalysisState &A = analysis_of(g);
-        DCR_TRY(dev_regrow(&A.fsr_vec, &A.fsr_vec_cap, 4 * n));
-        DCR_TRY(dev_regrow(&A.fsr_part, &A.fsr_part_cap, 2 * n + FSR_DOT_BLOCKS));  // a workgroup of a row kernel holds a row at least
-        DCR_TRY(dev_regrow(&A.fsr_ctl, &A.fsr_ctl_cap, (int64_t)sizeof(FsrCtl)));
+        DCR_TRY(A.fsr_vec.grow(4 * n));
+        DCR_TRY(A.fsr_part.grow(2 * n + FSR_DOT_BLOCKS));  // a workgroup of a row kernel holds a row at least
+        DCR_TRY(A.fsr_ctl.grow((int64_t)sizeof(FsrCtl)));
         DCR_TRY(sweep_score_buffer(g, &y));
-        x = A.fsr_vec;
+        x = A.fsr_vec.p;
         xp = x + n;
         zs = x + 2 * n;
         z = x + 3 * n;
-        part = A.fsr_part;
-        ctl = (FsrCtl *)A.fsr_ctl;
+        part = A.fsr_part.p;
+        ctl = (FsrCtl *)A.fsr_ctl.p;
         DCR_HIP(hipMemsetAsync(ctl, 0, sizeof(FsrCtl), g->stream));
         std::vector<int2> info;
         DCR_TRY(build_row_plan(g, &plan, &info));
@@ -297,7 +297,7 @@ struct FsrRun {
     // moved in a relayout needs nothing: the plan holds node ids, and every launch takes g->rowinfo as it is then.)
     int edge_added(int32_t u, int32_t v) {
         if (!host.add_edge(u, v)) return DCR_OK;
-        DCR_HIP(hipMemcpyAsync(analysis_of(g).rows, host.rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(analysis_of(g).rows.p, host.rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
         plan.n_long = (int)host.count[0];
         plan.n_mid = (int)host.count[1];

@@ -164,12 +164,12 @@ struct HopRun {
     int setup(bool want_dist, int max_w) {
         n = g->n;
         AnalysisState &A = analysis_of(g);
-        DCR_TRY(dev_regrow(&A.hop_bits, &A.hop_bits_cap, 3 * n * max_w));
-        DCR_TRY(dev_regrow(&A.hop_ctl, &A.hop_ctl_cap, (int64_t)64 * HOP_MAX_W * (int64_t)(sizeof(unsigned long long) + sizeof(int32_t))));
-        if (want_dist) DCR_TRY(dev_regrow(&A.hop_dist, &A.hop_dist_cap, (int64_t)64 * max_w * n));
-        totals = (unsigned long long *)A.hop_ctl;
+        DCR_TRY(A.hop_bits.grow(3 * n * max_w));
+        DCR_TRY(A.hop_ctl.grow((int64_t)64 * HOP_MAX_W * (int64_t)(sizeof(unsigned long long) + sizeof(int32_t))));
+        if (want_dist) DCR_TRY(A.hop_dist.grow((int64_t)64 * max_w * n));
+        totals = (unsigned long long *)A.hop_ctl.p;
         src = (int32_t *)(totals + 64 * HOP_MAX_W);
-        dist = want_dist ? A.hop_dist : nullptr;
+        dist = want_dist ? A.hop_dist.p : nullptr;
         return build_row_plan(g, &plan, nullptr);
     }
 
@@ -179,8 +179,7 @@ struct HopRun {
     int batch(const int32_t *sources, int64_t first, int B, int64_t max_hops, int32_t *out_dist, int32_t *out_ecc, int64_t *out_reached,
               int64_t *out_total) {
         hipStream_t st = g->stream;
-        AnalysisState &A = *g->analysis;
-        visited = A.hop_bits;
+        visited = g->analysis->hop_bits.p;
         frontier = visited + n * W;
         next = frontier + n * W;
         DCR_HIP(hipMemsetAsync(visited, 0, sizeof(uint64_t) * (size_t)(2 * n * W), st));  // (every row writes `next` in every level)

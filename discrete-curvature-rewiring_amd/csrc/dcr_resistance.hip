@@ -81,13 +81,13 @@ static int resistance_batches(dcr_graph *g, const int32_t *u, const int32_t *v, 
     const int nb_el = (int)std::min<int64_t>(COL_UPDATE_BLOCKS, blocks_of(n * COL_CP));
 
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.res_vec, &A.res_vec_cap, n + 5 * n * COL_B));
-    DCR_TRY(dev_regrow(&A.res_part, &A.res_part_cap, (int64_t)COL_B * std::max(2 * nb_mv, nb_el)));
-    DCR_TRY(dev_regrow(&A.res_ctl, &A.res_ctl_cap, (int64_t)sizeof(ResCtl)));
-    double *z = A.res_vec, *p = z + n * COL_B, *r = p + n * COL_B, *y = r + n * COL_B, *q = y + n * COL_B;  // 16-byte aligned each
+    DCR_TRY(A.res_vec.grow(n + 5 * n * COL_B));
+    DCR_TRY(A.res_part.grow((int64_t)COL_B * std::max(2 * nb_mv, nb_el)));
+    DCR_TRY(A.res_ctl.grow((int64_t)sizeof(ResCtl)));
+    double *z = A.res_vec.p, *p = z + n * COL_B, *r = p + n * COL_B, *y = r + n * COL_B, *q = y + n * COL_B;  // 16-byte aligned each
     double *s = q + n * COL_B;
-    const ColLayout L = {z, p, r, y, q, s, A.res_part, 0, 0, nb_mv, nb_el};  // one group
-    const ResProblem prob = {reinterpret_cast<ResCtl *>(A.res_ctl)};
+    const ColLayout L = {z, p, r, y, q, s, A.res_part.p, 0, 0, nb_mv, nb_el};  // one group
+    const ResProblem prob = {reinterpret_cast<ResCtl *>(A.res_ctl.p)};
     inv_sqrt_degree(g, s);
     DCR_HIP(hipGetLastError());
 

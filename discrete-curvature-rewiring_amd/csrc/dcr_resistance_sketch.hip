@@ -179,29 +179,29 @@ struct SketchRun {
         const int nb_el = (int)std::min<int64_t>(COL_UPDATE_BLOCKS, blocks_of(n * COL_CP));
         const int64_t gstride = 6 * n * COL_B, pstride = (int64_t)COL_B * std::max(nb_mv, nb_el);
         AnalysisState &A = analysis_of(g);
-        DCR_TRY(dev_regrow(&A.skt_vec, &A.skt_vec_cap, n + groups * gstride));
-        DCR_TRY(dev_regrow(&A.skt_part, &A.skt_part_cap, groups * pstride));
-        DCR_TRY(dev_regrow(&A.skt_ctl, &A.skt_ctl_cap, (int64_t)sizeof(SktCtl) * groups));
-        double *z = A.skt_vec, *p = z + n * COL_B, *r = p + n * COL_B, *y = r + n * COL_B, *q = y + n * COL_B;  // 16-byte aligned each
+        DCR_TRY(A.skt_vec.grow(n + groups * gstride));
+        DCR_TRY(A.skt_part.grow(groups * pstride));
+        DCR_TRY(A.skt_ctl.grow((int64_t)sizeof(SktCtl) * groups));
+        double *z = A.skt_vec.p, *p = z + n * COL_B, *r = p + n * COL_B, *y = r + n * COL_B, *q = y + n * COL_B;  // 16-byte aligned each
         c = q + n * COL_B;
-        double *s = A.skt_vec + groups * gstride;
-        L = ColLayout{z, p, r, y, q, s, A.skt_part, gstride, pstride, nb_mv, nb_el};
-        prob = SketchProblem{reinterpret_cast<SktCtl *>(A.skt_ctl), c, gstride};
+        double *s = z + groups * gstride;
+        L = ColLayout{z, p, r, y, q, s, A.skt_part.p, gstride, pstride, nb_mv, nb_el};
+        prob = SketchProblem{reinterpret_cast<SktCtl *>(A.skt_ctl.p), c, gstride};
         hipStream_t st = g->stream;
         inv_sqrt_degree(g, s);
         DCR_HIP(hipGetLastError());
         slot_acc = pair_acc = nullptr;
         pair_u = pair_v = nullptr;
         if (want_edges && g->cap_total > 0) {
-            DCR_TRY(dev_regrow(&A.skt_slot, &A.skt_slot_cap, g->cap_total));
-            slot_acc = A.skt_slot;
+            DCR_TRY(A.skt_slot.grow(g->cap_total));
+            slot_acc = A.skt_slot.p;
             DCR_HIP(hipMemsetAsync(slot_acc, 0, sizeof(double) * (size_t)g->cap_total, st));
         }
         if (P > 0) {
-            DCR_TRY(dev_regrow(&A.skt_pair, &A.skt_pair_cap, P));
-            DCR_TRY(dev_regrow(&A.skt_pair_idx, &A.skt_pair_idx_cap, 2 * P));
-            pair_acc = A.skt_pair;
-            pair_u = A.skt_pair_idx;
+            DCR_TRY(A.skt_pair.grow(P));
+            DCR_TRY(A.skt_pair_idx.grow(2 * P));
+            pair_acc = A.skt_pair.p;
+            pair_u = A.skt_pair_idx.p;
             pair_v = pair_u + P;
             DCR_HIP(hipMemsetAsync(pair_acc, 0, sizeof(double) * (size_t)P, st));
             DCR_HIP(hipMemcpyAsync(pair_u, u, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));

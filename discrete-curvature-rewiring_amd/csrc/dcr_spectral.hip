@@ -270,11 +270,7 @@ static bool top_ritz(const double *alpha, const double *beta, int k, bool full, 
 // ---- host: plan, driver ------------------------------------------------------------------------------------------------------------
 void spectral_release_basis(dcr_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    AnalysisState *A = g->analysis;
-    if (!A) return;
-    if (A->spc_basis) (void)hipFree(A->spc_basis);
-    A->spc_basis = nullptr;
-    A->spc_basis_cap = 0;
+    if (g->analysis) g->analysis->spc_basis.free();
 }
 
 struct SpecRun {
@@ -289,25 +285,25 @@ struct SpecRun {
     int32_t *order;
     unsigned *ticket;
 
-    double *col(int j) const { return A->spc_basis + (int64_t)j * n; }
+    double *col(int j) const { return A->spc_basis.p + (int64_t)j * n; }
     // w -= sum_C (k_C . w) k_C; with beta_out also *beta_out = |w| afterwards
     void deflate(double *beta_out) const {
         if (one) {
-            hipLaunchKernelGGL(k_spec_defl_dot<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part);
-            hipLaunchKernelGGL(k_spec_defl_apply<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part,
+            hipLaunchKernelGGL(k_spec_defl_dot<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks.p, order, kd, w, A->spc_part.p);
+            hipLaunchKernelGGL(k_spec_defl_apply<true>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks.p, order, kd, w, A->spc_part.p,
                                ticket, beta_out);
         } else {
-            hipLaunchKernelGGL(k_spec_defl_dot<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part);
-            hipLaunchKernelGGL(k_spec_defl_apply<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks, order, kd, w, A->spc_part,
+            hipLaunchKernelGGL(k_spec_defl_dot<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks.p, order, kd, w, A->spc_part.p);
+            hipLaunchKernelGGL(k_spec_defl_apply<false>, dim3(n_chunks), dim3(256), 0, g->stream, A->spc_chunks.p, order, kd, w, A->spc_part.p,
                                ticket, beta_out);
         }
     }
     // w orthogonal to columns 0 .. jc - 1: classical Gram-Schmidt, twice
     void orthogonalise(int jc) const {
         for (int pass = 0; pass < 2; ++pass) {
-            hipLaunchKernelGGL(k_spec_gs_coef, dim3(blocks_of(n_waves, 4)), dim3(256), 0, g->stream, A->spc_basis, w, n, jc,
-                               n_waves, A->spc_part, coef, ticket);
-            hipLaunchKernelGGL(k_spec_gs_apply, dim3(blocks_of(n)), dim3(256), 0, g->stream, A->spc_basis, w, n, jc, coef);
+            hipLaunchKernelGGL(k_spec_gs_coef, dim3(blocks_of(n_waves, 4)), dim3(256), 0, g->stream, A->spc_basis.p, w, n, jc,
+                               n_waves, A->spc_part.p, coef, ticket);
+            hipLaunchKernelGGL(k_spec_gs_apply, dim3(blocks_of(n)), dim3(256), 0, g->stream, A->spc_basis.p, w, n, jc, coef);
         }
     }
     void normalise(const double *beta_in, int j) const {
@@ -321,7 +317,7 @@ struct SpecRun {
     // Lanczos step j: alpha[j], beta[j], and column j + 1 when there is room for it
     void step(int j, int m) const {
         hipLaunchKernelGGL(k_spec_matvec, dim3(row_grid<SpecRows>(plan)), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, col(j), z, s, w,
-                           A->spc_part, ticket, alpha + j);
+                           A->spc_part.p, ticket, alpha + j);
         // The deflation comes LAST.  Each column carries a rounding-size component along the k_C; Gram-Schmidt hands w the sum
         // of those, weighted by alpha and beta, and with nothing behind it that component obeys the Lanczos recurrence of an
         // eigenvalue inside the spectrum (P B P k = 0) and doubles per step, while alpha = v . B v goes on treating k as
@@ -405,30 +401,30 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
     R.n_waves = (int)((n + SP_WAVE_ELEMS - 1) / SP_WAVE_ELEMS);
 
     // buffers
-    DCR_TRY(dev_regrow(&A.spc_vec, &A.spc_vec_cap, 4 * n));
-    DCR_TRY(dev_regrow(&A.spc_basis, &A.spc_basis_cap, m * n));
-    DCR_TRY(dev_regrow(&A.spc_rows, &A.spc_rows_cap, n));
-    DCR_TRY(dev_regrow(&A.spc_chunks, &A.spc_chunks_cap, (int64_t)chunks.size()));
+    DCR_TRY(A.spc_vec.grow(4 * n));
+    DCR_TRY(A.spc_basis.grow(m * n));
+    DCR_TRY(A.spc_rows.grow(n));
+    DCR_TRY(A.spc_chunks.grow((int64_t)chunks.size()));
     const int64_t part_need = std::max<int64_t>({(int64_t)R.n_waves * m, (int64_t)row_grid<SpecRows>(*plan), 2 * (int64_t)R.n_chunks});
-    DCR_TRY(dev_regrow(&A.spc_part, &A.spc_part_cap, part_need));
-    DCR_TRY(dev_regrow(&A.spc_small, &A.spc_small_cap, 4 * m + 8));
-    DCR_TRY(dev_regrow(&A.spc_ctl, &A.spc_ctl_cap, 4));
-    R.s = A.spc_vec;
-    R.kd = A.spc_vec + n;
-    R.z = A.spc_vec + 2 * n;
-    R.w = A.spc_vec + 3 * n;
-    R.alpha = A.spc_small;
-    R.beta = A.spc_small + m;
-    R.scal = A.spc_small + 2 * m;  // 8 scalars
-    R.coef = A.spc_small + 2 * m + 8;
-    R.ritz = A.spc_small + 3 * m + 8;
-    R.order = A.spc_rows;
-    R.ticket = A.spc_ctl + 1;
-    DCR_HIP(hipMemsetAsync(A.spc_ctl, 0, 4 * sizeof(unsigned), g->stream));
+    DCR_TRY(A.spc_part.grow(part_need));
+    DCR_TRY(A.spc_small.grow(4 * m + 8));
+    DCR_TRY(A.spc_ctl.grow(4));
+    R.s = A.spc_vec.p;
+    R.kd = R.s + n;
+    R.z = R.s + 2 * n;
+    R.w = R.s + 3 * n;
+    R.alpha = A.spc_small.p;
+    R.beta = R.alpha + m;
+    R.scal = R.alpha + 2 * m;  // 8 scalars
+    R.coef = R.alpha + 2 * m + 8;
+    R.ritz = R.alpha + 3 * m + 8;
+    R.order = A.spc_rows.p;
+    R.ticket = A.spc_ctl.p + 1;
+    DCR_HIP(hipMemsetAsync(A.spc_ctl.p, 0, 4 * sizeof(unsigned), g->stream));
     DCR_HIP(hipMemcpyAsync(R.kd, kd.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, g->stream));
     if (!order.empty())
         DCR_HIP(hipMemcpyAsync(R.order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, g->stream));
-    DCR_HIP(hipMemcpyAsync(A.spc_chunks, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
+    DCR_HIP(hipMemcpyAsync(A.spc_chunks.p, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
     inv_sqrt_degree(g, R.s);
     hipLaunchKernelGGL(k_spec_start, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, R.w, n, (uint64_t)0, o.seed);
     R.first_column();
@@ -450,7 +446,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
             const bool early = j + 1 < SP_CHECK_EVERY && ((j + 1) & j) == 0;
             if (!(early || (j + 1) % SP_CHECK_EVERY == 0 || j + 1 == m || forced)) continue;
             DCR_HIP(hipGetLastError());
-            DCR_HIP(hipMemcpyAsync(ab.data(), A.spc_small, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, g->stream));
+            DCR_HIP(hipMemcpyAsync(ab.data(), A.spc_small.p, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, g->stream));
             DCR_HIP(hipStreamSynchronize(g->stream));
             const double *alpha = ab.data(), *beta = ab.data() + m;
             if (j == 0) {  // column 0 is a unit vector of the deflated space: its Rayleigh quotient and its true residual
@@ -481,7 +477,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
             if (!top_ritz(alpha, beta, k, true, &th, vec)) DCR_FAIL(DCR_ESTATE, "spectral gap: the tridiagonal QL iteration did not converge");
             DCR_HIP(hipMemcpyAsync(R.ritz, vec.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, g->stream));
             DCR_HIP(hipStreamSynchronize(g->stream));
-            hipLaunchKernelGGL(k_spec_combine, dim3(blocks_of(n)), dim3(256), 0, g->stream, A.spc_basis, R.ritz, n, k, R.w);
+            hipLaunchKernelGGL(k_spec_combine, dim3(blocks_of(n)), dim3(256), 0, g->stream, A.spc_basis.p, R.ritz, n, k, R.w);
             R.first_column();
             ++restarts;
             last_cycle = breakdown || forced;

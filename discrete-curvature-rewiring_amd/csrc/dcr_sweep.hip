@@ -321,23 +321,23 @@ static int sweep_buffers(dcr_graph *g, SweepPlan *P) {
     P->nb_diff = (int)blocks_of(n, SW_SCAN_BLOCK);
     const int64_t nb_most = std::max<int64_t>(P->nb_table, 3 * (int64_t)P->nb_diff);
     AnalysisState &A = analysis_of(g);
-    DCR_TRY(dev_regrow(&A.swp_keys, &A.swp_keys_cap, 2 * n));
-    DCR_TRY(dev_regrow(&A.swp_idx, &A.swp_idx_cap, 6 * n));
-    DCR_TRY(dev_regrow(&A.swp_table, &A.swp_table_cap, table_len + 2 * nb_most));
-    DCR_TRY(dev_regrow(&A.swp_f64, &A.swp_f64_cap, 2 * n));
-    DCR_TRY(dev_regrow(&A.swp_ctl, &A.swp_ctl_cap, SW_CTL_WORDS));
-    P->keys[0] = A.swp_keys;
-    P->keys[1] = A.swp_keys + n;
-    P->ids[0] = A.swp_idx;
-    P->ids[1] = A.swp_idx + n;
-    P->rank = A.swp_idx + 2 * n;
-    P->diff = A.swp_idx + 3 * n;
-    P->table = A.swp_table;
-    P->part = A.swp_table + table_len;
+    DCR_TRY(A.swp_keys.grow(2 * n));
+    DCR_TRY(A.swp_idx.grow(6 * n));
+    DCR_TRY(A.swp_table.grow(table_len + 2 * nb_most));
+    DCR_TRY(A.swp_f64.grow(2 * n));
+    DCR_TRY(A.swp_ctl.grow(SW_CTL_WORDS));
+    P->keys[0] = A.swp_keys.p;
+    P->keys[1] = A.swp_keys.p + n;
+    P->ids[0] = A.swp_idx.p;
+    P->ids[1] = A.swp_idx.p + n;
+    P->rank = A.swp_idx.p + 2 * n;
+    P->diff = A.swp_idx.p + 3 * n;
+    P->table = A.swp_table.p;
+    P->part = A.swp_table.p + table_len;
     P->boff = P->part + nb_most;
-    P->score = A.swp_f64;
-    P->profile = A.swp_f64 + n;
-    P->ctl = A.swp_ctl;
+    P->score = A.swp_f64.p;
+    P->profile = A.swp_f64.p + n;
+    P->ctl = A.swp_ctl.p;
     return DCR_OK;
 }
 

@@ -234,8 +234,10 @@ def test_call_surface():
     assert 'atomicAdd' not in source                                   # no floating-point atomics: the sums have a fixed order
     for kernel in ('k_sketch_rhs', 'k_sketch_accumulate', 'k_sketch_pairs', 'struct SketchProblem', 'col_cg_solve'):
         assert kernel in source
+    # every buffer of the sketch is an owning member of the analysis state, freed with it
     state = open(os.path.join(CSRC, 'dcr_analysis.h')).read()
-    release = open(os.path.join(CSRC, 'dcr_analysis.hip')).read()
-    release = release[release.index('void AnalysisState::release()'):]
+    state = state[state.index('struct AnalysisState {'):]
+    state = state[:state.index('\n};')]
     for b in ('vec', 'part', 'ctl', 'slot', 'pair', 'pair_idx'):
-        assert f'*skt_{b} = nullptr' in state and re.search(rf'\bskt_{b}\b', release)
+        assert re.search(rf'^\s*DevBuf<[^>]+>\s+skt_{b}\s*;', state, flags=re.M), b
+    assert '*' not in re.sub(r'//.*', '', state)     # no raw pointer left to free by hand
