@@ -18,7 +18,7 @@ def fosr(data, num_iterations, initial_power_iters=50, x0=None, seed=0):
 
     Returns a ``Data`` whose ``edge_index`` int64 ``[2, M + 2 added]`` is the input's (``to_edge_index()`` of a ``DcrGraph``
     before the call) followed by ``(u, v), (v, u)`` of each added edge in the order added, and whose ``edge_type`` int64 is 0 on
-    the input's entries and 1 on the added ones, for the relational models of the paper (which are not part of this package;
+    the input's entries and 1 on the added ones, for the relational models of the paper (models/rgcn.py: ``RGCN`` reads it;
     models/gcn.py trains on ``edge_index`` as it stands).  Every other attribute of a ``Data`` argument is carried over, and the
     tensors are on the device of its ``edge_index``.  Only pairs that are not yet edges are ever added (include/dcr.h)."""
     if isinstance(data, DcrGraph):

@@ -578,6 +578,37 @@ int dcr_spmm_csr_rows2_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev
                                int64_t n_first, int64_t n_sel, const float *B_dev, int64_t b_off2, float *C_dev, int64_t n_feat,
                                int64_t ldb, int64_t ldc, const float *bias_dev, int relu, void *hip_stream);
 
+/* ---- R-GCN typed aggregation (device pointers, caller's stream) ------------
+ * The mean-per-relation layer of Schlichtkrull et al. eq. 2 with c_{i,r} = |N_r(i)| (torch_geometric's RGCNConv with
+ * aggr='mean'; models/rgcn.py), evaluated transform-first: one GEMM forms Zall = X·[W_0 | ... | W_{R-1} | W_root], one
+ * sweep of a typed CSR forms the output.  Typed CSR: rowptr int64, col int32, val float32 (1 / |N_r(i)|) and rel uint8,
+ * one entry per slot.  PRECONDITION: inside every row the slots are sorted by relation (stably within a relation) and
+ * every rel[e] < n_rel; both kernels rely on it (a larger rel[e] is read as n_rel - 1: wrong sums, no stray access).
+ * 1 <= n_rel <= 8; that and every argument error dcr_spmm_csr_f32_dev rejects (null pointers, n_rows < 0, n_feat <= 0,
+ * a leading dimension below its row) return DCR_EINVAL without a launch.  fp32, row-major, leading dimensions in
+ * elements.  Every output element is accumulated with fused multiply-adds over the slots that feed it in CSR order; a
+ * row above 96 slots in the fixed strided order of dcr_spmm_csr_f32_dev, partial sums added in group order.  No
+ * floating-point atomics: the same bits on every run for a given CSR.  Asynchronous on hip_stream.
+ *
+ * The gather (forward), rows = targets:
+ *   C[i,:] = sum_e val[e] * B[col[e], rel[e]*n_feat + :]  (+ B[i, n_rel*n_feat + :] with self_block)  (+ bias)  (ReLU)
+ * the slot sum first, then the row's own block, then the bias, one rounding each.  ldb >= (n_rel + self_block) * n_feat,
+ * ldc >= n_feat; with self_block B has a row for every output row.  With n_rel = 1 and self_block = 0 the result is
+ * dcr_spmm_csr_f32_dev's on the same CSR, bit for bit. */
+int dcr_spmm_csr_typed_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev, const float *val_dev, const uint8_t *rel_dev,
+                               const float *B_dev, float *C_dev, int64_t n_rows, int64_t n_feat, int64_t n_rel, int64_t ldb,
+                               int64_t ldc, int self_block, const float *bias_dev, int relu, void *hip_stream);
+/* The expand (backward), run on the typed CSR of the TRANSPOSED pattern (rows = sources, the same val and rel per edge,
+ * slots again sorted by relation):
+ *   C[j, r*n_feat + :]     = sum_{e in row j, rel[e] = r} val[e] * G[col[e], :]        for every r in [0, n_rel)
+ *   C[j, n_rel*n_feat + :] = G[j, :]                                                    with self_block
+ * Every element of the (n_rel + self_block) * n_feat columns of C is written (zeros where row j has no slot of r), so the
+ * gradient of Zall is complete after one launch and needs no memset.  ldg >= n_feat, ldc >= (n_rel + self_block) * n_feat;
+ * with self_block G has a row for every output row. */
+int dcr_spmm_csr_typed_expand_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev, const float *val_dev,
+                                      const uint8_t *rel_dev, const float *G_dev, float *C_dev, int64_t n_rows, int64_t n_feat,
+                                      int64_t n_rel, int64_t ldg, int64_t ldc, int self_block, void *hip_stream);
+
 /* ---- GCN weight gradient on the matrix cores (device pointers, caller's stream)
  * C[M x N] = A^T * B with A [K x M] and B [K x N] row-major fp32 (lda/ldb/ldc in
  * elements), K = number of nodes: the backward of GCNConv's bias-free Linear,
