@@ -215,7 +215,10 @@ static int spmm_dispatch(const int64_t *rowptr, const int32_t *col, const float 
     const int F = (int)n_feat;
     // (the template is chosen by the width of ONE block: a block of a two-block call is accumulated exactly like a call of its own)
     const bool v4 = (F % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && (((uintptr_t)B & 15) == 0);
-    const bool v2 = (F % 2 == 0) && (ldb % 2 == 0) && (ldc % 2 == 0) && (((uintptr_t)B & 7) == 0);
+    // (rows from `split` on read B + b_off2: the 8-byte path needs that operand aligned too, and falls back to scalar loads
+    //  where it is not; the 16-byte path's second operand is dcr_spmm_csr_rows2_f32_dev's own check)
+    const bool v2 = (F % 2 == 0) && (ldb % 2 == 0) && (ldc % 2 == 0) && (((uintptr_t)B & 7) == 0) &&
+                    (split >= n_rows || b_off2 % 2 == 0);
 #define GO(L, V) launch_spmm<L, V>(rowptr, col, val, B, C, n_rows, F, ldb, ldc, bias, relu, (int)n_blocks, blk_c, st, rows, split, b_off2)
     if (v4) {
         const int lanes = F / 4;
@@ -274,7 +277,8 @@ extern "C" int dcr_spmm_csr_rows_f32_dev(const int64_t *rowptr, const int32_t *c
 
 // Two row lists over two column blocks of one operand in ONE launch: output rows [0, n_first) are rows rows_dev[k] of Â·B0,
 // rows [n_first, n_sel) those of Â·B1 with B1 = B0 + b_off2 floats (the training rows of Â·Z_train and the validation rows of
-// Â·Z_eval of an epoch, Z = [Z_train | Z_eval]).  Each row as dcr_spmm_csr_rows_f32_dev computes it.
+// Â·Z_eval of an epoch, Z = [Z_train | Z_eval]).  Each row as dcr_spmm_csr_rows_f32_dev computes it; where B1 is only 4-byte
+// aligned and B0 would take 8-byte loads, BOTH lists are computed as that call computes B1's (scalar loads).
 extern "C" int dcr_spmm_csr_rows2_f32_dev(const int64_t *rowptr, const int32_t *col, const float *val, const int64_t *rows,
                                           int64_t n_first, int64_t n_sel, const float *B, int64_t b_off2, float *C, int64_t n_feat,
                                           int64_t ldb, int64_t ldc, const float *bias, int relu, void *hip_stream) {

@@ -93,6 +93,59 @@ def test_every_aggregation_entry_point_against_fp64(graph):
         assert torch.equal(gcn.spmm(csr.rowptr, csr.col, csr.val, b0.contiguous(), n, bias)[290], bias)
 
 
+@pytest.mark.parametrize('b_off2', [7, 1])
+def test_rows2_second_operand_an_odd_number_of_floats_on(b_off2):
+    """dcr_spmm_csr_rows2_f32_dev at a width, leading dimensions and a first operand that take 8-byte loads, the second operand
+    an odd number of floats further on: only 4-byte aligned, so the call must fall back to scalar loads, not fail and not load
+    float2 from it.  Small integers and dyadic weights: every fp32 operation is exact, the fp64 product bit for bit."""
+    import numpy as np
+    from dcr import _lib
+    lib = _lib.lib()
+    f, ldb, n = 6, 14, 48
+    rng = np.random.default_rng(50 + b_off2)
+    lengths = [int(rng.integers(0, 9)) for _ in range(n)]
+    lengths[0], lengths[5], lengths[6], lengths[9] = 200, 97, 96, 0          # two hub rows, the longest short row, an empty one
+    rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    col = rng.integers(0, n, rowptr[-1]).astype(np.int32)
+    val = (0.5 ** rng.integers(0, 4, rowptr[-1])).astype(np.float32)
+    A = np.zeros((n, n))
+    np.add.at(A, (np.repeat(np.arange(n), lengths), col), val.astype(np.float64))
+    Bv = np.full((n, ldb), np.nan, dtype=np.float32)                         # NaN in the columns neither operand holds
+    for off in (0, b_off2):
+        Bv[:, off:off + f] = rng.integers(-4, 5, (n, f))
+    bias_v = rng.integers(-3, 4, f).astype(np.float32)
+    rows_a = np.array([0, 3, 5, 6, 9, 20, 47], dtype=np.int64)
+    rows_b = np.array([5, 0, 1, 2, 9, 6, 30, 31, 46], dtype=np.int64)
+    both = np.concatenate([rows_a, rows_b])
+    d_rowptr, d_col, d_val, d_B, d_bias, d_both = (torch.from_numpy(a).cuda() for a in (rowptr, col, val, Bv, bias_v, both))
+    assert d_B.data_ptr() % 16 == 0 and f % 4 == 2 and ldb % 2 == 0 and b_off2 % 2 == 1 and b_off2 + f <= ldb
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def rows2(n_first, n_sel, B, off2, width=f, ld=ldb):
+        out = torch.full((n_sel, width), float('nan'), device='cuda')
+        rc = lib.dcr_spmm_csr_rows2_f32_dev(d_rowptr.data_ptr(), d_col.data_ptr(), d_val.data_ptr(), d_both.data_ptr(), n_first, n_sel,
+                                            B.data_ptr(), off2, out.data_ptr(), width, ld, width, d_bias.data_ptr(), 0, st)
+        return rc, out
+
+    rc, out = rows2(rows_a.size, both.size, d_B, b_off2)
+    assert rc == 0, rc
+    want = np.concatenate([(A @ Bv[:, :f].astype(np.float64))[rows_a], (A @ Bv[:, b_off2:b_off2 + f].astype(np.float64))[rows_b]]) + bias_v
+    assert out.cpu().numpy().tobytes() == (want + 0.0).astype(np.float32).tobytes()
+    # the second list empty: the second operand is never read, the call is dcr_spmm_csr_rows_f32_dev (random floats)
+    R = torch.randn(n, ldb, device='cuda', generator=torch.Generator(device='cuda').manual_seed(b_off2))
+    rc, out = rows2(both.size, both.size, R, b_off2)
+    assert rc == 0, rc
+    one = torch.full((both.size, f), float('nan'), device='cuda')
+    rc = lib.dcr_spmm_csr_rows_f32_dev(d_rowptr.data_ptr(), d_col.data_ptr(), d_val.data_ptr(), d_both.data_ptr(), both.size, R.data_ptr(),
+                                       one.data_ptr(), f, ldb, f, d_bias.data_ptr(), 0, st)
+    assert rc == 0 and bool(torch.isfinite(one).all()) and torch.equal(out, one)
+    # a width that takes 16-byte loads still refuses a second operand that breaks them
+    rc, out = rows2(rows_a.size, both.size, R, b_off2, width=4)
+    assert rc == -1 and b'16 bytes' in lib.dcr_last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())
+
+
 def _model_case(ei, w, n, seed=3):
     from dcr.data import Data, Dataset
     from models.gcn import GCN

@@ -183,6 +183,50 @@ def test_layer_caches_its_csr_per_graph_identity(torch_backend):
     assert conv._cache_csr is None
 
 
+def test_gpu_shapes_reach_every_typed_spmm_instantiation():
+    """tests/test_rgcn_gpu.py launches all 15 (LPR, VEC) instantiations of both kernels, every added width and the third pad
+    is needed for that, and ``vec_lpr`` still is the dispatch csrc/dcr_rgcn.hip has."""
+    import rgcn_shapes as S
+    picked = {S.vec_lpr(f, *S.leading_dims(f, n_rel, self_block, pad)) for f in S.N_FEATS for pad in S.PADS for n_rel in (1, 2, 3, 8)
+              for self_block in (0, 1)}
+    assert picked == {(v, l) for v in (1, 2, 4) for l in (4, 8, 16, 32, 64)}
+    # beyond (VEC, LPR): a second trip of the f0 loop at every VEC, and VEC 2 forced by a leading dimension on 4 to 64 lanes
+    # (path = (VEC, LPR, more than one trip, VEC narrowed by a leading dimension))
+    reached = S.paths()
+    assert {(4, 64, True, False), (2, 64, True, False), (1, 64, True, False)} <= reached
+    assert {(2, 4, False, True), (2, 32, False, True), (2, 64, False, True), (2, 64, True, True)} <= reached
+    # no added entry is idle: without any one of them some path is no longer run
+    for f in (20, 13, 17, 10, 18, 34, 66, 130, 65):
+        assert S.paths(n_feats=[w for w in S.N_FEATS if w != f]) < reached, f
+    assert 2 in S.PADS and S.paths(pads=[p for p in S.PADS if p != 2]) < reached
+    for f in (1, 2, 3, 4, 6, 7, 64, 68, 260):
+        assert f in S.N_FEATS
+    assert {0, 1} <= set(S.PADS)
+    # the table itself, from the text of the source
+    src = open(os.path.join(PKG, 'csrc', 'dcr_rgcn.hip')).read()
+    m = re.search(r'#define DCR_TYPED_PICK\(GO, F, v4, v2\)(.*?)while \(0\)', src, flags=re.S)
+    assert m, 'DCR_TYPED_PICK not found'
+    m = re.search(r'if \(v4\) \{(.*?)\} else if \(v2\) \{(.*?)\} else \{(.*?)\}\s*\\\s*\}', m.group(1), flags=re.S)
+    assert m, 'DCR_TYPED_PICK: not the v4 / v2 / scalar branches'
+    for vec, body in zip((4, 2, 1), m.groups()):
+        if vec > 1:
+            assert re.search(r'const int lanes = \(F\) / %d;' % vec, body), vec
+        count = r'lanes' if vec > 1 else r'\(F\)'
+        steps = re.findall(r'if \(%s <= (\d+)\) GO\((\d+), (\d+)\);' % count, body)
+        assert [tuple(int(x) for x in s) for s in steps] == [(l, l, vec) for l in S.LPRS[:-1]], (vec, steps)
+        last = re.findall(r'else GO\((\d+), (\d+)\);', body)
+        assert [tuple(int(x) for x in s) for s in last] == [(S.LPRS[-1], vec)], (vec, last)
+        assert len(re.findall(r'GO\(', body)) == len(S.LPRS)
+    # what narrows VEC: the width, both leading dimensions and the pointers the entry point names
+    for name, lds, ptrs in (('dcr_spmm_csr_typed_f32_dev', ('ldb', 'ldc'), ('B',)), ('dcr_spmm_csr_typed_expand_f32_dev', ('ldg', 'ldc'), ('G', 'C'))):
+        body = src[src.index('extern "C" int ' + name):]
+        for vec, mask in ((4, 15), (2, 7)):
+            want = r'const bool v%d = \(F %% %d == 0\)' % (vec, vec) + ''.join(r' && \(%s %% %d == 0\)' % (ld, vec) for ld in lds) + \
+                ''.join(r' && \(\(\(uintptr_t\)%s & %d\) == 0\)' % (p, mask) for p in ptrs) + ';'
+            assert re.search(want, body[:body.index('#undef GO')]), (name, vec)
+    assert S.vec_lpr(64, 256, 64) == (4, 16) and S.vec_lpr(64, 256, 64, residues=(8,)) == (2, 32) and S.vec_lpr(64, 256, 64, residues=(0, 4)) == (1, 64)
+
+
 def test_call_surface():
     from dcr import _lib
     header = open(os.path.join(REPO, 'include', 'dcr.h')).read()
