@@ -142,6 +142,18 @@ def test_incremental_pass_of_a_triangle_kind(curv):
         assert library_plan(n, E, 2 * E, sd2, 300, 0, impl, True, None, None, curv, False)[0] in (NC_CLASSES, NC_EDGES)
 
 
+def test_hub_supplement_flips_between_8190_and_8191():
+    """Stated as literals: on both node-centric routes, full and incremental, the hub supplement is planned from a bound on the
+    degrees of 8,191 and not at 8,190 (tests/test_hub_giant_limits_gpu.py moves a node across by single edits)."""
+    n, E, sd2 = 20000, 60000, 3.0e8                # dense enough that no full pass is the two-hop engine's
+    for curv, inc, pending, impl, full, route in (
+            (BFC, False, 0, 2, None, NC_CLASSES), (BFC, False, 0, 2, 2 ** 40, NC_EDGES), (BFC, True, 1, 2, None, NC_EDGES),
+            (BFC, True, DIRTY_EDITS + 1, 2, None, NC_CLASSES), (BFC, True, 1, 0, None, NC_EDGES), (AUGMENTED, False, 0, 2, None, NC_CLASSES),
+            (HAANTJES, True, 1, 0, None, NC_EDGES)):
+        for deg, hub in ((8190, False), (8191, True)):
+            assert library_plan(n, E, 2 * E, sd2, deg, pending, impl, True, full, None, curv, inc)[:3] == (route, False, hub), (curv, inc, deg)
+
+
 def test_constants_are_those_of_the_sources():
     """The limits and guards this file's transcription uses, as the sources spell them: a changed constant is a diff here."""
     assert (H2_MAXDEG, NC_MAXD, DIRTY_EDITS) == (5000, 8190, 3)
