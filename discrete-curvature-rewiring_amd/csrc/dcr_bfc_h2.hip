@@ -441,6 +441,55 @@ __device__ inline int h2s_insert_nbr(unsigned *exkey, unsigned k) {  // the memb
     return -1;
 }
 
+// ---- the wave classes' forms of h2_mark4 and h2_again4 -----------------------------------------------------------------
+// The SAME hashes, words and bits (h2_bit, h2_word_mask, h2_again; the block classes keep the forms above), formed with fewer
+// instructions — the three wave-class kernels sit at their vector-issue limit (profiles/h2_sweep_reuse_ab.txt):
+//  - the word index and the bit of either bitmap are bit fields of ONE product, h2_mul24(key): one extract each, where
+//    h2_bit, a shift and a mask stood;
+//  - an entry that does not count takes mask 0 by an AND with its sign-extended valid bit: written as a conditional the
+//    second multiply (an asm statement, never speculated) kept it a branch of its own per entry;
+//  - the B2 bit of an entry seen before goes in with mask 0 for the other entries of the piece, under the one branch
+//    "any of the four": no branch per entry.
+template <int L1>
+__device__ inline void h2s_mark4(unsigned *b1, unsigned *b2, const unsigned kk[4], unsigned valid) {
+    unsigned p[4], m[4], old[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        p[jj] = h2_mul24(kk[jj]);
+        const unsigned both = (1u << ((p[jj] >> (24 - L1)) & 31u)) | (1u << ((h2_mul24c(kk[jj]) >> 19) & 31u));
+        m[jj] = both & (unsigned)__builtin_amdgcn_sbfe((int)valid, (unsigned)jj, 1u);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) old[jj] = atomicOr(&b1[__builtin_amdgcn_ubfe(p[jj], 29 - L1, L1 - 5)], m[jj]);
+    bool seen[4], any = false;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        seen[jj] = m[jj] != 0u && (old[jj] & m[jj]) == m[jj];
+        any |= seen[jj];
+    }
+    if (any) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+            atomicOr(&b2[__builtin_amdgcn_ubfe(p[jj], 31 - L1, L1 - 7)], seen[jj] ? 1u << ((p[jj] >> (26 - L1)) & 31u) : 0u);
+    }
+}
+// the B2 bits of the four entries (the caller masks them with the entries that count)
+template <int L1>
+__device__ inline unsigned h2s_again4(const unsigned *b2, const unsigned kk[4]) {
+    unsigned p[4], wd[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        p[jj] = h2_mul24(kk[jj]);
+        wd[jj] = b2[__builtin_amdgcn_ubfe(p[jj], 31 - L1, L1 - 7)];
+    }
+    unsigned f = 0u;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) f |= __builtin_amdgcn_ubfe(wd[jj], __builtin_amdgcn_ubfe(p[jj], 26 - L1, 5), 1u) << jj;
+    return f;
+}
+// (The piece-to-row search stays h2_piece_row, from scratch per 64-piece step: bracketing step q + 1 from the last row of step
+//  q saves a ballot and RAISED the vector + scalar instructions per launch of all three kernels — built, measured, dropped.)
+
 // k, rk: the lane's member of N(u) and its row (loaded ahead by the caller); NP: 64-piece steps a node of this class can
 // have — all pieces of the node stay in registers and serve both sweeps; mid(): called once between the sweeps (the
 // caller's prefetch of the next node)
@@ -500,13 +549,15 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
     for (int q = 0; q < NP; ++q) {
         if (64 * q >= P) continue;  // uniform
         const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
-        const unsigned vm = meta[q] & 0xFu;
-        const unsigned isu = h2_eq4(kk, (unsigned)u) & vm;
-        if (isu) {  // (vm != 0: the lane has piece 64 q + lane of row meta >> 4)
+        const unsigned isu = h2_eq4(kk, (unsigned)u) & meta[q] & 0xFu;
+        if (isu) {  // (the lane has piece 64 q + lane of row meta >> 4)
             const int r = (int)(meta[q] >> 4);
             s->rev[r] = (s->a.desc[r].x & ~3) + 4 * (64 * q + lane - s->a.poff[r]) + __ffs((int)isu) - 1;
         }
-        h2_mark4<L1>(s->a.b1, s->b2, kk, vm & ~isu);
+        // u's own entry leaves the piece's valid mask here, for both sweeps: the reverse slot is taken, nothing later reads
+        // that bit, and sweep B need not look for u a second time
+        meta[q] &= ~isu;
+        h2s_mark4<L1>(s->a.b1, s->b2, kk, meta[q] & 0xFu);
     }
     mid();
     h2_wave_sync();  // sweep A is through: b1 and the descriptors are dead, their space becomes the second phase's arrays
@@ -571,8 +622,7 @@ __device__ inline void h2s_node(const View &g, int u, int2 ru, int k, int2 rk, H
         fl[q] = 0u;
         if (64 * q >= P) continue;  // uniform
         const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
-        const unsigned vm = meta[q] & 0xFu;
-        fl[q] = h2_again4<L1>(s->b2, kk, vm & ~h2_eq4(kk, (unsigned)u));
+        fl[q] = h2s_again4<L1>(s->b2, kk) & meta[q] & 0xFu;  // (the valid mask is without u's entry since sweep A)
         nfl += __popc(fl[q]);
     }
     // The flagged entries are queued by LANE, not by entry position (one ballot, count and branch per position cost the

@@ -29,7 +29,8 @@ def load(name):
         acc[k][row['Counter_Name']] += float(row['Counter_Value']); disp[k].add(row['Dispatch_Id'])
     return {k: {c: v / len(disp[k]) for c, v in acc[k].items()} for k in acc}, {k: len(v) for k, v in disp.items()}
 w, nd = load('waits'); i, _ = load('insts'); l, _ = load('lds')
-passes = max(nd.get(k, 0) for k in nd if k.endswith('k_h2_clear')) if any(k.endswith('k_h2_clear') for k in nd) else 1
+# passes profiled: the closing kernel runs once per two-hop launch (k_h2_clear, counted here before, now runs once per process)
+passes = max([nd[k] for k in nd if k.endswith('k_h2_final')] or [1])
 per = {}
 tot_valu = tot_quad = 0.0
 for k in sorted(w):
