@@ -1,293 +1,11 @@
-// GCN sparse aggregation of libdcr_hip.so: C = Â · B (+ bias, ReLU) on CSR, fp32.
-//
-// Replaces the propagate/scatter-add of torch_geometric GCNConv (third-party; call site models/gcn.py:36).
-// HBM / Infinity-Cache gather-bound: every non-zero pulls one row of B (n_feat floats).  A row of Â is owned by a group of LPR lanes,
-// each lane holding VEC consecutive features, so one wave-instruction reads (64/LPR) rows of B in 16-byte
-// pieces (full 128-B lines for n_feat >= 32) and a wave covers 64/LPR output rows.  MFMA has nothing to do here:
-// the dense contraction (X·Wᵀ) is done before this kernel on the matrix cores by the GEMM library.
+// What a GCN training step of libdcr_hip.so does around its sparse aggregation (csrc/dcr_spmm.hip), fp32: ReLU + dropout
+// between the layers, the activation fused into the next layer's dense contraction, loss and accuracy on the selected rows,
+// the head of an epoch in one kernel per direction, and the Adam step as one launch.
 #include <cstdint>
 #include "dcr_internal.h"
 #include "dcr_philox.h"
 
-namespace dcr {
-
-// accumulate non-zeros e0, e0 + stride, ... < e1 of one row into acc (U gathers of B in flight).  NBLK > 1: B holds NBLK
-// column blocks `blk` floats apart (two operands aggregated in one sweep of the indices, models/gcn.py forward_pair);
-// every block is accumulated with exactly the operations, in exactly the order, of a sweep of its own.
-template <int VEC, int U, int NBLK>
-__device__ inline void spmm_accumulate(const int32_t *__restrict__ col, const float *__restrict__ val,
-                                       const float *__restrict__ B, int64_t ldb, int f0, int64_t e0, int64_t e1,
-                                       int64_t stride, int blk, float (&acc)[NBLK][VEC]) {
-    constexpr int UU = NBLK > 1 ? U / 2 : U;  // the same number of gathers in flight
-    int64_t e = e0;
-    for (; e + (UU - 1) * stride < e1; e += UU * stride) {
-        int c[UU];
-        float w[UU];
-        float b[UU][NBLK][VEC];
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-            c[u] = col[e + u * stride];
-            w[u] = val[e + u * stride];
-        }
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) {
-                const float *src = B + (int64_t)c[u] * ldb + f0 + k * blk;
-                if (VEC == 4) {
-                    const float4 t = *reinterpret_cast<const float4 *>(src);
-                    b[u][k][0] = t.x; b[u][k][1 % VEC] = t.y; b[u][k][2 % VEC] = t.z; b[u][k][3 % VEC] = t.w;
-                } else if (VEC == 2) {
-                    const float2 t = *reinterpret_cast<const float2 *>(src);
-                    b[u][k][0] = t.x; b[u][k][1 % VEC] = t.y;
-                } else {
-                    b[u][k][0] = src[0];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UU; ++u)
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k)
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) acc[k][q] = fmaf(w[u], b[u][k][q], acc[k][q]);
-    }
-    // What is left (fewer than UU non-zeros) as ONE more batch with the missing slots masked off — one element at a time, each
-    // with its index load and its gather behind one another, cost two memory latencies per non-zero, and on a graph of
-    // average degree 20 that was most of the kernel's time.  Same operations in the same order: a masked slot adds nothing.
-    if (e < e1) {
-        int c[UU];
-        float w[UU];
-        bool ok[UU];
-        float b[UU][NBLK][VEC];
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-            ok[u] = e + u * stride < e1;
-            c[u] = ok[u] ? col[e + u * stride] : 0;
-            w[u] = ok[u] ? val[e + u * stride] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) {
-                const float *src = B + (int64_t)c[u] * ldb + f0 + k * blk;
-                if (VEC == 4) {
-                    const float4 t = ok[u] ? *reinterpret_cast<const float4 *>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    b[u][k][0] = t.x; b[u][k][1 % VEC] = t.y; b[u][k][2 % VEC] = t.z; b[u][k][3 % VEC] = t.w;
-                } else if (VEC == 2) {
-                    const float2 t = ok[u] ? *reinterpret_cast<const float2 *>(src) : make_float2(0.f, 0.f);
-                    b[u][k][0] = t.x; b[u][k][1 % VEC] = t.y;
-                } else {
-                    b[u][k][0] = ok[u] ? src[0] : 0.f;
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UU; ++u)
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k)
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) acc[k][q] = ok[u] ? fmaf(w[u], b[u][k][q], acc[k][q]) : acc[k][q];
-    }
-}
-
-// Rows up to SPMM_LONG non-zeros: one LPR-lane group per row, non-zeros in order.  Longer rows (the hubs of a
-// power-law graph: thousands of non-zeros, which one group would chew through long after the rest of the grid has
-// finished) are parked in LDS and then taken by the whole workgroup: group g accumulates non-zeros g, g + G, ... and
-// the partial sums are added in group order, so the result is deterministic.
-constexpr int SPMM_LONG = 96;
-
-template <int LPR, int VEC, int NBLK>
-__global__ void __launch_bounds__(256) k_spmm_csr(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                   const float *__restrict__ val, const float *__restrict__ B,
-                                                   float *__restrict__ C, int64_t n_rows, int n_feat, int64_t ldb,
-                                                   int64_t ldc, const float *__restrict__ bias, int relu, int blk, int64_t blk_c,
-                                                   const int64_t *__restrict__ rows, int64_t split, int64_t b_off2) {
-    // rows: nullptr, or the n_rows rows of the matrix to compute (output row k = row rows[k] of the product); output rows
-    // from `split` on take their operand b_off2 floats further into B (two row lists over two column blocks in one launch)
-    constexpr int ROWS_PER_BLOCK = 256 / LPR;
-    constexpr int G = ROWS_PER_BLOCK;        // lane groups per workgroup
-    constexpr int U = LPR <= 8 ? 8 : 4;      // narrow rows of B: more gathers in flight per group
-    __shared__ int long_rows[ROWS_PER_BLOCK];
-    __shared__ int n_long;
-    __shared__ float red[256 * VEC];
-    const int sub = threadIdx.x / LPR;       // which row of the block / which group
-    const int sl = threadIdx.x % LPR;        // lane inside the group
-    // group `sub` of workgroup b owns row sub * gridDim + b: consecutive (hub) rows land in different workgroups
-    const int64_t row = (int64_t)sub * gridDim.x + blockIdx.x;
-    if (threadIdx.x == 0) n_long = 0;
-    __syncthreads();
-    if (row < n_rows) {
-        const int64_t mrow = rows ? rows[row] : row;
-        const float *Bk = row >= split ? B + b_off2 : B;
-        const int64_t e0 = rowptr[mrow], e1 = rowptr[mrow + 1];
-        if (e1 - e0 > SPMM_LONG) {
-            if (sl == 0) long_rows[atomicAdd(&n_long, 1)] = sub;
-        } else {
-            for (int f0 = sl * VEC; f0 < n_feat; f0 += LPR * VEC) {
-                float acc[NBLK][VEC];
-#pragma unroll
-                for (int k = 0; k < NBLK; ++k)
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) acc[k][q] = 0.f;
-                spmm_accumulate<VEC, U, NBLK>(col, val, Bk, ldb, f0, e0, e1, 1, blk, acc);
-#pragma unroll
-                for (int k = 0; k < NBLK; ++k) {
-                    float *dst = C + row * ldc + f0 + k * blk_c;
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) {
-                        float r = acc[k][q];
-                        if (bias) r += bias[f0 + q];
-                        if (relu) r = r > 0.f ? r : 0.f;
-                        dst[q] = r;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int nl = n_long;  // uniform
-    for (int li = 0; li < nl; ++li) {
-        const int64_t lrow = (int64_t)long_rows[li] * gridDim.x + blockIdx.x;
-        const int64_t lmrow = rows ? rows[lrow] : lrow;
-        const float *Bk = lrow >= split ? B + b_off2 : B;
-        const int64_t e0 = rowptr[lmrow], e1 = rowptr[lmrow + 1];
-        for (int fb = 0; fb < n_feat; fb += LPR * VEC) {  // uniform trip count
-            const int f0 = fb + sl * VEC;
-            float acc[NBLK][VEC];
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k)
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) acc[k][q] = 0.f;
-            if (f0 < n_feat) spmm_accumulate<VEC, U, NBLK>(col, val, Bk, ldb, f0, e0 + sub, e1, G, blk, acc);
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) {
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) red[threadIdx.x * VEC + q] = acc[k][q];
-                __syncthreads();
-                if (sub == 0 && f0 < n_feat) {
-                    float *dst = C + lrow * ldc + f0 + k * blk_c;
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) {
-                        float r = 0.f;
-                        for (int g = 0; g < G; ++g) r += red[(g * LPR + sl) * VEC + q];
-                        if (bias) r += bias[f0 + q];
-                        if (relu) r = r > 0.f ? r : 0.f;
-                        dst[q] = r;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-    }
-}
-
-template <int LPR, int VEC>
-static void launch_spmm(const int64_t *rowptr, const int32_t *col, const float *val, const float *B, float *C,
-                        int64_t n_rows, int n_feat, int64_t ldb, int64_t ldc, const float *bias, int relu, int n_blocks,
-                        int64_t blk_c, hipStream_t st, const int64_t *rows, int64_t split, int64_t b_off2) {
-    constexpr int ROWS_PER_BLOCK = 256 / LPR;
-    const int64_t blocks = (n_rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    if (n_blocks == 2)
-        hipLaunchKernelGGL((k_spmm_csr<LPR, VEC, 2>), dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, val, B, C, n_rows,
-                           n_feat, ldb, ldc, bias, relu, n_feat, blk_c, rows, split, b_off2);
-    else
-        hipLaunchKernelGGL((k_spmm_csr<LPR, VEC, 1>), dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, val, B, C, n_rows,
-                           n_feat, ldb, ldc, bias, relu, 0, (int64_t)0, rows, split, b_off2);
-}
-
-}  // namespace dcr
-
 using namespace dcr;
-
-static int spmm_dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const float *B, float *C,
-                         int64_t n_rows, int64_t n_feat, int64_t n_blocks, int64_t ldb, int64_t ldc, const float *bias, int relu,
-                         void *hip_stream, int64_t blk_c = -1, const int64_t *rows = nullptr, int64_t split = INT64_MAX,
-                         int64_t b_off2 = 0) {
-    // blk_c: where the second block of the output starts relative to the first (floats); -1: next to it (n_feat)
-    if (!rowptr || !B || !C || n_rows < 0 || n_feat <= 0 || n_blocks < 1 || n_blocks > 2 || ldb < n_feat * n_blocks ||
-        ldc < (blk_c < 0 ? n_feat * n_blocks : n_feat))
-        DCR_FAIL(DCR_EINVAL, "bad SpMM arguments");
-    if (blk_c < 0) blk_c = n_feat;
-    if (n_rows == 0) return DCR_OK;
-    if (n_feat > INT32_MAX / 2) DCR_FAIL(DCR_EINVAL, "n_feat too large");
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int F = (int)n_feat;
-    // (the template is chosen by the width of ONE block: a block of a two-block call is accumulated exactly like a call of its own)
-    const bool v4 = (F % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && (((uintptr_t)B & 15) == 0);
-    // (rows from `split` on read B + b_off2: the 8-byte path needs that operand aligned too, and falls back to scalar loads
-    //  where it is not; the 16-byte path's second operand is dcr_spmm_csr_rows2_f32_dev's own check)
-    const bool v2 = (F % 2 == 0) && (ldb % 2 == 0) && (ldc % 2 == 0) && (((uintptr_t)B & 7) == 0) &&
-                    (split >= n_rows || b_off2 % 2 == 0);
-#define GO(L, V) launch_spmm<L, V>(rowptr, col, val, B, C, n_rows, F, ldb, ldc, bias, relu, (int)n_blocks, blk_c, st, rows, split, b_off2)
-    if (v4) {
-        const int lanes = F / 4;
-        if (lanes <= 4) GO(4, 4);
-        else if (lanes <= 8) GO(8, 4);
-        else if (lanes <= 16) GO(16, 4);
-        else if (lanes <= 32) GO(32, 4);
-        else GO(64, 4);
-    } else if (v2) {
-        const int lanes = F / 2;
-        if (lanes <= 4) GO(4, 2);
-        else if (lanes <= 8) GO(8, 2);
-        else if (lanes <= 16) GO(16, 2);
-        else if (lanes <= 32) GO(32, 2);
-        else GO(64, 2);
-    } else {
-        if (F <= 4) GO(4, 1);
-        else if (F <= 8) GO(8, 1);
-        else if (F <= 16) GO(16, 1);
-        else if (F <= 32) GO(32, 1);
-        else GO(64, 1);
-    }
-#undef GO
-    DCR_HIP(hipGetLastError());
-    return DCR_OK;
-}
-
-extern "C" int dcr_spmm_csr_f32_dev(const int64_t *rowptr, const int32_t *col, const float *val, const float *B,
-                                    float *C, int64_t n_rows, int64_t n_feat, int64_t ldb, int64_t ldc,
-                                    const float *bias, int relu, void *hip_stream) {
-    return spmm_dispatch(rowptr, col, val, B, C, n_rows, n_feat, 1, ldb, ldc, bias, relu, hip_stream);
-}
-
-extern "C" int dcr_spmm_csr_f32_pair_dev(const int64_t *rowptr, const int32_t *col, const float *val, const float *B,
-                                         float *C, int64_t n_rows, int64_t n_feat, int64_t ldb, int64_t ldc,
-                                         const float *bias, int relu, void *hip_stream) {
-    return spmm_dispatch(rowptr, col, val, B, C, n_rows, n_feat, 2, ldb, ldc, bias, relu, hip_stream);
-}
-
-extern "C" int dcr_spmm_csr_f32_pair_split_dev(const int64_t *rowptr, const int32_t *col, const float *val, const float *B,
-                                               float *C0, float *C1, int64_t n_rows, int64_t n_feat, int64_t ldb, int64_t ldc,
-                                               const float *bias, int relu, void *hip_stream) {
-    if (!C0 || !C1 || ((C1 - C0) % 4) != 0) DCR_FAIL(DCR_EINVAL, "bad SpMM arguments (the two outputs 16 bytes apart modulo 16)");
-    return spmm_dispatch(rowptr, col, val, B, C0, n_rows, n_feat, 2, ldb, ldc, bias, relu, hip_stream, (int64_t)(C1 - C0));
-}
-
-// Rows rows_dev[0..n_sel) of Â·B (+ bias) only, output row k = row rows_dev[k]: the last layer of a training epoch is read at
-// the training rows (loss) and the validation rows (accuracy) and nowhere else (experiment/training_loop.py:50-51,64-71 index
-// the model's output with the split masks).  Every computed row is accumulated exactly as dcr_spmm_csr_f32_dev does it.
-extern "C" int dcr_spmm_csr_rows_f32_dev(const int64_t *rowptr, const int32_t *col, const float *val, const int64_t *rows,
-                                         int64_t n_sel, const float *B, float *C, int64_t n_feat, int64_t ldb, int64_t ldc,
-                                         const float *bias, int relu, void *hip_stream) {
-    if (!rows && n_sel > 0) DCR_FAIL(DCR_EINVAL, "bad SpMM arguments (no row list)");
-    return spmm_dispatch(rowptr, col, val, B, C, n_sel, n_feat, 1, ldb, ldc, bias, relu, hip_stream, -1, rows);
-}
-
-// Two row lists over two column blocks of one operand in ONE launch: output rows [0, n_first) are rows rows_dev[k] of Â·B0,
-// rows [n_first, n_sel) those of Â·B1 with B1 = B0 + b_off2 floats (the training rows of Â·Z_train and the validation rows of
-// Â·Z_eval of an epoch, Z = [Z_train | Z_eval]).  Each row as dcr_spmm_csr_rows_f32_dev computes it; where B1 is only 4-byte
-// aligned and B0 would take 8-byte loads, BOTH lists are computed as that call computes B1's (scalar loads).
-extern "C" int dcr_spmm_csr_rows2_f32_dev(const int64_t *rowptr, const int32_t *col, const float *val, const int64_t *rows,
-                                          int64_t n_first, int64_t n_sel, const float *B, int64_t b_off2, float *C, int64_t n_feat,
-                                          int64_t ldb, int64_t ldc, const float *bias, int relu, void *hip_stream) {
-    if ((!rows && n_sel > 0) || n_first < 0 || n_first > n_sel || b_off2 < 0 || b_off2 + n_feat > ldb)
-        DCR_FAIL(DCR_EINVAL, "bad SpMM arguments (row lists)");
-    // (the 16-byte path needs both operands aligned: decided on B0, so B1 must keep its alignment)
-    if ((b_off2 % 4) != 0 && (n_feat % 4) == 0) DCR_FAIL(DCR_EINVAL, "bad SpMM arguments (second operand not 16 bytes apart)");
-    return spmm_dispatch(rowptr, col, val, B, C, n_sel, n_feat, 1, ldb, ldc, bias, relu, hip_stream, -1, rows, n_first, b_off2);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // ReLU + dropout between the GCN layers (models/gcn.py:38-42: x = act_fn(x); x = dropout(x)) as ONE pass over the

@@ -10,7 +10,7 @@ by the reference; call sites gcn.py:19,30,36): ``gcn_norm`` with self loops,
 [out, in]), aggregation at the target node, ``bias`` added after aggregation
 (state_dict key ``bias``).  The dense contraction X·Wᵀ runs on the matrix cores
 through the ROCm GEMM library; the sparse aggregation Â·(XWᵀ) + b is the
-hand-written HIP kernel ``dcr_spmm_csr_f32_dev`` (csrc/dcr_gcn.hip), wrapped in
+hand-written HIP kernel ``dcr_spmm_csr_f32_dev`` (csrc/dcr_spmm.hip), wrapped in
 an autograd Function whose backward is the same kernel on Âᵀ.
 """
 import ctypes
@@ -65,7 +65,7 @@ def _weighted_degree(source, target, w, n):
     """deg = scatter_add(w, target), float32, the same bits on every run.  On the GPU a scatter of float32 atomics adds in the
     order the threads arrive: weights that are not small integers then gave another Â, and other trained weights, from one
     run to the next.  There the weights are grouped by target (the CSR of Â's pattern) and each row is summed by the
-    aggregation kernel against a column of ones, which adds a row's entries in a fixed order (csrc/dcr_gcn.hip, k_spmm_csr).
+    aggregation kernel against a column of ones, which adds a row's entries in a fixed order (csrc/dcr_spmm.hip, k_spmm_csr).
     Unit weights give exact integer sums either way, the degrees of the published formula.  On the CPU, ``scatter_add_``
     adds in index order."""
     if _AGG_BACKEND == 'hip' and w.is_cuda:

@@ -9,7 +9,7 @@ y, the masks and of Â = D^-1/2 (A+I) D^-1/2 (all columns, renumbered rank-major
 
     Z_p = H_p · Wᵀ                      local GEMM (matrix cores)
     Z   = all_gather(Z_p)               the one exchange step of the layer      [backward: reduce_scatter]
-    out = Â_p · Z + b                   local HIP SpMM (csrc/dcr_gcn.hip)        [backward: Â_pᵀ · d_out]
+    out = Â_p · Z + b                   local HIP SpMM (csrc/dcr_spmm.hip)       [backward: Â_pᵀ · d_out]
 
 The first layer's input is the constant feature matrix, so (as in the single-GPU model) Â_p·X is computed once — one
 all-gather of X at set-up — and the layer is then a purely local GEMM: no exchange step at all for layer 1.

@@ -11,7 +11,7 @@ ordinary edge of its type, a relation with no edge into i contributes nothing.  
 shapes (``weight`` [R, in, out], ``root`` [in, out], ``bias`` [out]), so state dicts interchange.
 
 Evaluated transform-first: ONE GEMM gives Zall = X·[W_0 | … | W_{R-1} | W_root] and ONE sweep of a typed CSR forms the output
-(``dcr_spmm_csr_typed_f32_dev``, csrc/dcr_rgcn.hip); the backward pass forms the whole of dZall in one sweep of the CSR of the
+(``dcr_spmm_csr_typed_f32_dev``, csrc/dcr_spmm.hip); the backward pass forms the whole of dZall in one sweep of the CSR of the
 transposed pattern (``dcr_spmm_csr_typed_expand_f32_dev``).  The dense products go through the GEMM library.
 """
 from typing import List
@@ -23,7 +23,7 @@ from dcr import _lib
 from models import gcn as _gcn
 from models.gcn import _ptr, _stream, relu_dropout
 
-MAX_RELATIONS = 8   # (TSPMM_MAX_REL in csrc/dcr_rgcn.hip)
+MAX_RELATIONS = 8   # (SPMM_MAX_REL in csrc/dcr_spmm.hip)
 
 
 class TypedCSR:
@@ -159,7 +159,7 @@ class _TypedAggregate(torch.autograd.Function):
 def typed_aggregate(zall, bias, csr, self_block=True):
     """The R-GCN aggregation of Zall = [Z_0 | … | Z_{R-1} | Z_root] (``self_block=False``: no root block) over ``csr``:
     out_i = Z_root[i] + Σ_slots val·Z_rel[col] + bias.  On the 'hip' backend (``models.gcn.set_aggregate_backend``) the two
-    kernels of csrc/dcr_rgcn.hip, and a CPU tensor raises; 'torch' is the plain-torch path of the CPU tests, never chosen
+    kernels of csrc/dcr_spmm.hip, and a CPU tensor raises; 'torch' is the plain-torch path of the CPU tests, never chosen
     automatically."""
     return _TypedAggregate.apply(zall, bias, csr, bool(self_block))
 

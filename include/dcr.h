@@ -540,7 +540,7 @@ int dcr_host_cdf_from_exp(const double *e, int64_t n, double S, double *out_cdf,
  * elsewhere; the two must agree bit for bit (tests/test_host_cpu.py). */
 int dcr_host_cdf_from_exp_plain(const double *e, int64_t n, double S, double *out_cdf, double *out_total);
 
-/* ---- GCN aggregation (device pointers, caller's stream) --------------------
+/* ---- GCN aggregation (csrc/dcr_spmm.hip; device pointers, caller's stream) ---
  * Replaces the propagate/scatter step of torch_geometric GCNConv (third-party,
  * call site models/gcn.py:36): C[i,:] = (bias ? bias : 0) + sum_e val[e] * B[col[e],:]
  * over CSR row i, optionally followed by ReLU.  fp32, row-major; ldb/ldc in
@@ -578,7 +578,7 @@ int dcr_spmm_csr_rows2_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev
                                int64_t n_first, int64_t n_sel, const float *B_dev, int64_t b_off2, float *C_dev, int64_t n_feat,
                                int64_t ldb, int64_t ldc, const float *bias_dev, int relu, void *hip_stream);
 
-/* ---- R-GCN typed aggregation (device pointers, caller's stream) ------------
+/* ---- R-GCN typed aggregation (csrc/dcr_spmm.hip; device pointers, caller's stream)
  * The mean-per-relation layer of Schlichtkrull et al. eq. 2 with c_{i,r} = |N_r(i)| (torch_geometric's RGCNConv with
  * aggr='mean'; models/rgcn.py), evaluated transform-first: one GEMM forms Zall = X·[W_0 | ... | W_{R-1} | W_root], one
  * sweep of a typed CSR forms the output.  Typed CSR: rowptr int64, col int32, val float32 (1 / |N_r(i)|) and rel uint8,

@@ -1,9 +1,9 @@
-"""The shapes the typed SpMM kernel pair (csrc/dcr_rgcn.hip) is run at, and the dispatch that turns a shape into a kernel
+"""The shapes the typed SpMM kernel pair (csrc/dcr_spmm.hip) is run at, and the dispatch that turns a shape into a kernel
 instantiation, restated: plain Python, no torch, no GPU, so that tests/test_rgcn_cpu.py can say which of the 15 (LPR, VEC)
 instantiations tests/test_rgcn_gpu.py launches."""
 
 VECS = (4, 2, 1)
-LPRS = (4, 8, 16, 32, 64)                     # DCR_TYPED_PICK: the first LPR that holds a row's VEC-wide pieces, else 64
+LPRS = (4, 8, 16, 32, 64)                     # pick_lpr_vec: the first LPR that holds a row's VEC-wide pieces, else 64
 # The first nine: every VEC path, 260 > one group's stride of 64 lanes x 4.  Then one width per instantiation those never reach
 # (VEC 4 on 8 lanes; VEC 1 and VEC 2 on 8 to 64), and 130 / 65: a second trip of the f0 loop at VEC 2 / VEC 1 (64 lanes x VEC).
 N_FEATS = [1, 2, 3, 4, 6, 7, 64, 68, 260, 20, 13, 17, 10, 18, 34, 66, 130, 65]

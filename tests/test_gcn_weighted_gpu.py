@@ -1,7 +1,7 @@
 """Edge weights and self-loops already in the input, through every route Â takes on the GPU (the reference's loader always
 sets ``edge_attr`` and its model passes it on).  The check is the float64 restatement of PyG 2.0.3 ``gcn_norm`` in
 tests/gcn_fp64.py, built from the raw edge list: the aggregation entry points at widths that select every (LPR, VEC) template of
-``spmm_dispatch``, the model's logits and one training step's gradients on every first-layer and head route, the captured
+``spmm_dispatch`` (csrc/dcr_spmm.hip), the model's logits and one training step's gradients on every first-layer and head route, the captured
 epochs against the eager loop, and unit weights against no weights."""
 import ctypes
 import os

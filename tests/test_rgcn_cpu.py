@@ -185,7 +185,7 @@ def test_layer_caches_its_csr_per_graph_identity(torch_backend):
 
 def test_gpu_shapes_reach_every_typed_spmm_instantiation():
     """tests/test_rgcn_gpu.py launches all 15 (LPR, VEC) instantiations of both kernels, every added width and the third pad
-    is needed for that, and ``vec_lpr`` still is the dispatch csrc/dcr_rgcn.hip has."""
+    is needed for that, and ``vec_lpr`` still is the dispatch csrc/dcr_spmm.hip has."""
     import rgcn_shapes as S
     picked = {S.vec_lpr(f, *S.leading_dims(f, n_rel, self_block, pad)) for f in S.N_FEATS for pad in S.PADS for n_rel in (1, 2, 3, 8)
               for self_block in (0, 1)}
@@ -203,27 +203,29 @@ def test_gpu_shapes_reach_every_typed_spmm_instantiation():
         assert f in S.N_FEATS
     assert {0, 1} <= set(S.PADS)
     # the table itself, from the text of the source
-    src = open(os.path.join(PKG, 'csrc', 'dcr_rgcn.hip')).read()
-    m = re.search(r'#define DCR_TYPED_PICK\(GO, F, v4, v2\)(.*?)while \(0\)', src, flags=re.S)
-    assert m, 'DCR_TYPED_PICK not found'
-    m = re.search(r'if \(v4\) \{(.*?)\} else if \(v2\) \{(.*?)\} else \{(.*?)\}\s*\\\s*\}', m.group(1), flags=re.S)
-    assert m, 'DCR_TYPED_PICK: not the v4 / v2 / scalar branches'
-    for vec, body in zip((4, 2, 1), m.groups()):
-        if vec > 1:
-            assert re.search(r'const int lanes = \(F\) / %d;' % vec, body), vec
-        count = r'lanes' if vec > 1 else r'\(F\)'
-        steps = re.findall(r'if \(%s <= (\d+)\) GO\((\d+), (\d+)\);' % count, body)
-        assert [tuple(int(x) for x in s) for s in steps] == [(l, l, vec) for l in S.LPRS[:-1]], (vec, steps)
-        last = re.findall(r'else GO\((\d+), (\d+)\);', body)
-        assert [tuple(int(x) for x in s) for s in last] == [(S.LPRS[-1], vec)], (vec, last)
-        assert len(re.findall(r'GO\(', body)) == len(S.LPRS)
+    src = open(os.path.join(PKG, 'csrc', 'dcr_spmm.hip')).read()
+    m = re.search(r'static void pick_lpr_vec\(int F, VecOk v, Go &&go\) \{(.*?)\n\}\n', src, flags=re.S)
+    assert m, 'pick_lpr_vec not found'
+    table = m.group(1)
+    # VEC: the widest allowed, in this order; the count the LPR steps compare is the row's VEC-wide pieces
+    assert re.search(r'if \(v\.v4\) lpr\(Int<4>\{\}\);\s*else if \(v\.v2\) lpr\(Int<2>\{\}\);\s*else lpr\(Int<1>\{\}\);', table)
+    assert re.search(r'auto lpr = \[&\]\(auto vec\) \{\s*const int pieces = F / decltype\(vec\)::value;', table)
+    steps = re.findall(r'if \(pieces <= (\d+)\) go\(Int<(\d+)>\{\}, vec\);', table)
+    assert [tuple(int(x) for x in s) for s in steps] == [(l, l) for l in S.LPRS[:-1]], steps
+    assert re.findall(r'else go\(Int<(\d+)>\{\}, vec\);', table) == [str(S.LPRS[-1])]
+    assert len(re.findall(r'\bgo\(', table)) == len(S.LPRS)
     # what narrows VEC: the width, both leading dimensions and the pointers the entry point names
+    m = re.search(r'static VecOk vec_ok\(int F, int64_t ld_in, int64_t ld_out, std::initializer_list<const void \*> ptrs\) \{(.*?)\n\}\n', src,
+                  flags=re.S)
+    assert m, 'vec_ok not found'
+    assert 'bool all = F % vec == 0 && ld_in % vec == 0 && ld_out % vec == 0;' in m.group(1)
+    assert 'for (const void *p : ptrs) all = all && ((uintptr_t)p & (4 * vec - 1)) == 0;' in m.group(1)
+    assert 'return {ok(4), ok(2)};' in m.group(1)
     for name, lds, ptrs in (('dcr_spmm_csr_typed_f32_dev', ('ldb', 'ldc'), ('B',)), ('dcr_spmm_csr_typed_expand_f32_dev', ('ldg', 'ldc'), ('G', 'C'))):
         body = src[src.index('extern "C" int ' + name):]
-        for vec, mask in ((4, 15), (2, 7)):
-            want = r'const bool v%d = \(F %% %d == 0\)' % (vec, vec) + ''.join(r' && \(%s %% %d == 0\)' % (ld, vec) for ld in lds) + \
-                ''.join(r' && \(\(\(uintptr_t\)%s & %d\) == 0\)' % (p, mask) for p in ptrs) + ';'
-            assert re.search(want, body[:body.index('#undef GO')]), (name, vec)
+        body = body[:body.index('\n}\n')]
+        assert 'pick_lpr_vec(F, vec_ok(F, %s, %s, {%s}), [&]' % (lds + (', '.join(ptrs),)) in body, name
+        assert body.count('vec_ok(') == 1 and 'v2 =' not in body and 'v4 =' not in body, name
     assert S.vec_lpr(64, 256, 64) == (4, 16) and S.vec_lpr(64, 256, 64, residues=(8,)) == (2, 32) and S.vec_lpr(64, 256, 64, residues=(0, 4)) == (1, 64)
 
 
@@ -236,6 +238,6 @@ def test_call_surface():
         params = re.sub(r'/\*.*?\*/', '', m.group(1), flags=re.S)
         assert len(params.split(',')) == len(_lib.SIGNATURES[name][1]), name
     assert len(_lib.SIGNATURES['dcr_spmm_csr_typed_f32_dev'][1]) == 15 and len(_lib.SIGNATURES['dcr_spmm_csr_typed_expand_f32_dev'][1]) == 13
-    assert 'dcr_rgcn' in open(os.path.join(PKG, 'csrc', 'build.sh')).read().split()
+    assert 'dcr_spmm' in open(os.path.join(PKG, 'csrc', 'build.sh')).read().split()
     from models.rgcn import RGCN, RGCNConv, TypedCSR, rgcn_norm_csr, typed_aggregate
     assert all(callable(f) for f in (RGCN, RGCNConv, TypedCSR, rgcn_norm_csr, typed_aggregate))

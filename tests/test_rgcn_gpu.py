@@ -1,4 +1,4 @@
-"""The typed aggregation kernel pair (csrc/dcr_rgcn.hip) through the raw ABI, and the R-GCN layer on them (models/rgcn.py).
+"""The typed aggregation kernel pair (csrc/dcr_spmm.hip) through the raw ABI, and the R-GCN layer on them (models/rgcn.py).
 
 Exact cases: ``val`` dyadic and small integers in the operands, so every fp32 operation is exact and the result must equal a
 float64 numpy restatement bit for bit.  Random floats: the forward error bound of an fp32 ``fmaf`` sum against float64,
@@ -34,7 +34,7 @@ PATTERN = [(400, 'mixed'), (0, 'mixed'), (3, 'one'), (97, 'mixed'), (300, 'one')
 HUB_COLS = 136                                # the all-hub family: the next multiple of 8 above its largest n_rows (2 * 64 + 1)
 HUB_LENGTHS = (97, 130, 200, 98)
 RANDOM_FEATS = (3, 64, 260, 20, 13, 17, 10, 18, 34, 66)
-TSPMM_LONG = 96                              # (csrc/dcr_rgcn.hip) rows above it are parked and summed by the whole workgroup
+SPMM_LONG = 96                              # (SPMM_LONG of csrc/dcr_spmm.hip) rows above it are parked and summed by the whole workgroup
 
 
 @pytest.fixture(scope='module')
@@ -360,7 +360,7 @@ def parked_per_workgroup(rowptr, n_rows, G):
     """How many rows each workgroup parks: group ``sub`` of workgroup ``b`` owns row sub·grid + b."""
     grid = (n_rows + G - 1) // G
     lengths = np.diff(rowptr)
-    return [sum(1 for sub in range(G) if sub * grid + b < n_rows and lengths[sub * grid + b] > TSPMM_LONG) for b in range(grid)]
+    return [sum(1 for sub in range(G) if sub * grid + b < n_rows and lengths[sub * grid + b] > SPMM_LONG) for b in range(grid)]
 
 
 def test_every_row_a_hub_exact_values(lib):
@@ -409,7 +409,7 @@ def test_relation_above_n_rel_is_read_as_the_last(lib, n_feat):
     rows, cols, rels, vals = coo
     csr = typed_csr(*coo, FULL_ROWS)
     lengths = np.diff(csr[0])
-    assert set(csr[3].tolist()) == set(range(8)) and lengths.max() > TSPMM_LONG and 0 < lengths[lengths > 0].min() < 8
+    assert set(csr[3].tolist()) == set(range(8)) and lengths.max() > SPMM_LONG and 0 < lengths[lengths > 0].min() < 8
     csr_dev = tuple(dev(a) for a in csr)
     ld = 9 * n_feat + (-9 * n_feat) % 4                                          # (VEC 2 at 6, VEC 4 at 64, as an aligned call)
     for n_rel in (2, 3):
@@ -557,7 +557,7 @@ def hub_data():
     et = torch.from_numpy(rng.integers(0, 3, ei.shape[1]))
     csr = rgcn_norm_csr(ei, et, n, 3)
     deg_in, deg_out = (csr.rowptr[1:] - csr.rowptr[:-1]), (csr.rowptr_t[1:] - csr.rowptr_t[:-1])
-    assert int(deg_in[0]) > TSPMM_LONG and int(deg_out[0]) > TSPMM_LONG and int(deg_in[1]) == 0
+    assert int(deg_in[0]) > SPMM_LONG and int(deg_out[0]) > SPMM_LONG and int(deg_in[1]) == 0
     assert not torch.equal(csr.rowptr, csr.rowptr_t) and not torch.equal(csr.col, csr.col_t)
     assert set(csr.rel[:int(deg_in[0])].tolist()) == {0, 1, 2} and set(csr.rel_t[:int(deg_out[0])].tolist()) == {0, 1, 2}
     g = torch.Generator().manual_seed(6)

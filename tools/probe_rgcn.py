@@ -1,4 +1,4 @@
-"""Times the typed aggregation pair of csrc/dcr_rgcn.hip against what the package could do before it: one sweep of the typed CSR
+"""Times the typed aggregation pair of csrc/dcr_spmm.hip against what the package could do before it: one sweep of the typed CSR
 (the gather forward, the expand backward) against R calls of dcr_spmm_csr_f32_dev on per-relation CSRs, the adds that join them
 and the add (forward) or copy (backward) of the root term.
 
