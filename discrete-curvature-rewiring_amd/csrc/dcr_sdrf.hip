@@ -235,7 +235,8 @@ struct ImpBuf {
     int32_t *keys, *posx, *posy;  // hash table over N(x) ∪ N(y) minus {x,y}
     int32_t *c1, *c2;             // [dx], [dy]
     int32_t *clsx, *clsy;         // 0: only in own row (DX / DY), 1: in both rows (triangle), 2: the other endpoint
-    double *impb, *impc;          // class B (i == x) per b, class C (j == y) per a
+    int4 *descx, *descy;          // [dx+1], [dy]: {member, start of its row, its degree, its table slot (-1: an endpoint)} of row x
+                                  // (entry dx: x itself) and of row y, left by k_imp_insert
     int32_t *rowcount, *rowoff;   // [dx+1]
     uint32_t *adjbits;            // [dx+1][words]
     ImpStats *st;
@@ -261,6 +262,7 @@ __global__ void __launch_bounds__(256) k_imp_insert(RowView g, ImpBuf B, int x, 
         const bool isx = t < rx.y;
         const int p = isx ? t : t - rx.y;
         const int k = g.col[(isx ? rx.x : ry.x) + p];
+        const int2 rk = g.rowinfo[k];  // (in flight beside the probes: the descriptor the later kernels start from)
         if (isx) {
             B.c1[p] = 0;
             B.clsx[p] = k == y ? 2 : 0;
@@ -269,15 +271,19 @@ __global__ void __launch_bounds__(256) k_imp_insert(RowView g, ImpBuf B, int x, 
             B.clsy[p] = k == x ? 2 : 0;
             if (k == x) B.st->pos_x_in_y = p;
         }
-        if (k == (isx ? y : x)) continue;  // the endpoints themselves are never in the table
-        unsigned h = g_hash((unsigned)k, mask);
-        while (true) {
-            const unsigned old = atomicCAS((unsigned *)&B.keys[h], T_EMPTY, (unsigned)k);
-            if (old == T_EMPTY || old == (unsigned)k) break;
-            h = (h + 1) & mask;
+        int slot = -1;
+        if (k != (isx ? y : x)) {  // the endpoints themselves are never in the table
+            unsigned h = g_hash((unsigned)k, mask);
+            while (true) {
+                const unsigned old = atomicCAS((unsigned *)&B.keys[h], T_EMPTY, (unsigned)k);
+                if (old == T_EMPTY || old == (unsigned)k) break;
+                h = (h + 1) & mask;
+            }
+            if (isx) B.posx[h] = p;
+            else B.posy[h] = p;
+            slot = (int)h;  // (a triangle node: both rows' threads end their walk at the one slot that holds it)
         }
-        if (isx) B.posx[h] = p;
-        else B.posy[h] = p;
+        (isx ? B.descx : B.descy)[p] = make_int4(k, rk.x, rk.y, slot);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         B.st->x = x;
@@ -289,6 +295,7 @@ __global__ void __launch_bounds__(256) k_imp_insert(RowView g, ImpBuf B, int x, 
         B.st->deg_min_is_one = (rx.y < ry.y ? rx.y : ry.y) == 1;
         B.st->done_rows = 0;
         B.st->done_draw = 0;
+        B.descx[rx.y] = make_int4(x, rx.x, rx.y, -1);  // the candidate row of x itself
         // (pos_x_in_y: written above by the thread that meets x in row y; reset to -1 by the pipeline's last kernel)
     }
 }
@@ -418,126 +425,38 @@ __device__ inline void imp_close_stats(ImpBuf B, int curv_type, int *shi) {
     __syncthreads();
 }
 
-// K4: class B (i == x, j = y_nb[b] in DY) for workgroups [0,dy), class C (j == y, i = x_nb[a] in DX) for [dy,dy+dx).
-// (Round 4: a workgroup per element, its four waves sharing the row — a wave per element left the kernel waiting 22 us for
-//  the one wave that streams a hub's 1,400-entry row.)
-__global__ void __launch_bounds__(256) k_imp_bc(RowView g, ImpBuf B, int x, int y, unsigned mask, int curv_type) {
-    __shared__ int dec_sh, maxadj_sh;
-    const ImpStats st = *B.st;
-    const int lane = threadIdx.x & 63;
-    const int wv = blockIdx.x;
-    if (wv >= st.dx + st.dy) return;
-    const bool isB = wv < st.dy;
-    const int p = isB ? wv : wv - st.dy;
-    const int cls = isB ? B.clsy[p] : B.clsx[p];
-    double *out = isB ? B.impb : B.impc;
-    if (cls != 0) {
-        if (threadIdx.x == 0) out[p] = 0.0;
-        return;
-    }
-    if (curv_type != DCR_CURV_BFC) {
-        // 4 - d1 - d2 (+3T): one degree grows, one triangle appears (classical_curvatures.py:14-28)
-        const double d = curv_type == DCR_CURV_1D ? -1.0 : curv_type == DCR_CURV_AUGMENTED ? 2.0 : 1.0;
-        if (threadIdx.x == 0) out[p] = d;
-        return;
-    }
-    if (threadIdx.x == 0) {
-        dec_sh = 0;
-        maxadj_sh = 0;
-    }
-    __syncthreads();
-    const int2 rown = g.rowinfo[isB ? y : x];
-    const int node = g.col[rown.x + p];  // j for class B, i for class C
-    const int2 rn = g.rowinfo[node];
-    const int32_t *cnt_other = isB ? B.c1 : B.c2;  // counters of the side that loses edges
-    const int max_other = isB ? st.max1 : st.max2;
-    int n_dec0 = 0, n_maxadj = 0;
-    for (int base = 0; base < rn.y; base += 4 * 256) {
-        int w[4], h[4];
-        bool in[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int t = base + 256 * q + (int)threadIdx.x;
-            in[q] = t < rn.y;
-            w[q] = in[q] ? g.col[rn.x + t] : -1;
-        }
-        g_find4(B.keys, mask, w, in, h);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            bool dec0 = false, mxa = false;
-            if (h[q] >= 0) {
-                const int px = B.posx[h[q]], py = B.posy[h[q]];
-                const bool other_only = isB ? (px >= 0 && py < 0) : (py >= 0 && px < 0);
-                if (other_only) {
-                    const int c = cnt_other[isB ? px : py];
-                    dec0 = (c == 1);
-                    mxa = (c == max_other);
-                }
-            }
-            n_dec0 += __popcll(__ballot(dec0));
-            n_maxadj += __popcll(__ballot(mxa));
-        }
-    }
-    if (lane == 0) {  // (the per-wave totals are uniform over the wave: one lane adds them)
-        if (n_dec0) atomicAdd(&dec_sh, n_dec0);
-        if (n_maxadj) atomicAdd(&maxadj_sh, n_maxadj);
-    }
-    __syncthreads();
-    n_dec0 = dec_sh;
-    n_maxadj = maxadj_sh;
-    if (threadIdx.x != 0) return;
-    int s1, s2, m1, m2, d1, d2;
-    if (isB) {
-        const int cb = B.c2[p];
-        s1 = st.s1 - n_dec0;
-        m1 = (st.max1 > 0 && n_maxadj == st.cnt1) ? st.max1 - 1 : st.max1;
-        s2 = st.s2 - (cb > 0);
-        m2 = (cb == st.max2 && st.cnt2 == 1) ? st.sec2 : st.max2;
-        d1 = st.dx + 1;
-        d2 = st.dy;
-    } else {
-        const int ca = B.c1[p];
-        s2 = st.s2 - n_dec0;
-        m2 = (st.max2 > 0 && n_maxadj == st.cnt2) ? st.max2 - 1 : st.max2;
-        s1 = st.s1 - (ca > 0);
-        m1 = (ca == st.max1 && st.cnt1 == 1) ? st.sec1 : st.max1;
-        d1 = st.dx;
-        d2 = st.dy + 1;
-    }
-    const double after = bfc_value(d1, d2, st.T + 1, s1, s2, m1 > m2 ? m1 : m2);
-    out[p] = after - st.before;
-}
-
 // K2 (round 4: one launch for what were k_imp_count, k_imp_stats, k_imp_rows and k_imp_scan).  One workgroup per candidate row
 // a (i = x_nb[a]; a == dx: i = x) streams row i ONCE: every entry is looked up in the table; an entry that is in row y only is
 // a 4-cycle x - i - w - y (c1[a] grows, and c2 of the node it lands on: bfc_naive.py:26-29,36-37), an entry that is in
 // row y at all rules the pair (i, that neighbour) out (sdrf_no_cuda.py:35: has_edge) — a bit in the row's bitmap, as do i == j,
 // w == y and w == x.  The workgroup also settles the classes of its row and of a share of row y.  The LAST workgroup to
 // finish closes the stage: statistics of c1 / c2, triangles, base curvature, exclusive scan of the rows' candidate counts.
-__global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int x, int y, unsigned mask, int words, int curv_type,
-                                                         DevResult *res) {
+// The grid is dx + 1 workgroups and dy comes as an argument (the host sized the launch by both).  A workgroup starts from the
+// descriptor k_imp_insert left for its row — member, row extent, table slot — so the row's entries are the second link of its
+// chain of dependent reads, not the sixth (statistics block, rowinfo of x, col, probe walk, rowinfo of i came before them), and
+// its class is one read at a known slot, in flight beside them.
+__global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int x, int y, int dy, unsigned mask, int words,
+                                                         int curv_type, DevResult *res) {
     extern __shared__ uint32_t bits[];
     __shared__ int cnt_sh, c1_sh;
     __shared__ int shi[16 * 4];
     ImpStats *stp = B.st;
-    const int dx = stp->dx, dy = stp->dy;
-    const int pos_x_in_y = stp->pos_x_in_y;  // x is an endpoint, so it is not in the table
+    const int dx = (int)gridDim.x - 1;
     const int a = blockIdx.x;
-    const int2 rx = g.rowinfo[x], ry = g.rowinfo[y];
-    const int i = a < dx ? g.col[rx.x + a] : x;
+    const int4 d = B.descx[a];
+    const int pos_x_in_y = stp->pos_x_in_y;  // x is an endpoint, so it is not in the table
     for (int w = threadIdx.x; w < words; w += blockDim.x) bits[w] = 0u;
-    // class of row a: 2 = the other endpoint, 1 = also in row y (a triangle node), 0 = in row x only.  Every thread looks i up
-    // itself (one address: a broadcast) — behind one thread and a barrier the whole workgroup waited for two dependent reads.
+    // class of row a: 2 = the other endpoint, 1 = also in row y (a triangle node), 0 = in row x only.  Every thread reads the
+    // slot itself (one address: a broadcast) — behind one thread and a barrier the whole workgroup waited for it.
     int cls = 3, b_i = -1;  // b_i: position of i in row y + [y] (the pair (i, i) is ruled out: sdrf_no_cuda.py:35, i != j)
-    if (i == y) {
+    if (a == dx) {
+        b_i = pos_x_in_y;
+    } else if (d.w < 0) {  // i == y
         cls = 2;
         b_i = dy;
-    } else if (i == x) {
-        b_i = pos_x_in_y;
     } else {
-        const int h = g_find(B.keys, mask, i);
-        if (h >= 0) b_i = B.posy[h];
-        if (a < dx) cls = b_i >= 0 ? 1 : 0;
+        b_i = B.posy[d.w];  // (complete: every posy was written by the launch before)
+        cls = b_i >= 0 ? 1 : 0;
     }
     if (threadIdx.x == 0) {
         cnt_sh = 0;
@@ -548,7 +467,7 @@ __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int
     }
     __syncthreads();
     const bool counting = curv_type == DCR_CURV_BFC && cls == 0;
-    const int2 ri = g.rowinfo[i];
+    const int2 ri = make_int2(d.y, d.z);
     int c = 0;
     for (int base = 0; base < ri.y; base += 4 * 256) {  // four look-ups in flight per thread (a hub's row is 1,400 entries)
         int w[4], h[4];
@@ -578,12 +497,10 @@ __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int
     }
     if (threadIdx.x == 0 && b_i >= 0) atomicOr(&bits[b_i >> 5], 1u << (b_i & 31));  // i == j
     // classes of a share of row y (every position is settled by exactly one workgroup; nothing in this kernel reads them)
+    // (the slot of its member is in the row's descriptor: one posx read per position, no probe walk; -1: x itself, class 2)
     for (int b = a + (int)threadIdx.x * (int)gridDim.x; b < dy; b += (int)blockDim.x * (int)gridDim.x) {
-        const int k = g.col[ry.x + b];
-        if (k != x) {
-            const int h = g_find(B.keys, mask, k);
-            B.clsy[b] = (h >= 0 && B.posx[h] >= 0) ? 1 : 0;
-        }
+        const int h = B.descy[b].w;
+        if (h >= 0) B.clsy[b] = B.posx[h] >= 0 ? 1 : 0;
     }
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&c1_sh, c);
@@ -611,39 +528,81 @@ __global__ void __launch_bounds__(256) k_imp_rows_count(RowView g, ImpBuf B, int
     imp_close_stats(B, curv_type, shi);
     // exclusive scan of rowcount[0 .. rows): the candidates are emitted row by row (sdrf_no_cuda.py:32-37: outer loop over x_nb)
     const int rows = (int)gridDim.x;
-    __shared__ int wsum[4];
-    __shared__ int carry_sh;
-    if (threadIdx.x == 0) carry_sh = 0;
-    __syncthreads();
+    // 1,024 rows per step: a thread takes four consecutive rows (their loads in flight together), a wave scans its threads'
+    // totals, the waves' totals cross through LDS; the carry is a register every thread keeps, and the waves' totals alternate
+    // between two LDS sets, so a step has ONE barrier (256 rows a step, the carry through LDS: three).
+    __shared__ int wsum[2][4];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int base = 0; base < rows; base += 256) {
-        const int r = base + (int)threadIdx.x;
-        const int v = r < rows ? __hip_atomic_load(&B.rowcount[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        int incl = v;
+    int carry = 0;
+    for (int base = 0, par = 0; base < rows; base += 4 * 256, par ^= 1) {
+        const int r0 = base + 4 * (int)threadIdx.x;
+        int v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            v[q] = r0 + q < rows ? __hip_atomic_load(&B.rowcount[r0 + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        const int mine = v[0] + v[1] + v[2] + v[3];
+        int incl = mine;
         for (int off = 1; off < 64; off <<= 1) {
             const int t = __shfl_up(incl, off);
             if (lane >= off) incl += t;
         }
-        if (lane == 63) wsum[wid] = incl;
+        if (lane == 63) wsum[par][wid] = incl;
         __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wid; ++w) woff += wsum[w];
-        const int carry = carry_sh;
-        if (r < rows) B.rowoff[r] = carry + woff + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry_sh = carry + woff + incl;
-        __syncthreads();
+        int woff = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int s = wsum[par][w];
+            woff += w < wid ? s : 0;
+            all += s;
+        }
+        int o = carry + woff + incl - mine;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (r0 + q < rows) B.rowoff[r0 + q] = o;
+            o += v[q];
+        }
+        carry += all;
     }
-    if (threadIdx.x == 0) res->n_cand = carry_sh;
+    if (threadIdx.x == 0) res->n_cand = carry;
 }
 
-// K7: write the admitted candidates of row a, in j order, with their improvements.
-// (Round 4: the pipeline's last user of the hash table leaves it EMPTY for the next iteration — nothing here reads it, and the
-//  separate clearing kernel at the head of the pipeline is gone.)
-__global__ void __launch_bounds__(256) k_imp_emit(RowView g, ImpBuf B, int x, int y, int words, int curv_type,
+// the closing expressions of class B (i == x, j = y_nb[b] in DY joins row x) and class C (j == y, i = x_nb[a] in DX joins
+// row y): the side that gains the edge loses one member (own: its counter c_own), every counter of the other side adjacent to
+// it drops by one (n_dec0 of them stood at 1, n_maxadj of them at the maximum)
+__device__ inline double bfc_after_b(const ImpStats &st, int cb, int n_dec0, int n_maxadj) {
+    const int s1 = st.s1 - n_dec0;
+    const int m1 = (st.max1 > 0 && n_maxadj == st.cnt1) ? st.max1 - 1 : st.max1;
+    const int s2 = st.s2 - (cb > 0);
+    const int m2 = (cb == st.max2 && st.cnt2 == 1) ? st.sec2 : st.max2;
+    return bfc_value(st.dx + 1, st.dy, st.T + 1, s1, s2, m1 > m2 ? m1 : m2);
+}
+
+__device__ inline double bfc_after_c(const ImpStats &st, int ca, int n_dec0, int n_maxadj) {
+    const int s2 = st.s2 - n_dec0;
+    const int m2 = (st.max2 > 0 && n_maxadj == st.cnt2) ? st.max2 - 1 : st.max2;
+    const int s1 = st.s1 - (ca > 0);
+    const int m1 = (ca == st.max1 && st.cnt1 == 1) ? st.sec1 : st.max1;
+    return bfc_value(st.dx, st.dy + 1, st.T + 1, s1, s2, m1 > m2 ? m1 : m2);
+}
+
+// 4 - d1 - d2 (+3T): one degree grows, one triangle appears (classical_curvatures.py:14-28)
+__device__ inline double classical_bc(int curv_type) {
+    return curv_type == DCR_CURV_1D ? -1.0 : curv_type == DCR_CURV_AUGMENTED ? 2.0 : 1.0;
+}
+
+// K7: write the admitted candidates, row by row in j order, with their improvements.  Workgroups [0, dx): row a (i = x_nb[a]).
+// Workgroups [dx, dx + words): the row of x itself (i == x, class B), 32 positions b each.
+// Classes B and C were a launch of their own that streamed the row of every j in DY and every i in DX through the table again
+// (9.7 us and a launch boundary).  The admissibility bitmap already holds what they looked up: for i_a in DX and j_b in DY, bit
+// (a, b) is set exactly when i_a ~ j_b.  Class C of row a is therefore a count over the bits of its own bitmap row, which the
+// row's threads read anyway; class B of 32 positions is a count over one word column of the bitmap.  Same integers into the
+// same closing expression, no row is streamed, and the table is not read here:
+// (Round 4: the pipeline's last kernel leaves the hash table EMPTY for the next iteration; the separate clearing kernel at the
+//  head of the pipeline is gone.)
+__global__ void __launch_bounds__(256) k_imp_emit(ImpBuf B, int x, int y, int dx, int dy, int words, int curv_type,
                                                    double *out, int32_t *ci, int32_t *cj, int64_t ts) {
-    __shared__ int wsum[4];
-    __shared__ int carry_sh;
+    __shared__ int wsum[2][4];
+    __shared__ int dec_sh[32], mxa_sh[32];
     const ImpStats st = *B.st;
     const int a = blockIdx.x;
     for (int64_t i = (int64_t)a * 256 + threadIdx.x; i < ts; i += (int64_t)gridDim.x * 256) {
@@ -652,56 +611,113 @@ __global__ void __launch_bounds__(256) k_imp_emit(RowView g, ImpBuf B, int x, in
         B.posy[i] = -1;
     }
     if (a == 0 && threadIdx.x == 0) B.st->pos_x_in_y = -1;
-    if (B.rowcount[a] == 0) return;
-    const int2 rx = g.rowinfo[x], ry = g.rowinfo[y];
-    const int i = a < st.dx ? g.col[rx.x + a] : x;
-    const int cls_a = a < st.dx ? B.clsx[a] : 3;
-    const int c1a = (a < st.dx && cls_a == 0) ? B.c1[a] : 0;
-    const int gam = st.max1 > st.max2 ? st.max1 : st.max2;
-    const int nb = st.dy + 1;
-    const int64_t row_base = B.rowoff[a];
-    if (threadIdx.x == 0) carry_sh = 0;
-    __syncthreads();
-    // one thread per candidate position b (256 per round): its place in the output is the number of admitted positions
-    // before it (ballots inside the wave, wave totals through LDS).  (One thread per 32-bit bitmap word, as this kernel
-    // first did it, leaves 5 of 256 threads busy for a typical 150-neighbour endpoint, 32 closing expressions each.)
+    const int nb = dy + 1;
+    const bool bfc = curv_type == DCR_CURV_BFC;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (a >= dx) {  // (uniform) class B: positions [32 wc, 32 wc + 32) of the row of x itself
+        const int wc = a - dx, lo = wc * 32;
+        const uint32_t *rowx = B.adjbits + (size_t)dx * words;
+        const uint32_t live = (nb - lo >= 32) ? 0xFFFFFFFFu : ((1u << (nb - lo)) - 1u);
+        const uint32_t adm = ~rowx[wc] & live;  // admitted: j in DY (triangle nodes, x and y have their bits set)
+        if (adm == 0u) return;
+        if (threadIdx.x < 32) dec_sh[threadIdx.x] = mxa_sh[threadIdx.x] = 0;
+        // place in the output: the admitted positions of this row in the words before (all of their bits are live)
+        int before = 0;
+        for (int w = threadIdx.x; w < wc; w += 256) before += __popc(~rowx[w]);
+        for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+        if (lane == 0) wsum[0][wid] = before;
+        __syncthreads();
+        before = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
+        if (bfc) {
+            // the members of DX adjacent to j_b lose a 4-cycle: only those whose counter stands at 1 or at the maximum matter
+            for (int r = threadIdx.x; r < dx; r += 256) {
+                const int c = B.c1[r];
+                if (B.clsx[r] != 0 || (c != 1 && c != st.max1)) continue;
+                uint32_t m = B.adjbits[(size_t)r * words + wc] & adm;
+                while (m) {
+                    const int bit = __ffs(m) - 1;
+                    m &= m - 1u;
+                    if (c == 1) atomicAdd(&dec_sh[bit], 1);
+                    if (c == st.max1) atomicAdd(&mxa_sh[bit], 1);
+                }
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x < 32 && ((adm >> threadIdx.x) & 1u)) {
+            const int b = lo + (int)threadIdx.x;
+            const int64_t o = (int64_t)B.rowoff[dx] + before + __popc(adm & ((1u << threadIdx.x) - 1u));
+            const int j = b < dy ? B.descy[b].x : y;
+            out[o] = bfc ? bfc_after_b(st, B.c2[b], dec_sh[threadIdx.x], mxa_sh[threadIdx.x]) - st.before : classical_bc(curv_type);
+            ci[o] = x < j ? x : j;  // sorted((i, j)), sdrf_no_cuda.py:37
+            cj[o] = x < j ? j : x;
+        }
+        return;
+    }
+    if (B.rowcount[a] == 0) return;
+    const int i = B.descx[a].x;
+    const int cls_a = B.clsx[a];
+    const int c1a = cls_a == 0 ? B.c1[a] : 0;
+    const int gam = st.max1 > st.max2 ? st.max1 : st.max2;
+    const int64_t row_base = B.rowoff[a];
+    const bool general = bfc && cls_a == 0;  // (a row of DX: its pairs with DY and with y change the ingredients)
+    // one thread per candidate position b (256 per round): its place in the output is the number of admitted positions
+    // before it (ballots inside the wave, wave totals through LDS, alternating between two sets: one barrier a round).  (One
+    // thread per 32-bit bitmap word, as this kernel first did it, leaves 5 of 256 threads busy for a typical 150-neighbour
+    // endpoint, 32 closing expressions each.)
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (int bbase = 0; bbase < nb; bbase += 256) {
+    int carry = 0, n_dec0 = 0, n_maxadj = 0;  // class C: the members of DY adjacent to i, counted as the rounds pass them
+    int64_t o_y = -1;                          // where the pair (i, y) goes (the thread of b == dy, in the last round)
+    for (int bbase = 0, par = 0; bbase < nb; bbase += 256, par ^= 1) {
         const int b = bbase + threadIdx.x;
         bool ok = false;
         if (b < nb) ok = ((B.adjbits[(size_t)a * words + (b >> 5)] >> (b & 31)) & 1u) == 0u;
+        int clsyb = 3, c2b = 0;
+        if (general && b < dy) {
+            clsyb = B.clsy[b];
+            c2b = B.c2[b];
+        }
+        const bool adj = general && b < dy && !ok && clsyb == 0;  // j_b in DY, i ~ j_b
+        n_dec0 += __popcll(__ballot(adj && c2b == 1));
+        n_maxadj += __popcll(__ballot(adj && c2b == st.max2));
         const unsigned long long m = __ballot(ok);
-        if (lane == 0) wsum[wid] = __popcll(m);
+        if (lane == 0) wsum[par][wid] = __popcll(m);
         __syncthreads();
-        int woff = 0;
-        for (int q = 0; q < wid; ++q) woff += wsum[q];
-        const int carry = carry_sh;
+        int woff = 0, all = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int s = wsum[par][q];
+            woff += q < wid ? s : 0;
+            all += s;
+        }
         if (ok) {
             const int64_t o = row_base + carry + woff + __popcll(m & lt);
-            const int j = b < st.dy ? g.col[ry.x + b] : y;
-            double val;
-            if (a == st.dx) {
-                val = B.impb[b];  // i == x: admitted only for j in DY
-            } else if (b == st.dy) {
-                val = B.impc[a];  // j == y: admitted only for i in DX
-            } else if (curv_type == DCR_CURV_BFC && cls_a == 0 && B.clsy[b] == 0) {
-                const int c2b = B.c2[b];
+            const int j = b < dy ? B.descy[b].x : y;
+            if (b == dy) {
+                o_y = o;  // j == y: admitted only for i in DX; its value needs the whole row's counts (below)
+            } else if (general && clsyb == 0) {
                 const int mm = (c1a + 1 > c2b + 1 ? c1a + 1 : c2b + 1);
                 const double after = bfc_value(st.dx, st.dy, st.T, st.s1 + (c1a == 0), st.s2 + (c2b == 0),
                                                mm > gam ? mm : gam);
-                val = after - st.before;
+                out[o] = after - st.before;
             } else {
-                val = 0.0;
+                out[o] = 0.0;
             }
-            out[o] = val;
             ci[o] = i < j ? i : j;  // sorted((i, j)), sdrf_no_cuda.py:37
             cj[o] = i < j ? j : i;
         }
-        __syncthreads();
-        if (threadIdx.x == 0) carry_sh = carry + wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
+        carry += all;
     }
+    // class C: the per-wave counts (uniform over a wave) summed over the workgroup, for the one thread that holds (i, y)
+    __syncthreads();
+    if (threadIdx.x == 0) dec_sh[0] = mxa_sh[0] = 0;
+    __syncthreads();
+    if (lane == 0 && general) {
+        if (n_dec0) atomicAdd(&dec_sh[0], n_dec0);
+        if (n_maxadj) atomicAdd(&mxa_sh[0], n_maxadj);
+    }
+    __syncthreads();
+    if (o_y >= 0)
+        out[o_y] = cls_a != 0 ? 0.0 : bfc ? bfc_after_c(st, c1a, dec_sh[0], mxa_sh[0]) - st.before : classical_bc(curv_type);
 }
 
 // the candidate drawn on the host, by index: (k, l) never leaves the device (dcr_sdrf_tail_at)
@@ -864,7 +880,7 @@ __global__ void __launch_bounds__(256) k_draw_partial(const double *__restrict__
 // grown on demand.  Nothing outside this file looks inside.
 struct SdrfScratch {
     ImpBuf imp{};                 // the improvement kernels' view: table {keys, posx, posy}[table_cap]; the row arrays c1, c2, clsx,
-    int64_t table_cap = 0;        // clsy, impb, impc, rowcount, rowoff [rows_cap]; adjbits [bits_cap]; st: one ImpStats
+    int64_t table_cap = 0;        // clsy, descx, descy, rowcount, rowoff [rows_cap]; adjbits [bits_cap]; st: one ImpStats
     int64_t rows_cap = 0, bits_cap = 0;
     bool table_dirty = true;      // the table is not all-empty (fresh allocation, or a pipeline that did not reach its last kernel)
     double *out = nullptr;        // compacted improvements and their candidate pairs [out_cap]
@@ -933,7 +949,7 @@ void sdrf_scratch_destroy(dcr_graph *g) {
     SdrfScratch *S = g->sdrf;
     if (!S) return;
     ImpBuf &B = S->imp;
-    dev_release(&B.keys, &B.posx, &B.posy, &B.c1, &B.c2, &B.clsx, &B.clsy, &B.impb, &B.impc, &B.rowcount, &B.rowoff, &B.adjbits, &B.st,
+    dev_release(&B.keys, &B.posx, &B.posy, &B.c1, &B.c2, &B.clsx, &B.clsy, &B.descx, &B.descy, &B.rowcount, &B.rowoff, &B.adjbits, &B.st,
                 &S->out, &S->ci, &S->cj, &S->red_scratch, &S->draw_bsum);
     if (S->out_h) (void)hipHostFree(S->out_h);
     if (S->ci_h) (void)hipHostFree(S->ci_h);
@@ -1038,15 +1054,15 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
     if (ts > S.table_cap) S.table_dirty = true;
     DCR_TRY(regrow_group(&S.table_cap, ts, ts, &B.keys, &B.posx, &B.posy));
     const int64_t rows_need = (int64_t)(dx > dy ? dx : dy) + 2;
-    DCR_TRY(regrow_group(&S.rows_cap, rows_need, 2 * rows_need + 64, &B.c1, &B.c2, &B.rowcount, &B.rowoff, &B.clsx, &B.clsy, &B.impb,
-                         &B.impc));
+    DCR_TRY(regrow_group(&S.rows_cap, rows_need, 2 * rows_need + 64, &B.c1, &B.c2, &B.rowcount, &B.rowoff, &B.clsx, &B.clsy, &B.descx,
+                         &B.descy));
     if ((int64_t)rows * words > S.bits_cap) DCR_TRY(dev_regrow(&B.adjbits, &S.bits_cap, 2 * (int64_t)rows * words));
     DCR_TRY(regrow_group(&S.out_cap, upper, 2 * upper + 1024, &S.out, &S.ci, &S.cj));
     RowView vw{g->rowinfo, g->col, g->slot_row};
 
-    // Five launches: insert both rows | per candidate row: classes, 4-cycle counters, admissibility bitmap, and the stage's
-    // closing statistics + scan by its last workgroup | classes B and C | emit (and leave the table empty) | the draw (its
-    // caller).  The table is only cleared here when the previous pipeline did not leave it empty.
+    // Four launches: insert both rows and leave a descriptor per member | per candidate row: classes, 4-cycle counters,
+    // admissibility bitmap, and the stage's closing statistics + scan by its last workgroup | emit, classes B and C from the
+    // bitmap (and leave the table empty) | the draw (its caller).  The table is only cleared here when the previous pipeline did not leave it empty.
     if (S.table_dirty) {
         const unsigned blocks = (unsigned)((S.table_cap + 255) / 256 > 1024 ? 1024 : (S.table_cap + 255) / 256);
         hipLaunchKernelGGL(k_imp_clear, dim3(blocks ? blocks : 1), dim3(256), 0, g->stream, B, S.table_cap);
@@ -1056,11 +1072,9 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
     const Ext *amax_parts = amax_from_parts ? (const Ext *)g->ext_part + EXT_PART_BLOCKS : nullptr;
     hipLaunchKernelGGL(k_imp_insert, dim3(gi + (amax_parts ? 1 : 0)), dim3(256), 0, g->stream, vw, B, x, y, mask, amax_parts,
                        amax_parts ? g->ext_part_n : 0, g->dres);
-    hipLaunchKernelGGL(k_imp_rows_count, dim3(rows), dim3(256), (size_t)words * 4, g->stream, vw, B, x, y, mask, words, curv_type,
-                       g->dres);
-    if (dx + dy > 0)
-        hipLaunchKernelGGL(k_imp_bc, dim3(dx + dy), dim3(256), 0, g->stream, vw, B, x, y, mask, curv_type);
-    hipLaunchKernelGGL(k_imp_emit, dim3(rows), dim3(256), 0, g->stream, vw, B, x, y, words, curv_type, S.out, S.ci, S.cj, ts);
+    hipLaunchKernelGGL(k_imp_rows_count, dim3(rows), dim3(256), (size_t)words * 4, g->stream, vw, B, x, y, dy, mask, words,
+                       curv_type, g->dres);
+    hipLaunchKernelGGL(k_imp_emit, dim3(dx + words), dim3(256), 0, g->stream, B, x, y, dx, dy, words, curv_type, S.out, S.ci, S.cj, ts);
     S.table_dirty = false;
     DCR_HIP(hipGetLastError());
     *upper_out = upper;
