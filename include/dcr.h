@@ -609,6 +609,41 @@ int dcr_spmm_csr_typed_expand_f32_dev(const int64_t *rowptr_dev, const int32_t *
                                       const uint8_t *rel_dev, const float *G_dev, float *C_dev, int64_t n_rows, int64_t n_feat,
                                       int64_t n_rel, int64_t ldg, int64_t ldc, int self_block, void *hip_stream);
 
+/* ---- GAT attention aggregation (csrc/dcr_gat.hip; device pointers, caller's stream)
+ * The layer of Velickovic et al. as torch_geometric's GATConv evaluates it (models/gat.py), H heads of C channels, flow
+ * source -> target, on Z = X*W [n, H*C] and the scores s_src[j,h] = <Z[j,h,:], att_src[h,:]>, s_dst likewise:
+ *   pre = s_src[j,h] + s_dst[i,h]     e = pre > 0 ? pre : negative_slope * pre
+ *   w = expf(e - m[i,h])              m = max of e, den = sum of w over the slots of row i
+ *   O[i,h,:] = (sum_slots w * Z[col,h,:]) / den[i,h]
+ * CSR by target: rowptr int64 [n + 1], col int32 (sources; every value in [0, n)).  A duplicated column is two slots; a row
+ * without slots gives O = 0 and the record (0, 1).  fp32, row-major, leading dimensions in elements: ldz for Z and dZ
+ * (>= H*C), lds for s_src, s_dst, dS_src and dS_dst (>= H), ldo for O and dO (>= H*C).  rec [n*H*2] receives (m, den) per
+ * (row, head) for the backward pass.
+ * Supported: 1 <= H <= 64; 1 <= C <= 64 always, up to 128 / 256 where C, ldz, ldo and the pointers of Z, O (expand: also dO,
+ * dZ) allow 8- / 16-byte accesses (C / VEC <= 64); n * H <= 2^31 - 2.  Outside that, a null pointer, n < 0, H or C < 1, a
+ * leading dimension below its width: DCR_EINVAL without a launch.  n = 0 is DCR_OK.
+ * Order: den and every element of the slot sum one operation per slot (fmaf for the products) in CSR order; a (row, head)
+ * above 96 slots as G strided partial sums added in group order, G = 256 / LPH, LPH the first of 4, 8, .., 64 lanes that
+ * holds C / VEC.  One true division per output element.  No floating-point atomics: the same bits on every call.
+ * Asynchronous on hip_stream. */
+int dcr_gat_gather_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev, const float *Z_dev, const float *s_src_dev,
+                           const float *s_dst_dev, float *O_dev, float *rec_dev, int64_t n, int64_t H, int64_t C, int64_t ldz,
+                           int64_t lds, int64_t ldo, double negative_slope, void *hip_stream);
+/* The backward pass in three launches.  With D[i,h] = <dO[i,h,:], O[i,h,:]> and alpha = expf(e - m) / den recomputed from
+ * the scores and rec with the forward's operations:
+ *   g_ij,h      = alpha * (<dO[i,h,:], Z[j,h,:]> - D[i,h]) * (pre > 0 ? 1 : negative_slope)
+ *   dZ[j,h,:]   = sum_i alpha * dO[i,h,:]      dS_src[j,h] = sum_i g_ij,h      dS_dst[i,h] = sum_j g_ij,h
+ * rowptr_dev is the target CSR's; rowptr_t / col_t (targets, in [0, n)) the CSR of the transposed pattern and slot_t
+ * (int64) the position of each of its slots in the target CSR (a permutation of [0, E)).  O and rec are the gather's
+ * outputs for the same operands.  work_rec [n*H*4] (16-byte aligned, else DCR_EINVAL) and work_g [E*H] (at least one
+ * element) are overwritten.  Every element of dZ's H*C columns and of dS_src's and dS_dst's H columns is written: no
+ * memset is needed.  Sums over slots in slot order of the CSR each runs on, long rows as above. */
+int dcr_gat_expand_f32_dev(const int64_t *rowptr_dev, const int64_t *rowptr_t_dev, const int32_t *col_t_dev,
+                           const int64_t *slot_t_dev, const float *Z_dev, const float *s_src_dev, const float *s_dst_dev,
+                           const float *O_dev, const float *dO_dev, const float *rec_dev, float *dZ_dev, float *dS_src_dev,
+                           float *dS_dst_dev, float *work_rec_dev, float *work_g_dev, int64_t n, int64_t H, int64_t C,
+                           int64_t ldz, int64_t lds, int64_t ldo, double negative_slope, void *hip_stream);
+
 /* ---- GCN weight gradient on the matrix cores (device pointers, caller's stream)
  * C[M x N] = A^T * B with A [K x M] and B [K x N] row-major fp32 (lda/ldb/ldc in
  * elements), K = number of nodes: the backward of GCNConv's bias-free Linear,
