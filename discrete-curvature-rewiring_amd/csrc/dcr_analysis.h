@@ -2,8 +2,8 @@
 // dcr_resistance_sketch.hip, dcr_diffusion.hip, dcr_fosr.hip, dcr_hops.hip, dcr_betweenness.hip) and the
 // curvature pass, SDRF and the GCN do not need: the deterministic reductions, the row plan and the row walker, the Cheeger ratio,
 // the analysis buffers of a graph, and the batched column CG that the resistance and diffusion solves share.  A new analysis
-// feature adds its buffers (one DevBuf line each in AnalysisState) and declarations here; dcr_internal.h and dcr_graph.hip stay
-// as they are.
+// feature adds its buffers (one line each in AnalysisState, of the owning DevBuf type of dcr_internal.h) and declarations here;
+// dcr_internal.h and dcr_graph.hip stay as they are.
 #pragma once
 #include "dcr_internal.h"
 
@@ -140,34 +140,6 @@ __device__ __forceinline__ void walk_rows(const RowPlan &plan, const int2 *__res
 }
 
 // ---- the analysis buffers of a graph, grown on demand; dcr_graph::analysis, created on first use (analysis_of) ----------------------
-// A device array that owns its memory.  It is never copied: a copy handed to a kernel launch or a helper would free the memory at
-// the end of the call, with the kernel still queued.  Kernels and helpers take the raw pointer p, which holds until the next grow().
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    int64_t cap = 0;  // elements
-
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { free(); }
-
-    void free() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // room for `need` elements: what is there when it is enough, else a new array of need + need / 4 + 64; the contents are lost
-    int grow(int64_t need) {
-        if (need <= cap) return DCR_OK;
-        free();
-        const int64_t nc = need + need / 4 + 64;
-        DCR_TRY(dev_alloc(&p, nc));
-        cap = nc;
-        return DCR_OK;
-    }
-};
-
 struct AnalysisState {
     DevBuf<int32_t> rows;         // [n] rows by degree class (build_row_plan)
 
@@ -511,7 +483,7 @@ int col_cg_solve(dcr_graph *g, const RowPlan &plan, const ColLayout &L, int ng, 
     const int64_t n = g->n;
     hipLaunchKernelGGL(k_col_start<P>, grid_el, dim3(256), 0, g->stream, prob, L.s, n, L.z, L.p, L.r, L.x, L.gstride);
     for (int64_t step = 0; step < max_steps; ++step) {
-        hipLaunchKernelGGL((k_col_matvec<P, 0>), grid_mv, dim3(256), 0, g->stream, prob, plan, g->rowinfo, g->col, L.p, L.z, L.s, L.q, L.part,
+        hipLaunchKernelGGL((k_col_matvec<P, 0>), grid_mv, dim3(256), 0, g->stream, prob, plan, g->rowinfo.p, g->col.p, L.p, L.z, L.s, L.q, L.part,
                            L.gstride, L.pstride);
         hipLaunchKernelGGL(k_col_update<typename P::Ctl>, grid_el, dim3(256), 0, g->stream, n, prob.ctl, L.p, L.q, L.x, L.r, L.part, L.gstride,
                            L.pstride);
@@ -525,7 +497,7 @@ int col_cg_solve(dcr_graph *g, const RowPlan &plan, const ColLayout &L, int ng, 
         if (active == 0) break;
     }
     hipLaunchKernelGGL(k_col_scale<P>, grid_el, dim3(256), 0, g->stream, n, L.s, L.x, L.z, L.gstride);
-    hipLaunchKernelGGL((k_col_matvec<P, 1>), grid_mv, dim3(256), 0, g->stream, prob, plan, g->rowinfo, g->col, L.x, L.z, L.s, L.q, L.part,
+    hipLaunchKernelGGL((k_col_matvec<P, 1>), grid_mv, dim3(256), 0, g->stream, prob, plan, g->rowinfo.p, g->col.p, L.x, L.z, L.s, L.q, L.part,
                        L.gstride, L.pstride);
     DCR_HIP(hipGetLastError());
     return DCR_OK;

@@ -59,7 +59,7 @@ int graph_components(dcr_graph *g, std::vector<int32_t> &labels) {
     for (int sweep = 0; g->cap_total > 0; ++sweep) {
         if (sweep > 100000) DCR_FAIL(DCR_ESTATE, "connected components did not settle");
         DCR_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(int32_t), g->stream));
-        hipLaunchKernelGGL(k_cc_hook, dim3(blocks_of(g->cap_total)), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
+        hipLaunchKernelGGL(k_cc_hook, dim3(blocks_of(g->cap_total)), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, g->slot_row.p,
                            g->cap_total, label, flag);
         hipLaunchKernelGGL(k_cc_compress, dim3(blocks_of(n)), dim3(256), 0, g->stream, label, n);
         DCR_HIP(hipGetLastError());
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(256) k_inv_sqrt_degree(const int2 *__restrict_
 }
 
 void inv_sqrt_degree(dcr_graph *g, double *s) {
-    hipLaunchKernelGGL(k_inv_sqrt_degree, dim3(blocks_of(g->n)), dim3(256), 0, g->stream, g->rowinfo, s, g->n);
+    hipLaunchKernelGGL(k_inv_sqrt_degree, dim3(blocks_of(g->n)), dim3(256), 0, g->stream, g->rowinfo.p, s, g->n);
 }
 
 // ---- the row plan ----------------------------------------------------------------------------------------------------------------
@@ -109,7 +109,7 @@ int build_row_plan(dcr_graph *g, RowPlan *plan, std::vector<int2> *info_out) {
     std::vector<int2> own;
     std::vector<int2> &info = info_out ? *info_out : own;
     info.resize((size_t)n);
-    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo.p, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     std::vector<int32_t> rows;
     classify_rows(info, rows, plan);

@@ -224,7 +224,7 @@ struct BtwRun {
         unsigned long long before = 0;
         for (int64_t level = 1;; ++level) {
             if (level > n) DCR_FAIL(DCR_ESTATE, "betweenness: more levels than nodes");
-            hipLaunchKernelGGL(k_btw_forward, grid, dim3(256), 0, st, plan, g->rowinfo, g->col, (int32_t)level, B, dist, sigma, ctl);
+            hipLaunchKernelGGL(k_btw_forward, grid, dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, (int32_t)level, B, dist, sigma, ctl);
             DCR_HIP(hipGetLastError());
             DCR_HIP(hipMemcpyAsync(&h, ctl, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             DCR_HIP(hipStreamSynchronize(st));
@@ -237,10 +237,10 @@ struct BtwRun {
             DCR_FAIL(DCR_ESTATE, "betweenness: the number of shortest paths of a pair exceeds the float64 range");
         for (int64_t level = last - 1; level >= 0; --level) {
             if (slot_acc)
-                hipLaunchKernelGGL(k_btw_backward<true>, grid, dim3(256), 0, st, plan, g->rowinfo, g->col, (int32_t)level, dist, sigma, delta,
+                hipLaunchKernelGGL(k_btw_backward<true>, grid, dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, (int32_t)level, dist, sigma, delta,
                                    slot_acc);
             else
-                hipLaunchKernelGGL(k_btw_backward<false>, grid, dim3(256), 0, st, plan, g->rowinfo, g->col, (int32_t)level, dist, sigma, delta,
+                hipLaunchKernelGGL(k_btw_backward<false>, grid, dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, (int32_t)level, dist, sigma, delta,
                                    slot_acc);
         }
         hipLaunchKernelGGL(k_btw_accumulate, dim3(std::min(blocks_of(n * BTW_CP), (unsigned)BTW_ACC_BLOCKS)), dim3(256), 0, st, n, ctl, delta,
@@ -259,7 +259,7 @@ struct BtwRun {
         std::vector<int32_t> col((size_t)cap);
         std::vector<double> acc((size_t)cap);
         if (cap > 0) {
-            DCR_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost, st));
+            DCR_HIP(hipMemcpyAsync(col.data(), g->col.p, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost, st));
             DCR_HIP(hipMemcpyAsync(acc.data(), slot_acc, sizeof(double) * (size_t)cap, hipMemcpyDeviceToHost, st));
         }
         DCR_HIP(hipStreamSynchronize(st));

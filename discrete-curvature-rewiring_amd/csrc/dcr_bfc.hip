@@ -650,13 +650,9 @@ __global__ void k_clear_counts(DevResult *res, int keep_guard) {
 }
 
 static int ensure_work(dcr_graph *g) {
-    if (g->work_cap >= g->cap_total / 2 + 64 && g->work[0]) return DCR_OK;
+    if (g->work_cap >= g->cap_total / 2 + 64 && g->work[0].p) return DCR_OK;
     int64_t cap = g->cap_total / 2 + 64;  // at most one undirected edge per two directed slots
-    for (int b = 0; b < NBINS; ++b) {
-        if (g->work[b]) (void)hipFree(g->work[b]);
-        g->work[b] = nullptr;
-        DCR_TRY(dev_alloc(&g->work[b], cap));
-    }
+    for (int b = 0; b < NBINS; ++b) DCR_TRY(g->work[b].alloc(cap));
     g->work_cap = cap;
     return DCR_OK;
 }
@@ -679,21 +675,21 @@ static void launch_bin(dcr_graph *g, const View &vw, int curv_type, double *byte
     if (per_cu < 1) per_cu = 1;
     const int grid = num_cu * per_cu;
     hipLaunchKernelGGL((k_edge_pass<SLOTS, TEAM, MODE, bin_desc_cap(B), bin_chunk(B)>), dim3(grid), dim3(TEAM), 0, st,
-                       vw, g->work[B], &g->dres->work_count[B], &g->dres->work_next[B], curv_type, g->curv,
+                       vw, g->work[B].p, &g->dres.p->work_count[B], &g->dres.p->work_next[B], curv_type, g->curv.p,
                        bytes_total);
 }
 
 template <int MODE>
 static int run_pass(dcr_graph *g, int curv_type, double *bytes_total, bool incremental = false, bool nc_rest = false) {
     DCR_TRY(ensure_work(g));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, incremental ? g->dirty.p : nullptr,
             (int32_t)g->n, nc_rest ? 1 : 0};
     WorkLists wl;
-    for (int b = 0; b < NBINS; ++b) wl.w[b] = g->work[b];
+    for (int b = 0; b < NBINS; ++b) wl.w[b] = g->work[b].p;
     // can an edge exceed the largest table at all?  (max_deg_bound is an upper bound of every degree)
     const bool giant_possible = MODE != MODE_BYTES && 2 * (int64_t)g->max_deg_bound + 2 > bin_max_keys(NBINS - 1);
-    if (giant_possible && !g->giant_list) DCR_TRY(dev_alloc(&g->giant_list, (int64_t)GIANT_LIST_CAP * 5));
-    wl.giant = giant_possible ? g->giant_list : nullptr;
+    if (giant_possible && !g->giant_list.p) DCR_TRY(g->giant_list.alloc((int64_t)GIANT_LIST_CAP * 5));
+    wl.giant = giant_possible ? g->giant_list.p : nullptr;
     if (g->num_cu <= 0) {
         g->num_cu = 256;
         hipDeviceProp_t prop;
@@ -701,11 +697,11 @@ static int run_pass(dcr_graph *g, int curv_type, double *bytes_total, bool incre
             g->num_cu = prop.multiProcessorCount;
     }
     const int num_cu = g->num_cu;
-    hipLaunchKernelGGL(k_clear_counts, dim3(1), dim3(64), 0, g->stream, g->dres, nc_rest ? 1 : 0);
+    hipLaunchKernelGGL(k_clear_counts, dim3(1), dim3(64), 0, g->stream, g->dres.p, nc_rest ? 1 : 0);
     int64_t blocks = (g->cap_total + CLASSIFY_CHUNK - 1) / CLASSIFY_CHUNK;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_classify, dim3((unsigned)blocks), dim3(256), 0, g->stream, vw, g->cap_total, curv_type, MODE,
-                       g->curv, wl, g->dres, bytes_total);
+                       g->curv.p, wl, g->dres.p, bytes_total);
     if (curv_type != DCR_CURV_1D || MODE == MODE_BYTES) {
         // the bins are independent: fork them onto side streams so their tails overlap; heaviest first
         DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
@@ -783,8 +779,8 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
 // the per-node flags of the incremental pass and, with them, the list of flagged nodes (DevResult::touched_n: whoever zeroes the
 // flags resets the list — a node is appended when its byte leaves zero)
 static void clear_dirty_flags(dcr_graph *g) {
-    (void)hipMemsetAsync(g->dirty, 0, (size_t)(g->n > 0 ? g->n : 1), g->stream);
-    (void)hipMemsetAsync(&g->dres->touched_n, 0, sizeof(int32_t), g->stream);
+    (void)hipMemsetAsync(g->dirty.p, 0, (size_t)(g->n > 0 ? g->n : 1), g->stream);
+    (void)hipMemsetAsync(&g->dres.p->touched_n, 0, sizeof(int32_t), g->stream);
 }
 
 int dcr_curvature_pass(dcr_graph *g, int curv_type) { return curvature_pass_impl(g, curv_type, false); }
@@ -794,15 +790,15 @@ int dcr_curvature_pass_incremental(dcr_graph *g, int curv_type) { return curvatu
 int dcr_curvature_pass_argmin(dcr_graph *g, int curv_type, int incremental, int32_t *out_u, int32_t *out_v,
                               double *out_val) {
     DCR_TRY(curvature_pass_impl(g, curv_type, incremental != 0, true));
-    if (g->hres->ext_slot < 0) DCR_FAIL(DCR_ENOTFOUND, "graph has no edges");
-    g->am_x = g->hres->ext_u;
-    g->am_y = g->hres->ext_v;
-    g->am_dx = g->hres->ext_du;
-    g->am_dy = g->hres->ext_dv;
+    if (g->hres.p->ext_slot < 0) DCR_FAIL(DCR_ENOTFOUND, "graph has no edges");
+    g->am_x = g->hres.p->ext_u;
+    g->am_y = g->hres.p->ext_v;
+    g->am_dx = g->hres.p->ext_du;
+    g->am_dy = g->hres.p->ext_dv;
     g->am_valid = true;
-    if (out_u) *out_u = g->hres->ext_u;
-    if (out_v) *out_v = g->hres->ext_v;
-    if (out_val) *out_val = g->hres->ext_val;
+    if (out_u) *out_u = g->hres.p->ext_u;
+    if (out_v) *out_v = g->hres.p->ext_v;
+    if (out_val) *out_val = g->hres.p->ext_val;
     return DCR_OK;
 }
 
@@ -844,9 +840,9 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
         if (with_argmin) DCR_TRY(argmin_after_pass());
         DCR_TRY(sync_result(g));
         if (g->last_engine == 0)
-            for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres->h2_count[c];
+            for (int c = 0; c < 5; ++c) g->h2_last_count[c] = g->hres.p->h2_count[c];
         // a two-hop pass that reports anything: the next one starts from the stand-alone clear
-        if (g->last_engine == 0 && (g->hres->h2_status != 0 || g->hres->misc[0] != 0 || g->hres->flag_too_big != 0)) g->h2_head_clean = false;
+        if (g->last_engine == 0 && (g->hres.p->h2_status != 0 || g->hres.p->misc[0] != 0 || g->hres.p->flag_too_big != 0)) g->h2_head_clean = false;
         return DCR_OK;
     };
     auto pass_again = [&](bool node_centric_only) -> int {  // the whole pass once more
@@ -857,12 +853,12 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
     if (g->last_engine == 0) {
         // (the bound: the longest chain of one call is four more launches — a missing retry stage (3), then a missing triangle
         //  stage for what only the retry launch listed (4), then pools grown once or twice (2); six leaves room for a third growth)
-        for (int again = 0; again < 6 && g->hres->misc[0] == 0; ++again) {
-            const int st = g->hres->h2_status;
+        for (int again = 0; again < 6 && g->hres.p->misc[0] == 0; ++again) {
+            const int st = g->hres.p->h2_status;
             // a pass without its triangle stage in which some block-class unit listed for it: whatever else the pass reports, the
             // next launch carries the stage, and so does every later pass of this graph (the closing kernel leaves 4 only in place
             // of 0: behind a 3 or a 2 the count says the same)
-            const bool want_tri = !g->h2_last_tri_stage && g->hres->h2_fallback > 0;
+            const bool want_tri = !g->h2_last_tri_stage && g->hres.p->h2_fallback > 0;
             if (want_tri) g->h2_expect_triangles = true;
             if (st == 3) {
                 // launched without its retry stage, and some node's tables filled up: nothing was written; from now on every
@@ -880,11 +876,11 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
             g->ext_part_valid = false;
             DCR_TRY(pass_again(false));
         }
-        if (g->hres->h2_status != 0) g->ext_part_valid = false;  // (the closing kernel wrote nothing)
+        if (g->hres.p->h2_status != 0) g->ext_part_valid = false;  // (the closing kernel wrote nothing)
         // (advisor, round 4) a two-hop pass that ended with a status may have left its edge set partly patched (h2_eset_apply
         // clears the journal before it applies it): the next two-hop pass rebuilds the set instead of trusting it
-        if (g->hres->h2_status != 0) g->h2_eset_valid = false;
-        if (g->hres->h2_status != 0 && g->hres->misc[0] == 0) {
+        if (g->hres.p->h2_status != 0) g->h2_eset_valid = false;
+        if (g->hres.p->h2_status != 0 && g->hres.p->misc[0] == 0) {
             // a table of the two-hop pass filled up (keys of a split node hashed unevenly) or a unit list overflowed:
             // nothing it wrote is kept, the node-centric kernels redo the whole pass
             g->ext_part_valid = false;
@@ -897,14 +893,14 @@ static int curvature_pass_impl(dcr_graph *g, int curv_type, bool want_incrementa
         g->pass_ms_total += ms;
         g->pass_count += 1;
     }
-    if (g->hres->misc[0] != 0) {
+    if (g->hres.p->misc[0] != 0) {
         char buf[256];
         snprintf(buf, sizeof buf, "curvature kernel invariant %d violated: row {%d,%d} a=%d b=%d block=%d thread=%d",
-                 g->hres->misc[0], g->hres->misc[1], g->hres->misc[2], g->hres->misc[3], g->hres->misc[4],
-                 g->hres->misc[5], g->hres->misc[6]);
+                 g->hres.p->misc[0], g->hres.p->misc[1], g->hres.p->misc[2], g->hres.p->misc[3], g->hres.p->misc[4],
+                 g->hres.p->misc[5], g->hres.p->misc[6]);
         DCR_FAIL(DCR_EHIP, buf);
     }
-    if (g->hres->flag_too_big)
+    if (g->hres.p->flag_too_big)
         DCR_FAIL(DCR_ECAPACITY, "more than 65536 edges with deg(u)+deg(v)+2 > 16384 (beyond every LDS table) in one pass");
     g->curv_type_last = curv_type;
     g->curv_valid = true;
@@ -920,8 +916,8 @@ int dcr_pass_engine(dcr_graph *g, int *out) {
 int dcr_h2_stats(dcr_graph *g, int32_t out[6]) {
     if (!g || !out) DCR_FAIL(DCR_EINVAL, "null argument");
     for (int i = 0; i < 6; ++i) out[i] = 0;
-    if (g->last_engine != 0 || !g->hres) return DCR_OK;
-    const DevResult &h = *g->hres;
+    if (g->last_engine != 0 || !g->hres.p) return DCR_OK;
+    const DevResult &h = *g->hres.p;
     out[0] = h.h2_ncand[0];
     out[1] = h.h2_ncand[1];
     out[2] = h.h2_fallback;
@@ -971,26 +967,20 @@ int dcr_bfc_ingredients(dcr_graph *g, int32_t u, int32_t v, int64_t out6[6]) {
     DCR_TRY(dcr_graph_degree(g, u, &du));
     DCR_TRY(dcr_graph_degree(g, v, &dv));
     const int keys = du + dv + 2;
-    int64_t *d_out = nullptr;
-    DCR_TRY(dev_alloc(&d_out, 6));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
-    if (keys <= bin_max_keys(0)) launch_single<0>(g, vw, u, v, d_out);
-    else if (keys <= bin_max_keys(1)) launch_single<1>(g, vw, u, v, d_out);
-    else if (keys <= bin_max_keys(2)) launch_single<2>(g, vw, u, v, d_out);
-    else if (keys <= bin_max_keys(3)) launch_single<3>(g, vw, u, v, d_out);
-    else if (keys <= bin_max_keys(4)) launch_single<4>(g, vw, u, v, d_out);
+    DevBuf<int64_t> d_out;
+    DCR_TRY(d_out.alloc(6));
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, nullptr, (int32_t)g->n, 0};
+    if (keys <= bin_max_keys(0)) launch_single<0>(g, vw, u, v, d_out.p);
+    else if (keys <= bin_max_keys(1)) launch_single<1>(g, vw, u, v, d_out.p);
+    else if (keys <= bin_max_keys(2)) launch_single<2>(g, vw, u, v, d_out.p);
+    else if (keys <= bin_max_keys(3)) launch_single<3>(g, vw, u, v, d_out.p);
+    else if (keys <= bin_max_keys(4)) launch_single<4>(g, vw, u, v, d_out.p);
     else {  // beyond every LDS table: device-memory path (the pair must be an edge for its flags to mean anything)
-        int rc = giant_edge(g, u, v, du, dv, -1, DCR_CURV_BFC, true, d_out);
-        if (rc != DCR_OK) {
-            (void)hipFree(d_out);
-            return rc;
-        }
+        DCR_TRY(giant_edge(g, u, v, du, dv, -1, DCR_CURV_BFC, true, d_out.p));
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out6, d_out, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) DCR_FAIL(DCR_EHIP, hipGetErrorString(e));
+    DCR_HIP(hipGetLastError());
+    DCR_HIP(hipMemcpyAsync(out6, d_out.p, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
 
@@ -1014,20 +1004,13 @@ int dcr_curvature_edge(dcr_graph *g, int32_t u, int32_t v, int curv_type, double
 
 static int algorithmic_bytes(dcr_graph *g, double out2[2]) {
     DCR_HIP(hipSetDevice(g->device));
-    double *d_total = nullptr;
-    DCR_TRY(dev_alloc(&d_total, 2));
-    DCR_HIP(hipMemsetAsync(d_total, 0, 2 * sizeof(double), g->stream));
-    int rc = run_pass<MODE_BYTES>(g, DCR_CURV_BFC, d_total);
-    if (rc == DCR_OK) {
-        hipError_t e = hipMemcpyAsync(out2, d_total, 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = DCR_EHIP;
-        }
-    }
-    (void)hipFree(d_total);
-    return rc;
+    DevBuf<double> d_total;
+    DCR_TRY(d_total.alloc(2));
+    DCR_HIP(hipMemsetAsync(d_total.p, 0, 2 * sizeof(double), g->stream));
+    DCR_TRY(run_pass<MODE_BYTES>(g, DCR_CURV_BFC, d_total.p));
+    DCR_HIP(hipMemcpyAsync(out2, d_total.p, 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipStreamSynchronize(g->stream));
+    return DCR_OK;
 }
 
 int dcr_bfc_algorithmic_bytes(dcr_graph *g, double *out_bytes) {

@@ -113,12 +113,12 @@ __global__ void __launch_bounds__(256) k_giant_unmark(const int2 *rowinfo, const
 }
 
 static int ensure_giant(dcr_graph *g, int d_table) {
-    if (!g->giant_pos) {
-        DCR_TRY(dev_alloc(&g->giant_pos, g->n > 0 ? g->n : 1));
-        DCR_HIP(hipMemsetAsync(g->giant_pos, 0, sizeof(int32_t) * (size_t)(g->n > 0 ? g->n : 1), g->stream));
+    if (!g->giant_pos.p) {
+        DCR_TRY(g->giant_pos.alloc(g->n > 0 ? g->n : 1));
+        DCR_HIP(hipMemsetAsync(g->giant_pos.p, 0, sizeof(int32_t) * (size_t)(g->n > 0 ? g->n : 1), g->stream));
     }
-    DCR_TRY(dev_regrow(&g->giant_cnt, &g->giant_cnt_cap, (int64_t)d_table + 1));
-    if (!g->giant_acc) DCR_TRY(dev_alloc(&g->giant_acc, 4));
+    DCR_TRY(g->giant_cnt.grow((int64_t)d_table + 1));
+    if (!g->giant_acc.p) DCR_TRY(g->giant_acc.alloc(4));
     return DCR_OK;
 }
 
@@ -128,22 +128,22 @@ int giant_edge(dcr_graph *g, int u, int v, int du, int dv, int64_t slot, int cur
     const int a = du >= dv ? u : v, b = du >= dv ? v : u;
     const int da = du >= dv ? du : dv, db = du >= dv ? dv : du;
     DCR_TRY(ensure_giant(g, da));
-    GiantAcc *acc = reinterpret_cast<GiantAcc *>(g->giant_acc);
+    GiantAcc *acc = reinterpret_cast<GiantAcc *>(g->giant_acc.p);
     const int n = (int)g->n;
     const unsigned ga = (unsigned)((da + 255) / 256 > 1024 ? 1024 : (da + 255) / 256 < 1 ? 1 : (da + 255) / 256);
     const unsigned gb = (unsigned)((db + 255) / 256 > 1024 ? 1024 : (db + 255) / 256 < 1 ? 1 : (db + 255) / 256);
-    hipLaunchKernelGGL(k_giant_mark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo, g->col, n, a, b, g->giant_pos,
-                       g->giant_cnt, acc);
-    hipLaunchKernelGGL(k_giant_sweep, dim3(gb), dim3(256), 0, g->stream, g->rowinfo, g->col, n, a, b, g->giant_pos,
-                       g->giant_cnt, acc);
+    hipLaunchKernelGGL(k_giant_mark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, a, b, g->giant_pos.p,
+                       g->giant_cnt.p, acc);
+    hipLaunchKernelGGL(k_giant_sweep, dim3(gb), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, a, b, g->giant_pos.p,
+                       g->giant_cnt.p, acc);
     if (need_cycles) {
         const unsigned gs = (unsigned)(db > 4096 ? 4096 : db < 1 ? 1 : db);
-        hipLaunchKernelGGL(k_giant_stream, dim3(gs), dim3(256), 0, g->stream, g->rowinfo, g->col, n, a, b, g->giant_pos,
-                           g->giant_cnt, acc);
+        hipLaunchKernelGGL(k_giant_stream, dim3(gs), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, a, b, g->giant_pos.p,
+                           g->giant_cnt.p, acc);
     }
-    hipLaunchKernelGGL(k_giant_finish, dim3(1), dim3(64), 0, g->stream, g->rowinfo, u, v, a, slot, curv_type,
-                       slot >= 0 ? g->curv : nullptr, acc, d_out6);
-    hipLaunchKernelGGL(k_giant_unmark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo, g->col, n, a, g->giant_pos);
+    hipLaunchKernelGGL(k_giant_finish, dim3(1), dim3(64), 0, g->stream, g->rowinfo.p, u, v, a, slot, curv_type,
+                       slot >= 0 ? g->curv.p : nullptr, acc, d_out6);
+    hipLaunchKernelGGL(k_giant_unmark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, a, g->giant_pos.p);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
 }
@@ -151,11 +151,11 @@ int giant_edge(dcr_graph *g, int u, int v, int du, int dv, int64_t slot, int cur
 // After the classify kernel: the edges it put on the giant list, one after the other.  One host sync to learn how many.
 int process_giant_edges(dcr_graph *g, int curv_type) {
     DCR_TRY(sync_result(g));
-    const int count = g->hres->giant_count;
+    const int count = g->hres.p->giant_count;
     if (count <= 0) return DCR_OK;
     if (count > GIANT_LIST_CAP) return DCR_OK;  // flag_too_big is set: the caller reports it
     std::vector<int32_t> rec((size_t)count * 5);
-    DCR_HIP(hipMemcpyAsync(rec.data(), g->giant_list, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(rec.data(), g->giant_list.p, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     for (int i = 0; i < count; ++i) {
         const int32_t *r = &rec[(size_t)i * 5];
@@ -335,24 +335,23 @@ __global__ void __launch_bounds__(256) k_hub_edges(View g, int h, const int32_t 
 int process_hub_edges(dcr_graph *g, int curv_type, bool incremental) {
     const int64_t cap = g->cap_total / (NC_MAXD + 1) + 2;  // there cannot be more nodes above NC_MAXD neighbours
     if (cap > g->hub_list_cap) {
-        if (g->hub_list) (void)hipFree(g->hub_list);
-        g->hub_list = nullptr;
-        DCR_TRY(dev_alloc(&g->hub_list, 2 * cap));
+        g->hub_list_cap = 0;
+        DCR_TRY(g->hub_list.alloc(2 * cap));
         g->hub_list_cap = cap;
     }
-    DCR_HIP(hipMemsetAsync(&g->dres->hub_count, 0, sizeof(int32_t), g->stream));
+    DCR_HIP(hipMemsetAsync(&g->dres.p->hub_count, 0, sizeof(int32_t), g->stream));
     const int n = (int)g->n;
     hipLaunchKernelGGL(k_find_hubs, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256 < 1 ? 1 : (n + 255) / 256)),
-                       dim3(256), 0, g->stream, g->rowinfo, n, g->hub_list, g->hub_list_cap, g->dres);
+                       dim3(256), 0, g->stream, g->rowinfo.p, n, g->hub_list.p, g->hub_list_cap, g->dres.p);
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
-    const int count = g->hres->hub_count;
+    const int count = g->hres.p->hub_count;
     if (count <= 0) return DCR_OK;
     if (count > g->hub_list_cap) DCR_FAIL(DCR_ESTATE, "more hubs than adjacency slots allow");
     std::vector<int32_t> hubs((size_t)count * 2);
-    DCR_HIP(hipMemcpyAsync(hubs.data(), g->hub_list, sizeof(int32_t) * hubs.size(), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(hubs.data(), g->hub_list.p, sizeof(int32_t) * hubs.size(), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, incremental ? g->dirty.p : nullptr,
             (int32_t)g->n, 1};
     for (int q = 0; q < count; ++q) {
         const int h = hubs[(size_t)q * 2], dh = hubs[(size_t)q * 2 + 1];
@@ -365,23 +364,20 @@ int process_hub_edges(dcr_graph *g, int curv_type, bool incremental) {
         waves = (waves / 4) * 4;
         if (waves < 4) waves = 4;
         const int64_t need = waves * (int64_t)dh;
-        if (need > g->hub_cnt_cap) {
-            if (g->hub_cnt) (void)hipFree(g->hub_cnt);
-            g->hub_cnt = nullptr;
-            DCR_TRY(dev_alloc(&g->hub_cnt, need));
-            g->hub_cnt_cap = need;
-            DCR_HIP(hipMemsetAsync(g->hub_cnt, 0, sizeof(uint32_t) * (size_t)need, g->stream));
+        if (need > g->hub_cnt.cap) {
+            DCR_TRY(g->hub_cnt.alloc(need));
+            DCR_HIP(hipMemsetAsync(g->hub_cnt.p, 0, sizeof(uint32_t) * (size_t)need, g->stream));
         }
         const unsigned ga = (unsigned)((dh + 255) / 256 > 1024 ? 1024 : (dh + 255) / 256);
-        hipLaunchKernelGGL(k_giant_mark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo, g->col, n, h, h, g->giant_pos,
-                           g->giant_cnt, reinterpret_cast<GiantAcc *>(g->giant_acc));
+        hipLaunchKernelGGL(k_giant_mark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, h, h, g->giant_pos.p,
+                           g->giant_cnt.p, reinterpret_cast<GiantAcc *>(g->giant_acc.p));
         if (curv_type == DCR_CURV_BFC)
             hipLaunchKernelGGL((k_hub_edges<MODE_BFC>), dim3((unsigned)(waves / 4)), dim3(256), 0, g->stream, vw, h,
-                               g->giant_pos, g->hub_cnt, (int64_t)dh, curv_type, g->curv);
+                               g->giant_pos.p, g->hub_cnt.p, (int64_t)dh, curv_type, g->curv.p);
         else
             hipLaunchKernelGGL((k_hub_edges<MODE_TRI>), dim3((unsigned)(waves / 4)), dim3(256), 0, g->stream, vw, h,
-                               g->giant_pos, g->hub_cnt, (int64_t)dh, curv_type, g->curv);
-        hipLaunchKernelGGL(k_giant_unmark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo, g->col, n, h, g->giant_pos);
+                               g->giant_pos.p, g->hub_cnt.p, (int64_t)dh, curv_type, g->curv.p);
+        hipLaunchKernelGGL(k_giant_unmark, dim3(ga), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, n, h, g->giant_pos.p);
         DCR_HIP(hipGetLastError());
     }
     return DCR_OK;

@@ -2239,7 +2239,7 @@ __global__ void __launch_bounds__(256) k_h2_final(View g, const uint4 *rec, doub
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // the pools of the triangle step were too small for the last pass: remember what it asked for (the counters kept counting)
 bool h2_grow_pools(dcr_graph *g) {
-    const DevResult &h = *g->hres;  // (per pool; both pools have the same size)
+    const DevResult &h = *g->hres.p;  // (per pool; both pools have the same size)
     const int64_t t = std::max(h.h2_ntask[0], h.h2_ntask[1]), c = std::max(h.h2_ncand[0], h.h2_ncand[1]), p = std::max(h.h2_npart[0], h.h2_npart[1]);
     if (h.h2_ntask[0] < 0 || h.h2_ntask[1] < 0 || h.h2_ncand[0] < 0 || h.h2_ncand[1] < 0 || h.h2_npart[0] < 0 || h.h2_npart[1] < 0) return false;
     if (t < 0 || c < 0 || p < 0) return false;  // the 31-bit counters wrapped: not a case for this engine
@@ -2251,45 +2251,38 @@ bool h2_grow_pools(dcr_graph *g) {
 }
 
 static int ensure_h2(dcr_graph *g) {
-    {
-        const int32_t *before = g->h2_weight;
-        DCR_TRY(dev_regrow(&g->h2_weight, &g->h2_weight_cap, g->n + 64));
-        if (g->h2_weight != before) g->h2_weight_valid = false;  // a new array: k_h2_weight fills it
-    }
-    DCR_TRY(dev_regrow(&g->h2_rec, &g->h2_rec_cap, g->cap_total + 64));
+    if (g->h2_weight.cap < g->n + 64) g->h2_weight_valid = false;  // a new array: k_h2_weight fills it
+    DCR_TRY(g->h2_weight.grow(g->n + 64));
+    DCR_TRY(g->h2_rec.grow(g->cap_total + 64));
     // edge set: at most cap_total / 2 undirected edges, load <= 1/2
     int bits = 10;
     while ((1ll << bits) < g->cap_total) ++bits;
-    if (g->h2_eset_bits != bits || !g->h2_eset) {
-        if (g->h2_eset) (void)hipFree(g->h2_eset);
-        g->h2_eset = nullptr;
-        DCR_TRY(dev_alloc(&g->h2_eset, (int64_t)1 << bits));
+    if (g->h2_eset_bits != bits || !g->h2_eset.p) {
+        DCR_TRY(g->h2_eset.alloc((int64_t)1 << bits));
         g->h2_eset_bits = bits;
         g->h2_eset_valid = false;
     }
     int bbits = 16;
     while ((1ll << bbits) < 4 * g->cap_total) ++bbits;
-    if (g->h2_bloom_bits != bbits || !g->h2_bloom) {
-        if (g->h2_bloom) (void)hipFree(g->h2_bloom);
-        g->h2_bloom = nullptr;
-        DCR_TRY(dev_alloc(&g->h2_bloom, ((int64_t)1 << bbits) / 32));
+    if (g->h2_bloom_bits != bbits || !g->h2_bloom.p) {
+        DCR_TRY(g->h2_bloom.alloc(((int64_t)1 << bbits) / 32));
         g->h2_bloom_bits = bbits;
         g->h2_eset_valid = false;
     }
     const int64_t need[H2_CLASSES] = {g->n + 64, g->n + 64, g->n + 64, g->n + 64, g->n + g->cap_total / 4 + 64};
-    for (int c = 0; c < H2_CLASSES; ++c) DCR_TRY(dev_regrow(&g->h2_units[c], &g->h2_units_cap[c], need[c]));
-    DCR_TRY(dev_regrow(&g->h2_retry, &g->h2_retry_cap, g->n + g->cap_total / 4 + 64));
+    for (int c = 0; c < H2_CLASSES; ++c) DCR_TRY(g->h2_units[c].grow(need[c]));
+    DCR_TRY(g->h2_retry.grow(g->n + g->cap_total / 4 + 64));
     // triangle step pools: tasks are edges (with the partitions of split nodes: a few times that), candidates and partners
     // adjacency entries of theirs
     // (sized for power-law graphs; a pass that needs more says how much — h2_grow_pools — and is run again)
-    // (two pools of each kind, h2_*_cap counts both: see DevResult)
-    DCR_TRY(dev_regrow(&g->h2_task, &g->h2_task_cap, 2 * std::max<int64_t>(g->cap_total + 4096, g->h2_want[0])));
-    DCR_TRY(dev_regrow(&g->h2_cand, &g->h2_cand_cap, 2 * std::max<int64_t>(2 * g->cap_total + 65536, g->h2_want[1])));
-    DCR_TRY(dev_regrow(&g->h2_part, &g->h2_part_cap, 2 * std::max<int64_t>(g->cap_total + 65536, g->h2_want[2])));
+    // (two pools of each kind, the arrays hold both: see DevResult)
+    DCR_TRY(g->h2_task.grow(2 * std::max<int64_t>(g->cap_total + 4096, g->h2_want[0])));
+    DCR_TRY(g->h2_cand.grow(2 * std::max<int64_t>(2 * g->cap_total + 65536, g->h2_want[1])));
+    DCR_TRY(g->h2_part.grow(2 * std::max<int64_t>(g->cap_total + 65536, g->h2_want[2])));
     // the third step's per-wave lists: the split class (one workgroup of 16 waves per CU; the retry launch reuses its part)
     // and class M (three workgroups of 4 waves per CU)
     const int cus = g->num_cu > 0 ? g->num_cu : 256;
-    DCR_TRY(dev_regrow(&g->h2_lists, &g->h2_lists_cap, (int64_t)cus * (16 + 12) * H2_LIST_WORDS));
+    DCR_TRY(g->h2_lists.grow((int64_t)cus * (16 + 12) * H2_LIST_WORDS));
     return DCR_OK;
 }
 
@@ -2315,7 +2308,7 @@ static void launch_h2_small(dcr_graph *g, const View &vw, const H2Retry &rt, hip
     if (grid > (units + H2_WPB - 1) / H2_WPB) grid = (units + H2_WPB - 1) / H2_WPB;  // small graphs: no idle workgroups
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * H2_WPB), 0, st, vw,
-                       g->h2_units[C], &g->dres->h2_count[C], g->h2_units_cap[C], g->h2_rec, rt);
+                       g->h2_units[C].p, &g->dres.p->h2_count[C], g->h2_units[C].cap, g->h2_rec.p, rt);
 }
 
 template <int C, bool PARTS>
@@ -2327,7 +2320,7 @@ static void launch_h2_block(dcr_graph *g, const View &vw, const H2Tasks &tk, con
     if (grid > most) grid = most;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL((k_h2_block<h2_l1(C), h2_exs(C), h2_waves(C), PARTS>), dim3((unsigned)grid), dim3(64 * h2_waves(C)), 0,
-                       st, vw, tk, units, count, cap, g->h2_rec, rt, is_retry);
+                       st, vw, tk, units, count, cap, g->h2_rec.p, rt, is_retry);
 }
 
 int launch_curvature_pass_h2(dcr_graph *g) {
@@ -2338,22 +2331,22 @@ int launch_curvature_pass_h2(dcr_graph *g) {
             g->num_cu = prop.multiProcessorCount;
     }
     DCR_TRY(ensure_h2(g));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, nullptr, (int32_t)g->n, 0};
     H2Lists L;
     for (int c = 0; c < H2_CLASSES; ++c) {
-        L.units[c] = g->h2_units[c];
-        L.cap[c] = g->h2_units_cap[c];
+        L.units[c] = g->h2_units[c].p;
+        L.cap[c] = g->h2_units[c].cap;
     }
-    int32_t *status = &g->dres->h2_status;
-    const H2Retry rt{g->h2_retry, g->h2_retry_cap, g->h2_weight, g->dres};
-    const int64_t tcap = g->h2_task_cap / 2, ccap = g->h2_cand_cap / 2, pcap = g->h2_part_cap / 2;
-    DevResult *dr = g->dres;
-    unsigned *lists_L = g->h2_lists, *lists_M = g->h2_lists + (int64_t)g->num_cu * 16 * H2_LIST_WORDS;
-    const H2EdgeSet es{g->h2_eset, g->h2_eset_bits, g->h2_bloom, g->h2_bloom_bits};
-    H2Tasks tk{g->h2_task, g->h2_cand, g->h2_part, tcap, ccap, pcap, &dr->h2_ntask[0], &dr->h2_ncand[0], &dr->h2_npart[0],
-               &dr->h2_ncand_done[0], g->dres, g->h2_weight, 0u, lists_L, es};  // pool 0: the split class and the retry launch
-    const H2Tasks tkM{g->h2_task + tcap, g->h2_cand + ccap, g->h2_part + pcap, tcap, ccap, pcap, &dr->h2_ntask[1], &dr->h2_ncand[1],
-                      &dr->h2_npart[1], &dr->h2_ncand_done[1], g->dres, g->h2_weight, 0u, lists_M, es};  // pool 1: class M
+    int32_t *status = &g->dres.p->h2_status;
+    const H2Retry rt{g->h2_retry.p, g->h2_retry.cap, g->h2_weight.p, g->dres.p};
+    const int64_t tcap = g->h2_task.cap / 2, ccap = g->h2_cand.cap / 2, pcap = g->h2_part.cap / 2;
+    DevResult *dr = g->dres.p;
+    unsigned *lists_L = g->h2_lists.p, *lists_M = g->h2_lists.p + (int64_t)g->num_cu * 16 * H2_LIST_WORDS;
+    const H2EdgeSet es{g->h2_eset.p, g->h2_eset_bits, g->h2_bloom.p, g->h2_bloom_bits};
+    H2Tasks tk{g->h2_task.p, g->h2_cand.p, g->h2_part.p, tcap, ccap, pcap, &dr->h2_ntask[0], &dr->h2_ncand[0], &dr->h2_npart[0],
+               &dr->h2_ncand_done[0], g->dres.p, g->h2_weight.p, 0u, lists_L, es};  // pool 0: the split class and the retry launch
+    const H2Tasks tkM{g->h2_task.p + tcap, g->h2_cand.p + ccap, g->h2_part.p + pcap, tcap, ccap, pcap, &dr->h2_ntask[1], &dr->h2_ncand[1],
+                      &dr->h2_npart[1], &dr->h2_ncand_done[1], g->dres.p, g->h2_weight.p, 0u, lists_M, es};  // pool 1: class M
     // The head of the pass.  Steady state (the weights are kept by the edit kernels and the last pass left the result block
     // ready): the two plan kernels and nothing else, they clear what has to be cleared on their way.  Otherwise the stand-alone
     // k_h2_clear first (both bucket halves, and the weights when they have to be computed), k_h2_weight if so, the plan kernels
@@ -2363,7 +2356,7 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     const int64_t pblocks = (g->n + H2_PLAN_THREADS - 1) / H2_PLAN_THREADS;
     // (dirty: n bytes, allocated in whole words? — only the whole words are zeroed here, the caller's fill takes the rest)
     const bool whole = g->n % 4 == 0;
-    unsigned *dirty_words = reinterpret_cast<unsigned *>(g->dirty);
+    unsigned *dirty_words = reinterpret_cast<unsigned *>(g->dirty.p);
     const int64_t n_dirty_words = whole ? g->n / 4 : (int64_t)0;
     const bool run_weight = !g->h2_weight_valid;
     const bool fast_head = !run_weight && g->h2_head_clean && pblocks > 0;
@@ -2371,9 +2364,9 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     g->h2_head_clean = false;
     if (!fast_head) {
         const int64_t cb = (g->n + 255) / 256;
-        hipLaunchKernelGGL(k_h2_clear, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->dres, g->h2_weight,
+        hipLaunchKernelGGL(k_h2_clear, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->dres.p, g->h2_weight.p,
                            run_weight ? g->n : (int64_t)0, dirty_words, n_dirty_words);
-        if (run_weight && sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight);
+        if (run_weight && sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, g->h2_weight.p);
         g->h2_weight_valid = true;  // (from here on the edit kernels keep them)
     }
     g->h2_cleared_dirty = whole;
@@ -2384,15 +2377,15 @@ int launch_curvature_pass_h2(dcr_graph *g) {
                        g->h2_eset_tombs + g->h2_eset_pending <= ((int64_t)1 << g->h2_eset_bits) / 16;
     const bool journal = patch && g->h2_eset_pending > 0;
     if (pblocks > 0) {
-        hipLaunchKernelGGL(k_h2_plan<0>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight, L,
-                           g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec, es, 0);
+        hipLaunchKernelGGL(k_h2_plan<0>, dim3((unsigned)pblocks), dim3(H2_PLAN_THREADS), 0, g->stream, vw, g->h2_weight.p, L,
+                           g->dres.p, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec.p, es, 0);
         hipLaunchKernelGGL(k_h2_plan<1>, dim3((unsigned)(pblocks + (journal ? 1 : 0))), dim3(H2_PLAN_THREADS), 0, g->stream, vw,
-                           g->h2_weight, L, g->dres, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec, es, journal ? 1 : 0);
+                           g->h2_weight.p, L, g->dres.p, parity, fast_head ? 1 : 0, dirty_words, n_dirty_words, g->h2_rec.p, es, journal ? 1 : 0);
     }
     // records of split nodes are accumulated with atomics: start from zero (the fast head: k_h2_plan<1> has done it)
     if (!fast_head)
-        hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4],
-                           g->h2_rec);
+        hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_units[4].p, &g->dres.p->h2_count[4], g->h2_units[4].cap,
+                           g->h2_rec.p);
     g->h2_parity = 1 - parity;  // (the half of this pass is used; the other one is zero: k_h2_clear, or k_h2_plan<0> of this pass)
     g->h2_weight_launches += run_weight ? 1 : 0;
     g->h2_clear_launches += fast_head ? 0 : 1;
@@ -2430,9 +2423,9 @@ int launch_curvature_pass_h2(dcr_graph *g) {
         if (journal) g->h2_eset_tombs += g->h2_eset_pending;  // (applied by k_h2_plan<1> above, ahead of the fork)
     } else {
         DCR_HIP(hipStreamWaitEvent(g->aux, g->ev_fork, 0));
-        DCR_HIP(hipMemsetAsync(g->h2_eset, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, g->aux));
-        DCR_HIP(hipMemsetAsync(g->h2_bloom, 0, sizeof(unsigned) * (((size_t)1 << g->h2_bloom_bits) / 32), g->aux));
-        if (sblocks > 0) hipLaunchKernelGGL(k_h2_eset_build, dim3((unsigned)sblocks), dim3(256), 0, g->aux, vw, es, status, g->dres);
+        DCR_HIP(hipMemsetAsync(g->h2_eset.p, 0xFF, sizeof(unsigned long long) << g->h2_eset_bits, g->aux));
+        DCR_HIP(hipMemsetAsync(g->h2_bloom.p, 0, sizeof(unsigned) * (((size_t)1 << g->h2_bloom_bits) / 32), g->aux));
+        if (sblocks > 0) hipLaunchKernelGGL(k_h2_eset_build, dim3((unsigned)sblocks), dim3(256), 0, g->aux, vw, es, status, g->dres.p);
         g->h2_eset_tombs = 0;
         DCR_HIP(hipEventRecord(g->ev_aux, g->aux));
         eset_on_aux = true;
@@ -2447,8 +2440,8 @@ int launch_curvature_pass_h2(dcr_graph *g) {
         DCR_HIP(hipStreamWaitEvent(st_split, g->ev_aux, 0));
         if (st_mid != st_split) DCR_HIP(hipStreamWaitEvent(st_mid, g->ev_aux, 0));
     }
-    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4], &g->dres->h2_count[4], g->h2_units_cap[4], hint4, 0, st_split);
-    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3], &g->dres->h2_count[3], g->h2_units_cap[3], hint3, 0, st_mid);
+    launch_h2_block<4, true>(g, vw, tk, rt, g->h2_units[4].p, &g->dres.p->h2_count[4], g->h2_units[4].cap, hint4, 0, st_split);
+    launch_h2_block<3, false>(g, vw, tkM, rt, g->h2_units[3].p, &g->dres.p->h2_count[3], g->h2_units[3].cap, hint3, 0, st_mid);
     // The triangle stage (both launches here and the one behind the retry launch) goes with the pass only once some pass of this
     // graph has had a block-class unit on the probe path: the units join their triangle term themselves, and on a graph where all
     // of them can the launches found nothing to do, yet each pushed a full-chip grid through a full chip (32 us on average on the
@@ -2457,8 +2450,8 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     if (tri_stage) {
         // each block class's triangle step right behind it on its own stream (class M's behind the split class's: 292 us beside
         // the other classes, 60 alone — it started 90 us after M's end and sat on the critical path)
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec, status, 0);
-        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec, status, 0);
+        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 4)), dim3(256), 0, pool[lay[0]], es, tk, g->h2_rec.p, status, 0);
+        hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 8)), dim3(256), 0, pool[lay[1]], es, tkM, g->h2_rec.p, status, 0);
     }
     launch_h2_small<2>(g, vw, rt, on(2));
     launch_h2_small<1>(g, vw, rt, on(3));
@@ -2468,11 +2461,7 @@ int launch_curvature_pass_h2(dcr_graph *g) {
             DCR_HIP(hipEventRecord(done[si], pool[si]));
             DCR_HIP(hipStreamWaitEvent(g->stream, done[si], 0));
         }
-    if (!g->ext_part) {
-        Ext *p = nullptr;
-        DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
-        g->ext_part = p;
-    }
+    if (!g->ext_part.p) DCR_TRY(g->ext_part.alloc(2 * EXT_PART_BLOCKS));
     int64_t fblocks = (sblocks + H2_FINAL_Q - 1) / H2_FINAL_Q;
     if (fblocks > H2_FINAL_BLOCKS) fblocks = H2_FINAL_BLOCKS;
     if (fblocks > EXT_PART_BLOCKS / 4) fblocks = EXT_PART_BLOCKS / 4;  // (a pair of partial extrema per WAVE)
@@ -2480,15 +2469,15 @@ int launch_curvature_pass_h2(dcr_graph *g) {
     const bool retry_stage = g->h2_expect_retry;
     if (retry_stage) {
         // nodes whose tables filled up in their class: zero their records, redo them with worst-case partitions
-        hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap,
-                           g->h2_rec);
+        hipLaunchKernelGGL(k_h2_retry_zero, dim3(1024), dim3(256), 0, g->stream, vw, g->h2_retry.p, &g->dres.p->h2_retry, g->h2_retry.cap,
+                           g->h2_rec.p);
         tk.retry_flag = 0x80000000u;
-        launch_h2_block<4, true>(g, vw, tk, rt, g->h2_retry, &g->dres->h2_retry, g->h2_retry_cap, 64, 1, g->stream);
+        launch_h2_block<4, true>(g, vw, tk, rt, g->h2_retry.p, &g->dres.p->h2_retry, g->h2_retry.cap, 64, 1, g->stream);
         if (tri_stage)
-            hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 2)), dim3(256), 0, g->stream, es, tk, g->h2_rec, status, 1);
+            hipLaunchKernelGGL(k_h2_triangles, dim3((unsigned)(g->num_cu * 2)), dim3(256), 0, g->stream, es, tk, g->h2_rec.p, status, 1);
     }
-    hipLaunchKernelGGL(k_h2_final, dim3((unsigned)fblocks), dim3(256), 0, g->stream, vw, g->h2_rec, g->curv, status, (Ext *)g->ext_part,
-                       (Ext *)g->ext_part + EXT_PART_BLOCKS, &g->dres->h2_retry, retry_stage ? 1 : 0, &g->dres->h2_fallback,
+    hipLaunchKernelGGL(k_h2_final, dim3((unsigned)fblocks), dim3(256), 0, g->stream, vw, g->h2_rec.p, g->curv.p, status, g->ext_part.p,
+                       g->ext_part.p + EXT_PART_BLOCKS, &g->dres.p->h2_retry, retry_stage ? 1 : 0, &g->dres.p->h2_fallback,
                        tri_stage ? 1 : 0);
     g->h2_launches += 1;
     g->h2_last_retry_stage = retry_stage;
@@ -2510,14 +2499,14 @@ __global__ void __launch_bounds__(256) k_h2_weight_diff(const int32_t *kept, con
 
 int h2_weight_check(dcr_graph *g, int64_t *mismatches) {
     *mismatches = -1;
-    if (!g->h2_weight_valid || !g->h2_weight) return DCR_OK;
-    DCR_TRY(dev_regrow(&g->h2_weight_chk, &g->h2_weight_chk_cap, g->n + 64));
-    int32_t *fresh = g->h2_weight_chk, *count = g->h2_weight_chk + g->n;  // (the array has 64 words of slack)
+    if (!g->h2_weight_valid || !g->h2_weight.p) return DCR_OK;
+    DCR_TRY(g->h2_weight_chk.grow(g->n + 64));
+    int32_t *fresh = g->h2_weight_chk.p, *count = g->h2_weight_chk.p + g->n;  // (the array has 64 words of slack)
     DCR_HIP(hipMemsetAsync(fresh, 0, sizeof(int32_t) * (size_t)(g->n + 1), g->stream));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, nullptr, (int32_t)g->n, 0};
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, nullptr, (int32_t)g->n, 0};
     const int64_t sblocks = (g->cap_total + 255) / 256, cb = (g->n + 255) / 256;
     if (sblocks > 0) hipLaunchKernelGGL(k_h2_weight, dim3((unsigned)sblocks), dim3(256), 0, g->stream, vw, fresh);
-    hipLaunchKernelGGL(k_h2_weight_diff, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->h2_weight, fresh,
+    hipLaunchKernelGGL(k_h2_weight_diff, dim3((unsigned)(cb < 1 ? 1 : cb > 2048 ? 2048 : cb)), dim3(256), 0, g->stream, g->h2_weight.p, fresh,
                        g->n, count);
     DCR_HIP(hipGetLastError());
     int32_t bad = 0;

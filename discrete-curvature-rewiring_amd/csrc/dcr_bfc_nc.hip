@@ -881,20 +881,9 @@ static int ensure_nc(dcr_graph *g) {
     // units per class, from the smallest degree a member node can have and its sub-units (16 or 4 positions each)
     const int64_t need[NC_CLASSES] = {g->n * 4 + 64, g->cap_total / 3 + 64, g->cap_total / 6 + 64,
                                       g->cap_total / 3 + 64, g->cap_total / 6 + 64};
-    for (int c = 0; c < NC_CLASSES; ++c) {
-        if (g->nc_cap[c] < need[c]) {
-            if (g->nc_units[c]) (void)hipFree(g->nc_units[c]);
-            g->nc_units[c] = nullptr;
-            DCR_TRY(dev_alloc(&g->nc_units[c], need[c]));
-            g->nc_cap[c] = need[c];
-        }
-    }
-    if (g->nc_touch_cap < g->n + 64) {
-        if (g->nc_touch) (void)hipFree(g->nc_touch);
-        g->nc_touch = nullptr;
-        DCR_TRY(dev_alloc(&g->nc_touch, g->n + 64));
-        g->nc_touch_cap = g->n + 64;
-    }
+    for (int c = 0; c < NC_CLASSES; ++c)
+        if (g->nc_units[c].cap < need[c]) DCR_TRY(g->nc_units[c].alloc(need[c]));
+    if (g->nc_touch.cap < g->n + 64) DCR_TRY(g->nc_touch.alloc(g->n + 64));
     return DCR_OK;
 }
 
@@ -914,9 +903,9 @@ static void launch_nc_wave(dcr_graph *g, const View &vw, int curv_type, hipStrea
     // incremental pass after a few exactly flagged edits (an SDRF step): a handful of units, and a full persistent grid
     // costs more to start and drain than they do (pass 0.34 -> 0.26 ms with one workgroup per CU)
     if (vw.dirty && g->pending_edits <= DIRTY_EDITS && grid > g->num_cu) grid = g->num_cu;
-    hipLaunchKernelGGL((k_nc_wave<SLOTS, MODE, CHUNK>), dim3((unsigned)grid), dim3(256), 0, st, vw, g->nc_units[C],
-                       &g->dres->nc_count[C], g->nc_cap[C], g->nc_queues + C * NC_QUEUES * NC_QUEUE_STRIDE, curv_type,
-                       g->curv);
+    hipLaunchKernelGGL((k_nc_wave<SLOTS, MODE, CHUNK>), dim3((unsigned)grid), dim3(256), 0, st, vw, g->nc_units[C].p,
+                       &g->dres.p->nc_count[C], g->nc_units[C].cap, g->nc_queues.p + C * NC_QUEUES * NC_QUEUE_STRIDE, curv_type,
+                       g->curv.p);
 }
 
 template <int C, int MODE>
@@ -927,15 +916,15 @@ static void launch_nc_block(dcr_graph *g, const View &vw, int curv_type, hipStre
     int per_cu = (160 * 1024) / LDS;
     if (per_cu > 32 / W) per_cu = 32 / W;
     if (per_cu < 1) per_cu = 1;
-    hipLaunchKernelGGL((k_nc_block<SLOTS, W, MODE>), dim3(g->num_cu * per_cu), dim3(64 * W), 0, st, vw, g->nc_units[C],
-                       &g->dres->nc_count[C], g->nc_cap[C], &g->dres->nc_next[C], curv_type, g->curv);
+    hipLaunchKernelGGL((k_nc_block<SLOTS, W, MODE>), dim3(g->num_cu * per_cu), dim3(64 * W), 0, st, vw, g->nc_units[C].p,
+                       &g->dres.p->nc_count[C], g->nc_units[C].cap, &g->dres.p->nc_next[C], curv_type, g->curv.p);
 }
 
 template <int MODE>
 static void launch_nc_block_big(dcr_graph *g, const View &vw, int curv_type, hipStream_t st) {
-    hipLaunchKernelGGL((k_nc_block_big<MODE>), dim3(g->num_cu), dim3(256), 0, st, vw, g->nc_units[4],
-                       &g->dres->nc_count[4], g->nc_cap[4], &g->dres->nc_next[4], g->nc_units[3], &g->dres->nc_count[3],
-                       g->nc_cap[3], &g->dres->nc_next[3], curv_type, g->curv);
+    hipLaunchKernelGGL((k_nc_block_big<MODE>), dim3(g->num_cu), dim3(256), 0, st, vw, g->nc_units[4].p,
+                       &g->dres.p->nc_count[4], g->nc_units[4].cap, &g->dres.p->nc_next[4], g->nc_units[3].p, &g->dres.p->nc_count[3],
+                       g->nc_units[3].cap, &g->dres.p->nc_next[3], curv_type, g->curv.p);
 }
 
 template <int MODE>
@@ -947,32 +936,32 @@ static int run_nc(dcr_graph *g, int curv_type, bool incremental) {
         if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0)
             g->num_cu = prop.multiProcessorCount;
     }
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr,
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, incremental ? g->dirty.p : nullptr,
             (int32_t)g->n, 1};
     NcLists L;
     for (int c = 0; c < NC_CLASSES; ++c) {
-        L.units[c] = g->nc_units[c];
-        L.cap[c] = g->nc_cap[c];
+        L.units[c] = g->nc_units[c].p;
+        L.cap[c] = g->nc_units[c].cap;
     }
-    if (!g->nc_queues) DCR_TRY(dev_alloc(&g->nc_queues, 2 * NC_QUEUES * NC_QUEUE_STRIDE));
+    if (!g->nc_queues.p) DCR_TRY(g->nc_queues.alloc(2 * NC_QUEUES * NC_QUEUE_STRIDE));
     {
         const int64_t touch_words = incremental ? (g->n + 3) / 4 : 0;   // (the buffer holds n + 64 bytes)
         int64_t cb = (touch_words + 1023) / 1024;
         if (cb < 1) cb = 1;
         if (cb > 256) cb = 256;
-        hipLaunchKernelGGL(k_nc_clear, dim3((unsigned)cb), dim3(256), 0, g->stream, g->dres, g->nc_queues, 2 * NC_QUEUES * NC_QUEUE_STRIDE,
-                           reinterpret_cast<unsigned *>(g->nc_touch), touch_words);
+        hipLaunchKernelGGL(k_nc_clear, dim3((unsigned)cb), dim3(256), 0, g->stream, g->dres.p, g->nc_queues.p, 2 * NC_QUEUES * NC_QUEUE_STRIDE,
+                           reinterpret_cast<unsigned *>(g->nc_touch.p), touch_words);
     }
     if (incremental) {
         const int64_t blocks = (g->cap_total + 255) / 256;
-        if (blocks > 0) hipLaunchKernelGGL(k_nc_touch, dim3((unsigned)blocks), dim3(256), 0, g->stream, vw, g->nc_touch);
+        if (blocks > 0) hipLaunchKernelGGL(k_nc_touch, dim3((unsigned)blocks), dim3(256), 0, g->stream, vw, g->nc_touch.p);
     }
     const int64_t pblocks = (g->n + PLAN_THREADS - 1) / PLAN_THREADS;
     if (pblocks > 0) {
-        hipLaunchKernelGGL(k_nc_plan<0>, dim3((unsigned)pblocks), dim3(PLAN_THREADS), 0, g->stream, vw, L, g->nc_touch,
-                           g->dres);
-        hipLaunchKernelGGL(k_nc_plan<1>, dim3((unsigned)pblocks), dim3(PLAN_THREADS), 0, g->stream, vw, L, g->nc_touch,
-                           g->dres);
+        hipLaunchKernelGGL(k_nc_plan<0>, dim3((unsigned)pblocks), dim3(PLAN_THREADS), 0, g->stream, vw, L, g->nc_touch.p,
+                           g->dres.p);
+        hipLaunchKernelGGL(k_nc_plan<1>, dim3((unsigned)pblocks), dim3(PLAN_THREADS), 0, g->stream, vw, L, g->nc_touch.p,
+                           g->dres.p);
     }
     // the classes are independent: fork them onto side streams; the rarest, longest-running units first
     DCR_HIP(hipEventRecord(g->ev_fork, g->stream));
@@ -1280,27 +1269,22 @@ static int run_nc_fine(dcr_graph *g, int curv_type, bool incremental, bool list_
         if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) g->num_cu = prop.multiProcessorCount;
     }
     const int64_t need = g->cap_total / 2 + 64;  // every edge has one owner
-    if (g->nc_fine_cap < need) {
-        if (g->nc_fine_list) (void)hipFree(g->nc_fine_list);
-        g->nc_fine_list = nullptr;
-        DCR_TRY(dev_alloc(&g->nc_fine_list, need));
-        g->nc_fine_cap = need;
-    }
-    if (!g->nc_queues) DCR_TRY(dev_alloc(&g->nc_queues, 2 * NC_QUEUES * NC_QUEUE_STRIDE));
-    View vw{g->rowinfo, g->col, g->slot_row, g->cap_total, g->dres->misc, incremental ? g->dirty : nullptr, (int32_t)g->n, 1};
-    hipLaunchKernelGGL(k_nc_clear, dim3(1), dim3(256), 0, g->stream, g->dres, g->nc_queues, 0, (unsigned *)nullptr, (int64_t)0);
+    if (g->nc_fine_list.cap < need) DCR_TRY(g->nc_fine_list.alloc(need));
+    if (!g->nc_queues.p) DCR_TRY(g->nc_queues.alloc(2 * NC_QUEUES * NC_QUEUE_STRIDE));
+    View vw{g->rowinfo.p, g->col.p, g->slot_row.p, g->cap_total, g->dres.p->misc, incremental ? g->dirty.p : nullptr, (int32_t)g->n, 1};
+    hipLaunchKernelGGL(k_nc_clear, dim3(1), dim3(256), 0, g->stream, g->dres.p, g->nc_queues.p, 0, (unsigned *)nullptr, (int64_t)0);
     const int64_t blocks = (g->cap_total + 255) / 256;
-    if (incremental && list_by_rows && g->touched)  // (no list of the flagged nodes: the sweep)
-        hipLaunchKernelGGL(k_nc_fine_list_rows, dim3((unsigned)(2 * g->num_cu)), dim3(256), 0, g->stream, vw, curv_type, g->curv, g->touched,
-                           (int64_t)g->n, g->dres, g->nc_fine_list, g->nc_fine_cap, &g->dres->nc_count[0]);
+    if (incremental && list_by_rows && g->touched.p)  // (no list of the flagged nodes: the sweep)
+        hipLaunchKernelGGL(k_nc_fine_list_rows, dim3((unsigned)(2 * g->num_cu)), dim3(256), 0, g->stream, vw, curv_type, g->curv.p, g->touched.p,
+                           (int64_t)g->n, g->dres.p, g->nc_fine_list.p, g->nc_fine_list.cap, &g->dres.p->nc_count[0]);
     else if (blocks > 0)
-        hipLaunchKernelGGL(k_nc_fine_list, dim3((unsigned)blocks), dim3(256), 0, g->stream, vw, curv_type, g->curv, g->nc_fine_list,
-                           g->nc_fine_cap, &g->dres->nc_count[0]);
+        hipLaunchKernelGGL(k_nc_fine_list, dim3((unsigned)blocks), dim3(256), 0, g->stream, vw, curv_type, g->curv.p, g->nc_fine_list.p,
+                           g->nc_fine_list.cap, &g->dres.p->nc_count[0]);
     // (max_deg_bound: the host's upper bound on every degree, raised by one per edit; owners have at most NC_MAXD neighbours)
     const int64_t dmax = g->max_deg_bound < NC_MAXD ? g->max_deg_bound : NC_MAXD;
 #define DCR_NCF_LAUNCH(SLOTS_, PER_CU_)                                                                                          \
     hipLaunchKernelGGL((k_nc_fine_edges<SLOTS_, MODE>), dim3((unsigned)(g->num_cu * (PER_CU_))), dim3(64 * NCF_W), 0, g->stream, vw, \
-                       g->nc_fine_list, &g->dres->nc_count[0], g->nc_fine_cap, curv_type, g->curv)
+                       g->nc_fine_list.p, &g->dres.p->nc_count[0], g->nc_fine_list.cap, curv_type, g->curv.p)
     if (dmax <= 1024 / 2 - 2) DCR_NCF_LAUNCH(1024, 8);
     else if (dmax <= 4096 / 2 - 2) DCR_NCF_LAUNCH(4096, 4);
     else DCR_NCF_LAUNCH(16384, 1);

@@ -224,7 +224,7 @@ static void launch_sliced(dcr_graph *g, int W) {
     if (rounds > CH_MAX_ROUNDS) rounds = CH_MAX_ROUNDS;
     const int64_t chunk = per_round * rounds;
     const unsigned gx = (unsigned)((g->cap_total + chunk - 1) / chunk);
-    hipLaunchKernelGGL(k_cheeger_sliced<WL>, dim3(gx, (unsigned)groups), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
+    hipLaunchKernelGGL(k_cheeger_sliced<WL>, dim3(gx, (unsigned)groups), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, g->slot_row.p,
                        g->cap_total, g->analysis->chg_members.p, W, (int)rounds, g->analysis->chg_counts.p, (int64_t)64 * W);
 }
 
@@ -238,7 +238,7 @@ static int cheeger_run(dcr_graph *g, int W) {
         per = (per + 15) / 16 * 16;
         if (per < 512) per = 512;
         const unsigned gx = (unsigned)((g->cap_total + per - 1) / per);
-        hipLaunchKernelGGL(k_cheeger_lane, dim3(gx, (unsigned)W), dim3(256), 0, g->stream, g->rowinfo, g->col, g->slot_row,
+        hipLaunchKernelGGL(k_cheeger_lane, dim3(gx, (unsigned)W), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, g->slot_row.p,
                            g->cap_total, g->analysis->chg_members.p, W, per, g->analysis->chg_counts.p, n_sub);
     } else if (W >= 16) {
         launch_sliced<16>(g, W);

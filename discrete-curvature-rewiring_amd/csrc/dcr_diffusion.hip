@@ -343,7 +343,7 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
     double *s = z + groups * gstride;
     DifCtl *ctl = reinterpret_cast<DifCtl *>(A.dif_ctl.p);
     const ColLayout L = {z, p, r, x, q, s, A.dif_part.p, gstride, pstride, nb_mv, nb_el};
-    hipLaunchKernelGGL(k_dif_scale, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, s, n);
+    hipLaunchKernelGGL(k_dif_scale, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo.p, s, n);
     DCR_HIP(hipGetLastError());
 
     const int kk = sp ? (int)std::min<int64_t>(sp->k, n) : 0;
@@ -377,9 +377,9 @@ static int diffusion_batches(dcr_graph *g, const int32_t *sources, int64_t P, co
             hipLaunchKernelGGL(k_heat_start, grid_el, dim3(256), 0, g->stream, s, n, ctl, std::exp(-heat->t), z, x, gstride);
             double *z_in = z, *z_out = p;
             for (int64_t k = 0; k < heat->K; ++k, std::swap(z_in, z_out))
-                hipLaunchKernelGGL(k_heat_term, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo, g->col, z_in, s, heat->t / (double)(k + 1),
+                hipLaunchKernelGGL(k_heat_term, grid_mv, dim3(256), 0, g->stream, plan, g->rowinfo.p, g->col.p, z_in, s, heat->t / (double)(k + 1),
                                    z_out, x, gstride);
-            hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo, n, ctl, x, L.part, gstride, pstride);
+            hipLaunchKernelGGL(k_heat_mass, grid_el, dim3(256), 0, g->stream, g->rowinfo.p, n, ctl, x, L.part, gstride, pstride);
         } else {
             DCR_TRY(col_cg_solve(g, plan, L, ng, DifProblem{ctl}, h.data(), o.max_steps));
         }

@@ -306,19 +306,19 @@ struct FsrRun {
     }
     void power_step() const {
         hipStream_t st = g->stream;
-        hipLaunchKernelGGL(k_fosr_dot, dim3(std::min(blocks_of(n), (unsigned)FSR_DOT_BLOCKS)), dim3(256), 0, st, g->rowinfo, x, n,
+        hipLaunchKernelGGL(k_fosr_dot, dim3(std::min(blocks_of(n), (unsigned)FSR_DOT_BLOCKS)), dim3(256), 0, st, g->rowinfo.p, x, n,
                            2.0 * (double)g->n_edges, part, ctl);
-        hipLaunchKernelGGL(k_fosr_project, dim3(blocks_of(n)), dim3(256), 0, st, g->rowinfo, x, ctl, xp, zs, n);
-        hipLaunchKernelGGL(k_fosr_matvec, dim3(row_grid<FsrRows>(plan)), dim3(256), 0, st, plan, g->rowinfo, g->col, xp, zs, z, part, ctl);
+        hipLaunchKernelGGL(k_fosr_project, dim3(blocks_of(n)), dim3(256), 0, st, g->rowinfo.p, x, ctl, xp, zs, n);
+        hipLaunchKernelGGL(k_fosr_matvec, dim3(row_grid<FsrRows>(plan)), dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, xp, zs, z, part, ctl);
         hipLaunchKernelGGL(k_fosr_scale, dim3(blocks_of(n)), dim3(256), 0, st, z, ctl, x, n);
     }
     // y of what is in x, the order, the pick; *c: the control block as the pick left it (one small read)
     int pick(FsrCtl *c) const {
         hipStream_t st = g->stream;
-        hipLaunchKernelGGL(k_fosr_y, dim3(blocks_of(n)), dim3(256), 0, st, g->rowinfo, x, y, n);
+        hipLaunchKernelGGL(k_fosr_y, dim3(blocks_of(n)), dim3(256), 0, st, g->rowinfo.p, x, y, n);
         const int32_t *order, *rank;
         DCR_TRY(sweep_order(g, &order, &rank));
-        hipLaunchKernelGGL(k_fosr_pick, dim3(row_grid<FsrRows>(plan)), dim3(256), 0, st, plan, g->rowinfo, g->col, y, rank, order,
+        hipLaunchKernelGGL(k_fosr_pick, dim3(row_grid<FsrRows>(plan)), dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, y, rank, order,
                            (int32_t)n, (FsrPart *)part, ctl);
         DCR_HIP(hipGetLastError());
         DCR_HIP(hipMemcpyAsync(c, ctl, sizeof(FsrCtl), hipMemcpyDeviceToHost, st));

@@ -328,53 +328,46 @@ __global__ void k_relayout(const int2 *old_info, const int32_t *old_col, const d
 void launch_add_edge(dcr_graph *g, int32_t u, int32_t v) {
     g->h2_eset_pending += 1;
     g->ext_part_valid = false;
-    hipLaunchKernelGGL(k_add_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->rowcap, g->col, u, v, g->dres,
+    hipLaunchKernelGGL(k_add_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo.p, g->rowcap.p, g->col.p, u, v, g->dres.p,
                        h2_kept_weight(g));
 }
 
 void launch_sdrf_tail(dcr_graph *g, int32_t u, int32_t v, int edit_add, int do_remove, double bound, int edit_rem) {
     g->h2_eset_pending += 2;
     g->ext_part_valid = false;
-    hipLaunchKernelGGL(k_sdrf_tail, dim3(1), dim3(256), 0, g->stream, g->rowinfo, g->rowcap, g->col, g->curv, g->dirty, g->dres, u, v,
-                       edit_add, do_remove, bound, edit_rem, g->touched, (int32_t)g->n, h2_kept_weight(g));
+    hipLaunchKernelGGL(k_sdrf_tail, dim3(1), dim3(256), 0, g->stream, g->rowinfo.p, g->rowcap.p, g->col.p, g->curv.p, g->dirty.p, g->dres.p, u, v,
+                       edit_add, do_remove, bound, edit_rem, g->touched.p, (int32_t)g->n, h2_kept_weight(g));
 }
 
 void launch_remove_if_above(dcr_graph *g, double bound, int edit) {
     g->h2_eset_pending += 1;
     g->ext_part_valid = false;
     // flag the neighbourhood while the edge is still there, then remove it
-    hipLaunchKernelGGL(k_mark_dirty_ext, dim3(1), dim3(256), 0, g->stream, g->rowinfo, g->col, g->dirty, g->dres, bound,
-                       edit, g->touched, (int32_t)g->n);
-    hipLaunchKernelGGL(k_remove_if_above, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, g->dres, bound,
+    hipLaunchKernelGGL(k_mark_dirty_ext, dim3(1), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, g->dirty.p, g->dres.p, bound,
+                       edit, g->touched.p, (int32_t)g->n);
+    hipLaunchKernelGGL(k_remove_if_above, dim3(1), dim3(64), 0, g->stream, g->rowinfo.p, g->col.p, g->curv.p, g->dres.p, bound,
                        h2_kept_weight(g));
 }
 
 void launch_mark_dirty(dcr_graph *g, int32_t u, int32_t v, int edit) {
     if (u != -2 && (u < 0 || v < 0)) return;
-    hipLaunchKernelGGL(k_mark_dirty, dim3(1), dim3(256), 0, g->stream, g->rowinfo, g->col, g->dirty, u, v, edit, g->dres, g->touched,
+    hipLaunchKernelGGL(k_mark_dirty, dim3(1), dim3(256), 0, g->stream, g->rowinfo.p, g->col.p, g->dirty.p, u, v, edit, g->dres.p, g->touched.p,
                        (int32_t)g->n);
 }
 
 int sync_result(dcr_graph *g) {
-    DCR_HIP(hipMemcpyAsync(g->hres, g->dres, sizeof(DevResult), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(g->hres.p, g->dres.p, sizeof(DevResult), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
-    return DCR_OK;
-}
-
-static int alloc_layout(dcr_graph *g, int64_t cap_total) {
-    DCR_TRY(dev_alloc(&g->col, cap_total + 64));  // padded: rows are read in aligned 16-byte pieces
-    DCR_TRY(dev_alloc(&g->slot_row, cap_total));
-    DCR_TRY(dev_alloc(&g->curv, cap_total));
-    g->cap_total = cap_total;
     return DCR_OK;
 }
 
 // Re-pack every row with fresh slack (called when an append finds its row full).
 // Row order, in-row order and the (stale) curvature values keep their relative slot order.
+// The new layout is built in locals and exchanged in at the end: a failed allocation leaves the graph as it was.  (rowcap is
+// rewritten in place, behind the last allocation: a graph whose stream fails after that is lost either way.)
 int relayout(dcr_graph *g) {
-    g->ext_part_valid = false;  // slots move
     std::vector<int2> info((size_t)g->n);
-    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo.p, sizeof(int2) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     std::vector<int32_t> start((size_t)g->n), cap((size_t)g->n);
     int64_t tot = 0;
@@ -387,34 +380,32 @@ int relayout(dcr_graph *g) {
         tot += cap[(size_t)u];
         if (tot > INT32_MAX) DCR_FAIL(DCR_ECAPACITY, "adjacency exceeds 2^31 slots");
     }
-    int32_t *d_start = nullptr;
-    DCR_TRY(dev_alloc(&d_start, g->n));
-    DCR_HIP(hipMemcpyAsync(d_start, start.data(), sizeof(int32_t) * (size_t)g->n, hipMemcpyHostToDevice, g->stream));
-    DCR_HIP(hipMemcpyAsync(g->rowcap, cap.data(), sizeof(int32_t) * (size_t)g->n, hipMemcpyHostToDevice, g->stream));
-    int2 *old_info = g->rowinfo;
-    int32_t *old_col = g->col, *old_slot_row = g->slot_row;
-    double *old_curv = g->curv;
-    g->rowinfo = nullptr;
-    DCR_TRY(dev_alloc(&g->rowinfo, g->n));
-    DCR_TRY(alloc_layout(g, tot));
-    DCR_HIP(hipMemsetAsync(g->curv, 0, sizeof(double) * (size_t)tot, g->stream));
-    DCR_HIP(hipMemsetAsync(g->col, 0xff, sizeof(int32_t) * (size_t)tot, g->stream));
+    DevBuf<int32_t> d_start, col, slot_row;
+    DevBuf<int2> rowinfo;
+    DevBuf<double> curv;
+    DCR_TRY(d_start.alloc(g->n));
+    DCR_TRY(rowinfo.alloc(g->n));
+    DCR_TRY(col.alloc(tot + 64));  // padded: rows are read in aligned 16-byte pieces
+    DCR_TRY(slot_row.alloc(tot));
+    DCR_TRY(curv.alloc(tot));
+    DCR_HIP(hipMemcpyAsync(d_start.p, start.data(), sizeof(int32_t) * (size_t)g->n, hipMemcpyHostToDevice, g->stream));
+    DCR_HIP(hipMemsetAsync(curv.p, 0, sizeof(double) * (size_t)tot, g->stream));
+    DCR_HIP(hipMemsetAsync(col.p, 0xff, sizeof(int32_t) * (size_t)tot, g->stream));
+    DCR_HIP(hipMemcpyAsync(g->rowcap.p, cap.data(), sizeof(int32_t) * (size_t)g->n, hipMemcpyHostToDevice, g->stream));
     int waves_per_block = 4;
     dim3 grid((unsigned)((g->n + waves_per_block - 1) / waves_per_block));
-    hipLaunchKernelGGL(k_relayout, grid, dim3(64 * waves_per_block), 0, g->stream, old_info, old_col, old_curv, d_start,
-                       g->rowinfo, g->col, g->curv, g->slot_row, g->rowcap, g->n);
+    hipLaunchKernelGGL(k_relayout, grid, dim3(64 * waves_per_block), 0, g->stream, g->rowinfo.p, g->col.p, g->curv.p, d_start.p,
+                       rowinfo.p, col.p, curv.p, slot_row.p, g->rowcap.p, g->n);
     DCR_HIP(hipGetLastError());
     DCR_HIP(hipStreamSynchronize(g->stream));
-    (void)hipFree(old_info);
-    (void)hipFree(old_col);
-    (void)hipFree(old_slot_row);
-    (void)hipFree(old_curv);
-    (void)hipFree(d_start);
+    g->rowinfo.swap(rowinfo);
+    g->col.swap(col);
+    g->slot_row.swap(slot_row);
+    g->curv.swap(curv);
+    g->cap_total = tot;
+    g->ext_part_valid = false;  // slots moved
     // work lists are sized by slots
-    for (int b = 0; b < NBINS; ++b) {
-        if (g->work[b]) (void)hipFree(g->work[b]);
-        g->work[b] = nullptr;
-    }
+    for (int b = 0; b < NBINS; ++b) g->work[b].free();
     g->work_cap = 0;
     g->max_deg_bound = maxd;
     return DCR_OK;
@@ -423,6 +414,26 @@ int relayout(dcr_graph *g) {
 }  // namespace dcr
 
 using namespace dcr;
+
+dcr_graph::~dcr_graph() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    sdrf_scratch_destroy(this);
+    analysis_destroy(this);
+    for (int b = 0; b < NBINS - 1; ++b) {
+        if (side[b]) (void)hipStreamDestroy(side[b]);
+        if (ev_join[b]) (void)hipEventDestroy(ev_join[b]);
+    }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_aux) (void)hipEventDestroy(ev_aux);
+    if (aux) (void)hipStreamDestroy(aux);
+    for (int b = 0; b < 2; ++b)
+        if (low[b]) (void)hipStreamDestroy(low[b]);
+    if (ev_aux2) (void)hipEventDestroy(ev_aux2);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+}
 
 extern "C" {
 
@@ -521,25 +532,28 @@ int dcr_graph_create(int device, int64_t n, int64_t m, const int64_t *src, const
     }
     for (int b = 0; b < 2; ++b) DCR_HIP(hipStreamCreateWithPriority(&g->low[b], hipStreamNonBlocking, prio_low));
     DCR_HIP(hipEventCreateWithFlags(&g->ev_aux2, DCR_EVENT_FLAGS));
-    DCR_TRY(dev_alloc(&g->rowinfo, n));
-    DCR_TRY(dev_alloc(&g->rowcap, n));
-    DCR_TRY(alloc_layout(g, tot));
-    DCR_TRY(dev_alloc(&g->dres, 1));
+    DCR_TRY(g->rowinfo.alloc(n));
+    DCR_TRY(g->rowcap.alloc(n));
+    DCR_TRY(g->col.alloc(tot + 64));  // padded: rows are read in aligned 16-byte pieces
+    DCR_TRY(g->slot_row.alloc(tot));
+    DCR_TRY(g->curv.alloc(tot));
+    g->cap_total = tot;
+    DCR_TRY(g->dres.alloc(1));
     DCR_TRY(sdrf_scratch_create(g));
-    DCR_TRY(dev_alloc(&g->dirty, n + 4));  // OR-ed through 32-bit words
-    DCR_HIP(hipMemsetAsync(g->dirty, 0, (size_t)(n > 0 ? n : 1), g->stream));
-    DCR_TRY(dev_alloc(&g->touched, n + 64));
-    DCR_HIP(hipHostMalloc((void **)&g->hres, sizeof(DevResult), hipHostMallocDefault));
-    std::memset(g->hres, 0, sizeof(DevResult));
-    DCR_HIP(hipMemsetAsync(g->dres, 0, sizeof(DevResult), g->stream));
-    DCR_HIP(hipMemsetAsync(g->curv, 0, sizeof(double) * (size_t)(tot > 0 ? tot : 1), g->stream));
+    DCR_TRY(g->dirty.alloc(n + 4));  // OR-ed through 32-bit words
+    DCR_HIP(hipMemsetAsync(g->dirty.p, 0, (size_t)(n > 0 ? n : 1), g->stream));
+    DCR_TRY(g->touched.alloc(n + 64));
+    DCR_TRY(g->hres.alloc(1));
+    std::memset(g->hres.p, 0, sizeof(DevResult));
+    DCR_HIP(hipMemsetAsync(g->dres.p, 0, sizeof(DevResult), g->stream));
+    DCR_HIP(hipMemsetAsync(g->curv.p, 0, sizeof(double) * (size_t)(tot > 0 ? tot : 1), g->stream));
     if (n > 0) {
-        DCR_HIP(hipMemcpyAsync(g->rowinfo, info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, g->stream));
-        DCR_HIP(hipMemcpyAsync(g->rowcap, cap.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(g->rowinfo.p, info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(g->rowcap.p, cap.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
     }
     if (tot > 0) {
-        DCR_HIP(hipMemcpyAsync(g->col, col.data(), sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g->stream));
-        DCR_HIP(hipMemcpyAsync(g->slot_row, slot_row.data(), sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice,
+        DCR_HIP(hipMemcpyAsync(g->col.p, col.data(), sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g->stream));
+        DCR_HIP(hipMemcpyAsync(g->slot_row.p, slot_row.data(), sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice,
                                g->stream));
     }
     DCR_HIP(hipStreamSynchronize(g->stream));
@@ -547,35 +561,7 @@ int dcr_graph_create(int device, int64_t n, int64_t m, const int64_t *src, const
 }
 
 int dcr_graph_destroy(dcr_graph *g) {
-    if (!g) return DCR_OK;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    void *dev_ptrs[] = {g->rowinfo, g->rowcap, g->col, g->slot_row, g->curv, g->dres, g->dirty, g->nc_units[0], g->nc_units[1], g->nc_units[2],
-                        g->nc_units[3], g->nc_units[4], g->nc_touch, g->nc_fine_list, g->touched, g->nc_queues, g->giant_list,
-                        g->giant_pos, g->giant_cnt, g->giant_acc, g->hub_list, g->hub_cnt, g->h2_weight, g->h2_weight_chk,
-                        g->h2_units[0], g->h2_units[1], g->h2_units[2], g->h2_units[3], g->h2_units[4], g->h2_retry, g->h2_task, g->h2_cand, g->h2_part, g->h2_bloom,
-                        g->h2_rec, g->h2_eset, g->ext_part, g->h2_lists};
-    for (void *p : dev_ptrs)
-        if (p) (void)hipFree(p);
-    analysis_destroy(g);
-    sdrf_scratch_destroy(g);
-    for (int b = 0; b < NBINS; ++b)
-        if (g->work[b]) (void)hipFree(g->work[b]);
-    if (g->hres) (void)hipHostFree(g->hres);
-    for (int b = 0; b < NBINS - 1; ++b) {
-        if (g->side[b]) (void)hipStreamDestroy(g->side[b]);
-        if (g->ev_join[b]) (void)hipEventDestroy(g->ev_join[b]);
-    }
-    if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
-    if (g->ev_aux) (void)hipEventDestroy(g->ev_aux);
-    if (g->aux) (void)hipStreamDestroy(g->aux);
-    for (int b = 0; b < 2; ++b)
-        if (g->low[b]) (void)hipStreamDestroy(g->low[b]);
-    if (g->ev_aux2) (void)hipEventDestroy(g->ev_aux2);
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
+    delete g;  // (null: nothing)
     return DCR_OK;
 }
 
@@ -607,13 +593,13 @@ int dcr_graph_add_edge(dcr_graph *g, int32_t u, int32_t v) {
         launch_add_edge(g, u, v);
         DCR_HIP(hipGetLastError());
         DCR_TRY(sync_result(g));
-        if (g->hres->add_status == 0) {
+        if (g->hres.p->add_status == 0) {
             g->n_edges++;
             g->max_deg_bound++;
             launch_mark_dirty(g, u, v, g->pending_edits++);
             return DCR_OK;
         }
-        if (g->hres->add_status == 2) return DCR_OK;  // networkx: adding an existing edge changes nothing
+        if (g->hres.p->add_status == 2) return DCR_OK;  // networkx: adding an existing edge changes nothing
         DCR_TRY(relayout(g));
     }
     DCR_FAIL(DCR_ECAPACITY, "row still full after relayout");
@@ -627,11 +613,11 @@ int dcr_graph_remove_edge(dcr_graph *g, int32_t u, int32_t v) {
     launch_mark_dirty(g, u, v, g->pending_edits++);
     g->h2_eset_pending += 1;
     g->ext_part_valid = false;
-    hipLaunchKernelGGL(k_remove_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, g->curv, u, v, g->dres,
+    hipLaunchKernelGGL(k_remove_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo.p, g->col.p, g->curv.p, u, v, g->dres.p,
                        h2_kept_weight(g));
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
-    if (g->hres->misc[0] != 0) DCR_FAIL(DCR_ENOTFOUND, "edge not in graph");
+    if (g->hres.p->misc[0] != 0) DCR_FAIL(DCR_ENOTFOUND, "edge not in graph");
     g->n_edges--;
     return DCR_OK;
 }
@@ -644,10 +630,10 @@ int dcr_graph_has_edge(dcr_graph *g, int32_t u, int32_t v, int *out) {
     }
     DCR_TRY(check_pair(g, u, v));
     DCR_HIP(hipSetDevice(g->device));
-    hipLaunchKernelGGL(k_has_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo, g->col, u, v, g->dres);
+    hipLaunchKernelGGL(k_has_edge, dim3(1), dim3(64), 0, g->stream, g->rowinfo.p, g->col.p, u, v, g->dres.p);
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
-    *out = g->hres->misc[0];
+    *out = g->hres.p->misc[0];
     return DCR_OK;
 }
 
@@ -655,7 +641,7 @@ int dcr_graph_degree(dcr_graph *g, int32_t u, int32_t *out) {
     if (!g || !out || u < 0 || u >= g->n) DCR_FAIL(DCR_EINVAL, "bad argument");
     DCR_HIP(hipSetDevice(g->device));
     int2 ri;
-    DCR_HIP(hipMemcpyAsync(&ri, g->rowinfo + u, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(&ri, g->rowinfo.p + u, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     *out = ri.y;
     return DCR_OK;
@@ -665,12 +651,12 @@ int dcr_graph_neighbors(dcr_graph *g, int32_t u, int64_t cap, int32_t *out, int6
     if (!g || !n_out || u < 0 || u >= g->n) DCR_FAIL(DCR_EINVAL, "bad argument");
     DCR_HIP(hipSetDevice(g->device));
     int2 ri;
-    DCR_HIP(hipMemcpyAsync(&ri, g->rowinfo + u, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(&ri, g->rowinfo.p + u, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     *n_out = ri.y;
     if (ri.y > cap) DCR_FAIL(DCR_ECAPACITY, "neighbour buffer too small");
     if (ri.y > 0) {
-        DCR_HIP(hipMemcpyAsync(out, g->col + ri.x, sizeof(int32_t) * (size_t)ri.y, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(out, g->col.p + ri.x, sizeof(int32_t) * (size_t)ri.y, hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
     }
     return DCR_OK;
@@ -681,9 +667,9 @@ static int fetch_rows(dcr_graph *g, std::vector<int2> &info, std::vector<int32_t
     info.resize((size_t)g->n);
     col.resize((size_t)g->cap_total);
     if (g->n > 0)
-        DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo, sizeof(int2) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(info.data(), g->rowinfo.p, sizeof(int2) * (size_t)g->n, hipMemcpyDeviceToHost, g->stream));
     if (g->cap_total > 0)
-        DCR_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)g->cap_total, hipMemcpyDeviceToHost,
+        DCR_HIP(hipMemcpyAsync(col.data(), g->col.p, sizeof(int32_t) * (size_t)g->cap_total, hipMemcpyDeviceToHost,
                                g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
@@ -754,7 +740,7 @@ int dcr_curvature_read(dcr_graph *g, double *out_curv, int32_t *out_u, int32_t *
     DCR_TRY(fetch_rows(g, info, col));
     std::vector<double> cv((size_t)g->cap_total);
     if (g->cap_total > 0) {
-        DCR_HIP(hipMemcpyAsync(cv.data(), g->curv, sizeof(double) * (size_t)g->cap_total, hipMemcpyDeviceToHost,
+        DCR_HIP(hipMemcpyAsync(cv.data(), g->curv.p, sizeof(double) * (size_t)g->cap_total, hipMemcpyDeviceToHost,
                                g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
     }

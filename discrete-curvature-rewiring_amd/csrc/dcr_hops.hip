@@ -196,7 +196,7 @@ struct HopRun {
         unsigned long long now[64 * HOP_MAX_W], before[64 * HOP_MAX_W] = {};
         for (int64_t level = 1; max_hops < 0 || level <= max_hops; ++level) {
             if (level > n) DCR_FAIL(DCR_ESTATE, "hop distances: more levels than nodes");
-            hipLaunchKernelGGL(k_hop_level<W>, dim3(row_grid<HopRows>(plan)), dim3(256), 0, st, plan, g->rowinfo, g->col, frontier, visited,
+            hipLaunchKernelGGL(k_hop_level<W>, dim3(row_grid<HopRows>(plan)), dim3(256), 0, st, plan, g->rowinfo.p, g->col.p, frontier, visited,
                                next, live);
             hipLaunchKernelGGL(k_hop_count<W>, dim3(std::min(blocks_of((n + 63) / 64, 4), (unsigned)HOP_COUNT_BLOCKS)), dim3(256), 0, st, next,
                                n, (int32_t)level, dist, totals);

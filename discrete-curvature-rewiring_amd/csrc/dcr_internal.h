@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "dcr.h"
@@ -211,6 +213,54 @@ struct ImpStats {  // per (x,y) statistics for the improvement kernels; lives in
     int32_t pad_;
 };
 
+template <typename T>
+int dev_alloc(T **p, int64_t count, bool pinned = false) {  // pinned: page-locked host memory instead of device memory
+    void *q = nullptr;
+    const size_t bytes = (size_t)(count > 0 ? count : 1) * sizeof(T);
+    hipError_t e = pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+        set_error(std::string(pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
+        return DCR_ENOMEM;
+    }
+    *p = (T *)q;
+    return DCR_OK;
+}
+
+// A device array that owns its memory (PinnedBuf: the same in pinned host memory).  It is never copied: a copy handed to a kernel
+// launch or a helper would free the memory at the end of the call, with the kernel still queued.  Kernels, helpers and the structs
+// a launch takes by value get the raw pointer p, which holds until the next alloc(), grow() or swap().
+template <typename T, bool PINNED = false>
+struct DevBuf {
+    T *p = nullptr;
+    int64_t cap = 0;  // elements
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { free(); }
+
+    void free() {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // a new array of exactly `count` elements in place of what is there (empty if that fails); the contents are lost
+    int alloc(int64_t count) {
+        free();
+        DCR_TRY(dev_alloc(&p, count, PINNED));
+        cap = count;
+        return DCR_OK;
+    }
+    // room for `need` elements: what is there when it is enough, else a new array of need + need / 4 + 64; the contents are lost
+    int grow(int64_t need) { return need <= cap ? DCR_OK : alloc(need + need / 4 + 64); }
+    void swap(DevBuf &o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+};
+template <typename T>
+using PinnedBuf = DevBuf<T, true>;
+
 struct AnalysisState;  // dcr_analysis.h
 struct SdrfScratch;    // dcr_sdrf.hip
 
@@ -224,11 +274,11 @@ struct dcr_graph {
     int64_t cap_total = 0;  // adjacency slots allocated
 
     // HBM-resident graph: rows in insertion order, slack-padded
-    int2 *rowinfo = nullptr;     // [n] {start slot, degree}
-    int32_t *rowcap = nullptr;   // [n] capacity of each row
-    int32_t *col = nullptr;      // [cap_total] neighbour ids
-    int32_t *slot_row = nullptr; // [cap_total] owning row of each slot
-    double *curv = nullptr;      // [cap_total] curvature of the undirected edge stored at slot (col > row)
+    dcr::DevBuf<int2> rowinfo;      // [n] {start slot, degree}
+    dcr::DevBuf<int32_t> rowcap;    // [n] capacity of each row
+    dcr::DevBuf<int32_t> col;       // [cap_total + 64] neighbour ids (padded: rows are read in aligned 16-byte pieces)
+    dcr::DevBuf<int32_t> slot_row;  // [cap_total] owning row of each slot
+    dcr::DevBuf<double> curv;       // [cap_total] curvature of the undirected edge stored at slot (col > row)
 
     // degrees of the last arg-min edge as seen by the device; dropped by any edit
     int32_t am_x = -1, am_y = -1, am_dx = 0, am_dy = 0;
@@ -237,19 +287,16 @@ struct dcr_graph {
 
     int curv_type_last = -1;
     bool curv_valid = false;
-    uint8_t *dirty = nullptr;    // [n] node flags: an incident edge was added/removed at this node or a neighbour
+    dcr::DevBuf<uint8_t> dirty;  // [n + 4] node flags: an incident edge was added/removed at this node or a neighbour
     bool dirty_tracked = false;  // flags cover every edit since the last pass
     int pending_edits = 0;       // edits flagged since the last pass (the first DIRTY_EDITS get exact flags)
 
     // node-centric pass (dcr_bfc_nc.hip): unit lists per degree class
-    int2 *nc_units[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // {node, first sub-unit}
-    int64_t nc_cap[5] = {0, 0, 0, 0, 0};
-    int32_t *nc_queues = nullptr;  // dequeue cursors of the two wave-class kernels, one cache line each
-    uint8_t *nc_touch = nullptr;  // [n] incremental pass: node has a flagged neighbour
-    int64_t nc_touch_cap = 0;
-    int2 *nc_fine_list = nullptr;  // incremental pass behind a few exactly flagged edits: the edges to recompute {owner, position}
-    int64_t nc_fine_cap = 0;
-    int32_t *touched = nullptr;    // [n + 64] the flagged nodes, each once (DevResult::touched_n of them)
+    dcr::DevBuf<int2> nc_units[5];      // {node, first sub-unit}
+    dcr::DevBuf<int32_t> nc_queues;     // dequeue cursors of the two wave-class kernels, one cache line each (allocated on first use)
+    dcr::DevBuf<uint8_t> nc_touch;      // [n + 64] incremental pass: node has a flagged neighbour
+    dcr::DevBuf<int2> nc_fine_list;     // incremental pass behind a few exactly flagged edits: the edges to recompute {owner, position}
+    dcr::DevBuf<int32_t> touched;       // [n + 64] the flagged nodes, each once (DevResult::touched_n of them)
     double sum_deg2 = 0.0;        // sum of squared degrees when the graph was created (engine choice: size of the 2-hop neighbourhoods)
     int32_t max_deg_bound = 0;    // host-side upper bound on the largest degree (exact after create / relayout)
     int pass_impl = 0;            // 0: automatic (default: two-hop kernels for full Balanced Forman passes of graphs large enough to
@@ -259,23 +306,17 @@ struct dcr_graph {
     int last_engine = -1;         // which implementation ran the last pass: 0 two-hop, 1 edge-centric, 2 node-centric
 
     // two-hop pass (dcr_bfc_h2.hip)
-    int32_t *h2_weight = nullptr;     // [n] sum of the neighbours' degrees
-    int4 *h2_units[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // per class {node, partitions << 16 | partition, row start, degree}
-    int64_t h2_units_cap[5] = {0, 0, 0, 0, 0};
-    uint4 *h2_task = nullptr;         // triangle step pools (dcr_bfc_h2.hip)
-    int4 *h2_cand = nullptr;
-    int32_t *h2_part = nullptr;
-    unsigned *h2_lists = nullptr;     // per-wave lists of the block classes' third step (dcr_bfc_h2.hip: H2List)
-    int64_t h2_lists_cap = 0;
-    int64_t h2_task_cap = 0, h2_cand_cap = 0, h2_part_cap = 0;
+    dcr::DevBuf<int32_t> h2_weight;   // [n] sum of the neighbours' degrees
+    dcr::DevBuf<int4> h2_units[5];    // per class {node, partitions << 16 | partition, row start, degree}
+    dcr::DevBuf<uint4> h2_task;       // triangle step pools (dcr_bfc_h2.hip): two of each kind in one array, so each pool has half
+    dcr::DevBuf<int4> h2_cand;        // of the array's cap
+    dcr::DevBuf<int32_t> h2_part;
+    dcr::DevBuf<unsigned> h2_lists;   // per-wave lists of the block classes' third step (dcr_bfc_h2.hip: H2List)
     int64_t h2_want[3] = {0, 0, 0};   // pool sizes a pass asked for (tasks, candidates, partners)
-    unsigned *h2_bloom = nullptr;     // one bit per edge (prefilter of the edge set)
-    int h2_bloom_bits = 0;
-    int4 *h2_retry = nullptr;         // units of nodes whose tables filled up in their class (redone by the largest class)
-    int64_t h2_retry_cap = 0;
-    uint4 *h2_rec = nullptr;          // [cap_total] per directed slot {|sq| on the far side, max count, triangles, reverse slot}
-    int64_t h2_rec_cap = 0;
-    int64_t h2_weight_cap = 0;
+    dcr::DevBuf<unsigned> h2_bloom;   // one bit per edge (prefilter of the edge set)
+    int h2_bloom_bits = 0;            // 2^bits bits in the filter: keys its reallocation, and the kernels hash with it
+    dcr::DevBuf<int4> h2_retry;       // units of nodes whose tables filled up in their class (redone by the largest class)
+    dcr::DevBuf<uint4> h2_rec;        // [cap_total] per directed slot {|sq| on the far side, max count, triangles, reverse slot}
     // h2_weight holds W of the CURRENT rows (bit 31 aside): k_h2_weight has filled this array and every writer of a degree since
     // has kept it (dev_add_edge / dev_remove_edge, the only writers behind dcr_graph_create; relayout() moves rows and changes no
     // degree).  False for a new graph and whenever the array is (re)allocated; a pass then runs k_h2_weight.
@@ -285,9 +326,8 @@ struct dcr_graph {
     bool h2_head_clean = false;
     int h2_parity = 0;                 // the bucket half the next pass counts in
     int h2_weight_launches = 0, h2_clear_launches = 0;  // of the h2_launches: those that ran k_h2_weight / the stand-alone k_h2_clear
-    int32_t *h2_weight_chk = nullptr;  // dcr_h2_weight_check: W recomputed (diagnostic, allocated on first use)
-    int64_t h2_weight_chk_cap = 0;
-    unsigned long long *h2_eset = nullptr;  // every undirected edge as one 64-bit key (open addressing), rebuilt per pass
+    dcr::DevBuf<int32_t> h2_weight_chk;  // dcr_h2_weight_check: W recomputed (diagnostic, allocated on first use)
+    dcr::DevBuf<unsigned long long> h2_eset;  // [2^h2_eset_bits] every undirected edge as one 64-bit key (open addressing), rebuilt per pass
     int h2_eset_bits = 0;
     bool h2_expect_retry = false;      // some pass of this graph had nodes on the retry list: the retry stage is launched with every pass
     bool h2_expect_triangles = false;  // some pass of this graph had a block-class unit on the probe path (DevResult::h2_fallback):
@@ -301,32 +341,31 @@ struct dcr_graph {
     int32_t h2_last_count[5] = {-1, -1, -1, -1, -1};  // units per class of the previous pass (sizes the next grids)
 
     // edges beyond every LDS table (dcr_bfc_giant.hip): records {slot, u, v, deg u, deg v}; position map over all ids
-    int32_t *giant_list = nullptr;
-    int32_t *giant_pos = nullptr;
-    uint32_t *giant_cnt = nullptr;
-    int64_t giant_cnt_cap = 0;
-    int32_t *giant_acc = nullptr;
-    int32_t *hub_list = nullptr;   // {node, degree} pairs of the nodes above every table size
-    int64_t hub_list_cap = 0;
-    uint32_t *hub_cnt = nullptr;   // per-wave slot counters of k_hub_edges (kept all-zero between edges)
-    int64_t hub_cnt_cap = 0;
+    // (all allocated on first use)
+    dcr::DevBuf<int32_t> giant_list;
+    dcr::DevBuf<int32_t> giant_pos;
+    dcr::DevBuf<uint32_t> giant_cnt;
+    dcr::DevBuf<int32_t> giant_acc;
+    dcr::DevBuf<int32_t> hub_list;  // {node, degree} pairs of the nodes above every table size
+    int64_t hub_list_cap = 0;       // in pairs: the array holds twice as many elements
+    dcr::DevBuf<uint32_t> hub_cnt;  // per-wave slot counters of k_hub_edges (kept all-zero between edges)
 
     // curvature-pass work lists (edge-centric kernels)
-    int32_t *work[dcr::NBINS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int64_t work_cap = 0;
+    dcr::DevBuf<int32_t> work[dcr::NBINS];
+    int64_t work_cap = 0;  // of each of the five lists; 0 behind a relayout, which drops them (they are sized by slots)
 
     // per-block (value, slot) minima and maxima left by the two-hop pass's closing kernel (k_h2_final) or by the one sweep for
     // both (launch_argext_both): the first minimum after the pass and the stale first maximum of the removal step then need no
     // sweep of their own.  Valid until the next edit (a removal moves values between slots) or pass.
-    void *ext_part = nullptr;     // Ext[2][EXT_PART_BLOCKS]: minima, then maxima
+    dcr::DevBuf<dcr::Ext> ext_part;  // [2][EXT_PART_BLOCKS]: minima, then maxima (allocated on first use)
     int ext_part_n = 0;
     bool ext_part_valid = false;
 
     dcr::SdrfScratch *sdrf = nullptr;        // every buffer of the SDRF step (dcr_sdrf.hip), created with the graph
     dcr::AnalysisState *analysis = nullptr;  // every buffer of the graph-analysis calls (dcr_analysis.h), created on first use
 
-    dcr::DevResult *dres = nullptr;  // device
-    dcr::DevResult *hres = nullptr;  // pinned host
+    dcr::DevBuf<dcr::DevResult> dres;     // device
+    dcr::PinnedBuf<dcr::DevResult> hres;  // its mirror in pinned host memory
 
     // side streams: the work bins of a curvature pass run concurrently
     hipStream_t side[dcr::NBINS - 1] = {nullptr, nullptr, nullptr, nullptr};
@@ -343,7 +382,11 @@ struct dcr_graph {
     double pass_ms_total = 0.0;
     int64_t pass_count = 0;
     bool profile = false;
+
+    dcr_graph() = default;
+    ~dcr_graph();  // dcr_graph.hip: drains the stream, then the SDRF scratch, the analysis state, streams and events; the buffers go with the members
 };
+static_assert(!std::is_copy_constructible_v<dcr_graph>, "dcr_graph owns its device buffers");
 
 namespace dcr {
 
@@ -358,7 +401,7 @@ void launch_mark_dirty(dcr_graph *g, int32_t u, int32_t v, int edit);  // flag t
 
 // dcr_sdrf.hip
 int sdrf_scratch_create(dcr_graph *g);    // g->sdrf and the two buffers every iteration needs
-void sdrf_scratch_destroy(dcr_graph *g);  // frees g->sdrf and what it holds
+void sdrf_scratch_destroy(dcr_graph *g);  // deletes g->sdrf and with it what it holds
 int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_t st = nullptr);  // st: default the library stream
 // the same from the per-block extrema of the last two-hop pass (g->ext_part_valid), without sweeping the edges again
 int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st = nullptr);
@@ -378,34 +421,11 @@ int launch_curvature_pass_nc(dcr_graph *g, int curv_type, bool incremental, bool
 // dcr_bfc_h2.hip
 int launch_curvature_pass_h2(dcr_graph *g);
 // what the edit kernels get: the weights they keep current, or null while there are none to keep
-inline int32_t *h2_kept_weight(dcr_graph *g) { return g->h2_weight_valid ? g->h2_weight : nullptr; }
+inline int32_t *h2_kept_weight(dcr_graph *g) { return g->h2_weight_valid ? g->h2_weight.p : nullptr; }
 bool h2_grow_pools(dcr_graph *g);
 int h2_weight_check(dcr_graph *g, int64_t *mismatches);  // -1: no kept weights; else the nodes whose kept W differs from the rows' 
 
 // dcr_analysis.hip
 void analysis_destroy(dcr_graph *g);  // frees g->analysis and what it holds
-
-template <typename T>
-int dev_alloc(T **p, int64_t count) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T));
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-        return DCR_ENOMEM;
-    }
-    *p = (T *)q;
-    return DCR_OK;
-}
-
-template <typename T>
-int dev_regrow(T **p, int64_t *cap, int64_t need) {
-    if (need <= *cap) return DCR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    int64_t nc = need + need / 4 + 64;
-    DCR_TRY(dev_alloc(p, nc));
-    *cap = nc;
-    return DCR_OK;
-}
 
 }  // namespace dcr

@@ -223,7 +223,7 @@ struct SketchRun {
         }
         DCR_HIP(hipMemcpyAsync(prob.ctl, h.data(), sizeof(SktCtl) * (size_t)ng, hipMemcpyHostToDevice, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));  // h is reused by the solve
-        hipLaunchKernelGGL(k_sketch_rhs, dim3((unsigned)L.nb_mv, (unsigned)ng), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, L.s, seed,
+        hipLaunchKernelGGL(k_sketch_rhs, dim3((unsigned)L.nb_mv, (unsigned)ng), dim3(256), 0, g->stream, plan, g->rowinfo.p, g->col.p, L.s, seed,
                            first, prob.ctl, c, b_out, L.part, L.gstride, L.pstride);
         DCR_HIP(hipGetLastError());
         return DCR_OK;
@@ -235,7 +235,7 @@ struct SketchRun {
         std::vector<int32_t> col((size_t)cap);
         std::vector<double> acc((size_t)cap);
         if (cap > 0) {
-            DCR_HIP(hipMemcpyAsync(col.data(), g->col, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost, g->stream));
+            DCR_HIP(hipMemcpyAsync(col.data(), g->col.p, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost, g->stream));
             DCR_HIP(hipMemcpyAsync(acc.data(), slot_acc, sizeof(double) * (size_t)cap, hipMemcpyDeviceToHost, g->stream));
         }
         DCR_HIP(hipStreamSynchronize(g->stream));
@@ -290,7 +290,7 @@ int dcr_resistance_sketch(dcr_graph *g, const dcr_sketch_opts *opts, double *out
             DCR_TRY(R.rhs(o.seed, first, ng, k, o.tol, h, nullptr));
             DCR_TRY(col_cg_solve(g, R.plan, R.L, ng, R.prob, h.data(), o.max_steps));
             if (R.slot_acc)
-                hipLaunchKernelGGL(k_sketch_accumulate, dim3((unsigned)R.L.nb_mv), dim3(256), 0, st, R.plan, g->rowinfo, g->col, R.L.z, ng,
+                hipLaunchKernelGGL(k_sketch_accumulate, dim3((unsigned)R.L.nb_mv), dim3(256), 0, st, R.plan, g->rowinfo.p, g->col.p, R.L.z, ng,
                                    R.L.gstride, R.slot_acc);
             if (P > 0)
                 hipLaunchKernelGGL(k_sketch_pairs, dim3(std::min(blocks_of(P * COL_CP), (unsigned)SKT_PAIR_BLOCKS)), dim3(256), 0, st, R.pair_u,

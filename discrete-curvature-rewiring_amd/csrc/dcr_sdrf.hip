@@ -879,89 +879,63 @@ __global__ void __launch_bounds__(256) k_draw_partial(const double *__restrict__
 // Every buffer the SDRF step needs beyond the graph itself: dcr_graph::sdrf, created with the graph (sdrf_scratch_create),
 // grown on demand.  Nothing outside this file looks inside.
 struct SdrfScratch {
-    ImpBuf imp{};                 // the improvement kernels' view: table {keys, posx, posy}[table_cap]; the row arrays c1, c2, clsx,
-    int64_t table_cap = 0;        // clsy, descx, descy, rowcount, rowoff [rows_cap]; adjbits [bits_cap]; st: one ImpStats
-    int64_t rows_cap = 0, bits_cap = 0;
+    // what the improvement kernels see as an ImpBuf (imp_view): the table, three arrays of one capacity; the row arrays, eight of
+    // one capacity; the admissibility bitmap; one ImpStats
+    DevBuf<int32_t> keys, posx, posy;
+    DevBuf<int32_t> c1, c2, rowcount, rowoff, clsx, clsy;
+    DevBuf<int4> descx, descy;
+    DevBuf<uint32_t> adjbits;
+    DevBuf<ImpStats> st;
     bool table_dirty = true;      // the table is not all-empty (fresh allocation, or a pipeline that did not reach its last kernel)
-    double *out = nullptr;        // compacted improvements and their candidate pairs [out_cap]
-    int32_t *ci = nullptr, *cj = nullptr;
-    int64_t out_cap = 0;
-    double *out_h = nullptr;      // pinned host mirrors
-    int32_t *ci_h = nullptr, *cj_h = nullptr;
-    int64_t out_h_cap = 0, cand_h_cap = 0;
+    DevBuf<double> out;           // compacted improvements and their candidate pairs, three arrays of one capacity
+    DevBuf<int32_t> ci, cj;
+    PinnedBuf<double> out_h;      // pinned host mirrors
+    PinnedBuf<int32_t> ci_h, cj_h;
     int64_t n = 0;                // candidates of the last pipeline that was read back
-    Ext *red_scratch = nullptr;   // [ARGEXT_BLOCKS] per-workgroup partial extrema, allocated on first use (red_scratch_of)
-    double *draw_bsum = nullptr;  // [DRAW_BLOCKS] device-side draw: block sums of exp(tau * improvement)
+    DevBuf<Ext> red_scratch;      // [ARGEXT_BLOCKS] per-workgroup partial extrema, allocated on first use (red_scratch_of)
+    DevBuf<double> draw_bsum;     // [DRAW_BLOCKS] device-side draw: block sums of exp(tau * improvement)
 };
 
 constexpr int ARGEXT_BLOCKS = 1024;  // (8192 blocks: 92 us instead of 33 on S100k, the per-block reduction dominates)
 
-template <typename... T>
-static void dev_release(T **...p) {  // frees each and leaves it null
-    ((*p ? (void)hipFree(*p) : (void)0), ...);
-    ((*p = nullptr), ...);
+static ImpBuf imp_view(const SdrfScratch &S) {  // the raw pointers as they are now: taken again after any growth
+    return ImpBuf{S.keys.p, S.posx.p, S.posy.p, S.c1.p, S.c2.p, S.clsx.p, S.clsy.p, S.descx.p, S.descy.p, S.rowcount.p, S.rowoff.p,
+                  S.adjbits.p, S.st.p};
 }
 
-// Buffers that share one capacity: nothing when need <= *cap; otherwise every one is freed and allocated again with `next`
-// elements.  A failure halfway leaves the whole group empty (null pointers, capacity 0), which the next call and the release
-// both accept.
-template <typename... T>
-static int regrow_group(int64_t *cap, int64_t need, int64_t next, T **...p) {
-    if (need <= *cap) return DCR_OK;
-    *cap = 0;
-    dev_release(p...);
-    int rc = DCR_OK;
-    ((rc = rc == DCR_OK ? dev_alloc(p, next) : rc), ...);
+// Buffers that share one capacity: nothing when `need` fits; otherwise every one is freed, then allocated again with `next`
+// elements.  A failure halfway leaves the whole group empty, which the next call accepts.
+template <typename First, typename... Rest>
+static int regrow_group(int64_t need, int64_t next, First &first, Rest &...rest) {
+    if (need <= first.cap) return DCR_OK;
+    first.free();
+    (rest.free(), ...);
+    int rc = first.alloc(next);
+    ((rc = rc == DCR_OK ? rest.alloc(next) : rc), ...);
     if (rc != DCR_OK) {
-        dev_release(p...);
-        return rc;
+        first.free();
+        (rest.free(), ...);
     }
-    *cap = next;
-    return DCR_OK;
-}
-
-template <typename T>
-static int pinned_regrow(T **p, int64_t *cap, int64_t need) {
-    if (need <= *cap) return DCR_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    int64_t nc = need + need / 4 + 1024;
-    void *q = nullptr;
-    hipError_t e = hipHostMalloc(&q, (size_t)nc * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        set_error(std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        return DCR_ENOMEM;
-    }
-    *p = (T *)q;
-    *cap = nc;
-    return DCR_OK;
+    return rc;
 }
 
 int sdrf_scratch_create(dcr_graph *g) {
     SdrfScratch *S = g->sdrf = new SdrfScratch();
-    DCR_TRY(dev_alloc(&S->imp.st, 1));
-    DCR_HIP(hipMemsetAsync(S->imp.st, 0xFF, sizeof(ImpStats), g->stream));  // (pos_x_in_y = -1)
-    DCR_TRY(dev_alloc(&S->draw_bsum, DRAW_BLOCKS));
+    DCR_TRY(S->st.alloc(1));
+    DCR_HIP(hipMemsetAsync(S->st.p, 0xFF, sizeof(ImpStats), g->stream));  // (pos_x_in_y = -1)
+    DCR_TRY(S->draw_bsum.alloc(DRAW_BLOCKS));
     return DCR_OK;
 }
 
 void sdrf_scratch_destroy(dcr_graph *g) {
-    SdrfScratch *S = g->sdrf;
-    if (!S) return;
-    ImpBuf &B = S->imp;
-    dev_release(&B.keys, &B.posx, &B.posy, &B.c1, &B.c2, &B.clsx, &B.clsy, &B.descx, &B.descy, &B.rowcount, &B.rowoff, &B.adjbits, &B.st,
-                &S->out, &S->ci, &S->cj, &S->red_scratch, &S->draw_bsum);
-    if (S->out_h) (void)hipHostFree(S->out_h);
-    if (S->ci_h) (void)hipHostFree(S->ci_h);
-    if (S->cj_h) (void)hipHostFree(S->cj_h);
-    delete S;
+    delete g->sdrf;
     g->sdrf = nullptr;
 }
 
 static int red_scratch_of(dcr_graph *g, Ext **out) {  // allocated on first use
     SdrfScratch &S = *g->sdrf;
-    if (!S.red_scratch) DCR_TRY(dev_alloc(&S.red_scratch, ARGEXT_BLOCKS));
-    *out = S.red_scratch;
+    if (!S.red_scratch.p) DCR_TRY(S.red_scratch.alloc(ARGEXT_BLOCKS));
+    *out = S.red_scratch.p;
     return DCR_OK;
 }
 
@@ -977,12 +951,12 @@ int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_
     g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
     Ext *partial = nullptr;
     DCR_TRY(red_scratch_of(g, &partial));
-    RowView vw{g->rowinfo, g->col, g->slot_row};
+    RowView vw{g->rowinfo.p, g->col.p, g->slot_row.p};
     const unsigned blocks = argext_blocks(g->cap_total);
-    hipLaunchKernelGGL(k_argext_edges, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv, want_max, excl_u, excl_v, g->dres,
+    hipLaunchKernelGGL(k_argext_edges, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv.p, want_max, excl_u, excl_v, g->dres.p,
                        partial);
     hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads((int)blocks)), 0, st, vw, (const Ext *)partial, (int)blocks,
-                       want_max, g->dres);
+                       want_max, g->dres.p);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
 }
@@ -990,16 +964,12 @@ int launch_argext(dcr_graph *g, int want_max, int excl_u, int excl_v, hipStream_
 // one sweep for both extrema; the partials stay valid until the next edit (as the closing kernel's of the two-hop pass)
 int launch_argext_both(dcr_graph *g, hipStream_t st, bool clear_dirty) {
     if (!st) st = g->stream;
-    if (!g->ext_part) {
-        Ext *p = nullptr;
-        DCR_TRY(dev_alloc(&p, 2 * EXT_PART_BLOCKS));
-        g->ext_part = p;
-    }
-    RowView vw{g->rowinfo, g->col, g->slot_row};
+    if (!g->ext_part.p) DCR_TRY(g->ext_part.alloc(2 * EXT_PART_BLOCKS));
+    RowView vw{g->rowinfo.p, g->col.p, g->slot_row.p};
     const unsigned blocks = argext_blocks(g->cap_total);
-    hipLaunchKernelGGL(k_argext_edges_both, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv, (Ext *)g->ext_part,
-                       (Ext *)g->ext_part + EXT_PART_BLOCKS, reinterpret_cast<unsigned *>(g->dirty),
-                       clear_dirty ? (int64_t)(g->n + 3) / 4 : (int64_t)0, g->dres);   // (the flags hold n + 4 bytes)
+    hipLaunchKernelGGL(k_argext_edges_both, dim3(blocks), dim3(256), 0, st, vw, g->cap_total, g->curv.p, g->ext_part.p,
+                       g->ext_part.p + EXT_PART_BLOCKS, reinterpret_cast<unsigned *>(g->dirty.p),
+                       clear_dirty ? (int64_t)(g->n + 3) / 4 : (int64_t)0, g->dres.p);   // (the flags hold n + 4 bytes)
     DCR_HIP(hipGetLastError());
     g->ext_part_n = (int)blocks;
     g->ext_part_valid = true;
@@ -1009,9 +979,9 @@ int launch_argext_both(dcr_graph *g, hipStream_t st, bool clear_dirty) {
 int launch_argext_from_parts(dcr_graph *g, int want_max, hipStream_t st) {
     if (!st) st = g->stream;
     g->amax_valid = false;  // the ext fields of the result block are about to be overwritten
-    RowView vw{g->rowinfo, g->col, g->slot_row};
-    const Ext *parts = (const Ext *)g->ext_part + (want_max ? EXT_PART_BLOCKS : 0);
-    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads(g->ext_part_n)), 0, st, vw, parts, g->ext_part_n, want_max, g->dres);
+    RowView vw{g->rowinfo.p, g->col.p, g->slot_row.p};
+    const Ext *parts = g->ext_part.p + (want_max ? EXT_PART_BLOCKS : 0);
+    hipLaunchKernelGGL(k_argext_final, dim3(1), dim3(nparts_threads(g->ext_part_n)), 0, st, vw, parts, g->ext_part_n, want_max, g->dres.p);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
 }
@@ -1031,8 +1001,8 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
         dy = g->am_dy;
     } else {
         int2 rxy[2];
-        DCR_HIP(hipMemcpyAsync(&rxy[0], g->rowinfo + x, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
-        DCR_HIP(hipMemcpyAsync(&rxy[1], g->rowinfo + y, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(&rxy[0], g->rowinfo.p + x, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(&rxy[1], g->rowinfo.p + y, sizeof(int2), hipMemcpyDeviceToHost, g->stream));
         DCR_HIP(hipStreamSynchronize(g->stream));
         dx = rxy[0].y;
         dy = rxy[1].y;
@@ -1050,31 +1020,30 @@ static int imp_enqueue(dcr_graph *g, int32_t x, int32_t y, int curv_type, int64_
     // scratch: the table exactly as large as asked for; the row arrays and the output doubled (a re-allocation is a device
     // synchronisation + two driver calls, ~0.3 ms — a few of them inside a 20-iteration measurement are 1-2 % of it)
     SdrfScratch &S = *g->sdrf;
-    ImpBuf &B = S.imp;
-    if (ts > S.table_cap) S.table_dirty = true;
-    DCR_TRY(regrow_group(&S.table_cap, ts, ts, &B.keys, &B.posx, &B.posy));
+    if (ts > S.keys.cap) S.table_dirty = true;
+    DCR_TRY(regrow_group(ts, ts, S.keys, S.posx, S.posy));
     const int64_t rows_need = (int64_t)(dx > dy ? dx : dy) + 2;
-    DCR_TRY(regrow_group(&S.rows_cap, rows_need, 2 * rows_need + 64, &B.c1, &B.c2, &B.rowcount, &B.rowoff, &B.clsx, &B.clsy, &B.descx,
-                         &B.descy));
-    if ((int64_t)rows * words > S.bits_cap) DCR_TRY(dev_regrow(&B.adjbits, &S.bits_cap, 2 * (int64_t)rows * words));
-    DCR_TRY(regrow_group(&S.out_cap, upper, 2 * upper + 1024, &S.out, &S.ci, &S.cj));
-    RowView vw{g->rowinfo, g->col, g->slot_row};
+    DCR_TRY(regrow_group(rows_need, 2 * rows_need + 64, S.c1, S.c2, S.rowcount, S.rowoff, S.clsx, S.clsy, S.descx, S.descy));
+    if ((int64_t)rows * words > S.adjbits.cap) DCR_TRY(S.adjbits.grow(2 * (int64_t)rows * words));
+    DCR_TRY(regrow_group(upper, 2 * upper + 1024, S.out, S.ci, S.cj));
+    const ImpBuf B = imp_view(S);
+    RowView vw{g->rowinfo.p, g->col.p, g->slot_row.p};
 
     // Four launches: insert both rows and leave a descriptor per member | per candidate row: classes, 4-cycle counters,
     // admissibility bitmap, and the stage's closing statistics + scan by its last workgroup | emit, classes B and C from the
     // bitmap (and leave the table empty) | the draw (its caller).  The table is only cleared here when the previous pipeline did not leave it empty.
     if (S.table_dirty) {
-        const unsigned blocks = (unsigned)((S.table_cap + 255) / 256 > 1024 ? 1024 : (S.table_cap + 255) / 256);
-        hipLaunchKernelGGL(k_imp_clear, dim3(blocks ? blocks : 1), dim3(256), 0, g->stream, B, S.table_cap);
+        const unsigned blocks = (unsigned)((S.keys.cap + 255) / 256 > 1024 ? 1024 : (S.keys.cap + 255) / 256);
+        hipLaunchKernelGGL(k_imp_clear, dim3(blocks ? blocks : 1), dim3(256), 0, g->stream, B, S.keys.cap);
     }
     S.table_dirty = true;  // (until k_imp_emit below has been enqueued)
     const int gi = (dx + dy + 255) / 256 > 0 ? (dx + dy + 255) / 256 : 1;
-    const Ext *amax_parts = amax_from_parts ? (const Ext *)g->ext_part + EXT_PART_BLOCKS : nullptr;
+    const Ext *amax_parts = amax_from_parts ? g->ext_part.p + EXT_PART_BLOCKS : nullptr;
     hipLaunchKernelGGL(k_imp_insert, dim3(gi + (amax_parts ? 1 : 0)), dim3(256), 0, g->stream, vw, B, x, y, mask, amax_parts,
-                       amax_parts ? g->ext_part_n : 0, g->dres);
+                       amax_parts ? g->ext_part_n : 0, g->dres.p);
     hipLaunchKernelGGL(k_imp_rows_count, dim3(rows), dim3(256), (size_t)words * 4, g->stream, vw, B, x, y, dy, mask, words,
-                       curv_type, g->dres);
-    hipLaunchKernelGGL(k_imp_emit, dim3(dx + words), dim3(256), 0, g->stream, B, x, y, dx, dy, words, curv_type, S.out, S.ci, S.cj, ts);
+                       curv_type, g->dres.p);
+    hipLaunchKernelGGL(k_imp_emit, dim3(dx + words), dim3(256), 0, g->stream, B, x, y, dx, dy, words, curv_type, S.out.p, S.ci.p, S.cj.p, ts);
     S.table_dirty = false;
     DCR_HIP(hipGetLastError());
     *upper_out = upper;
@@ -1092,14 +1061,14 @@ static int pick_candidate(dcr_graph *g, int64_t cand_index) {
     if (!g) DCR_FAIL(DCR_EINVAL, "null graph");
     if (cand_index < 0 || cand_index >= g->sdrf->n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
     DCR_HIP(hipSetDevice(g->device));
-    hipLaunchKernelGGL(k_pick_candidate, dim3(1), dim3(1), 0, g->stream, g->sdrf->ci, g->sdrf->cj, cand_index, g->dres);
+    hipLaunchKernelGGL(k_pick_candidate, dim3(1), dim3(1), 0, g->stream, g->sdrf->ci.p, g->sdrf->cj.p, cand_index, g->dres.p);
     return DCR_OK;
 }
 
 static void fill_added(const dcr_graph *g, int32_t out_added[2]) {  // after a synchronisation: the pair the tail added
     if (!out_added) return;
-    out_added[0] = g->hres->cand_i;
-    out_added[1] = g->hres->cand_j;
+    out_added[0] = g->hres.p->cand_i;
+    out_added[1] = g->hres.p->cand_j;
 }
 
 extern "C" {
@@ -1116,10 +1085,10 @@ int dcr_argext(dcr_graph *g, int want_max, int32_t excl_u, int32_t excl_v, int32
     }
     DCR_TRY(launch_argext(g, want_max, excl_u, excl_v));
     DCR_TRY(sync_result(g));
-    if (g->hres->ext_slot < 0) DCR_FAIL(DCR_ENOTFOUND, "graph has no (eligible) edges");
-    if (out_u) *out_u = g->hres->ext_u;
-    if (out_v) *out_v = g->hres->ext_v;
-    if (out_val) *out_val = g->hres->ext_val;
+    if (g->hres.p->ext_slot < 0) DCR_FAIL(DCR_ENOTFOUND, "graph has no (eligible) edges");
+    if (out_u) *out_u = g->hres.p->ext_u;
+    if (out_v) *out_v = g->hres.p->ext_v;
+    if (out_val) *out_val = g->hres.p->ext_val;
     return DCR_OK;
 }
 
@@ -1134,21 +1103,17 @@ int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want
     // one host sync: the result block and the values go out together; the candidate count is not known yet, so the
     // copy is sized by its upper bound (dx+1)(dy+1), which the real count nearly reaches on a sparse graph
     if (upper > 0 && out_improvement) {
-        DCR_TRY(pinned_regrow(&S.out_h, &S.out_h_cap, upper));
-        DCR_HIP(hipMemcpyAsync(S.out_h, S.out, sizeof(double) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        if (upper > S.out_h.cap) DCR_TRY(S.out_h.alloc(upper + upper / 4 + 1024));
+        DCR_HIP(hipMemcpyAsync(S.out_h.p, S.out.p, sizeof(double) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
     }
     if (upper > 0 && want_candidates) {
-        if (upper > S.cand_h_cap) {
-            int64_t c1 = S.cand_h_cap, c2 = S.cand_h_cap;
-            DCR_TRY(pinned_regrow(&S.ci_h, &c1, upper));
-            DCR_TRY(pinned_regrow(&S.cj_h, &c2, upper));
-            S.cand_h_cap = c1 < c2 ? c1 : c2;
-        }
-        DCR_HIP(hipMemcpyAsync(S.ci_h, S.ci, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
-        DCR_HIP(hipMemcpyAsync(S.cj_h, S.cj, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        if (upper > S.ci_h.cap) DCR_TRY(S.ci_h.alloc(upper + upper / 4 + 1024));
+        if (upper > S.cj_h.cap) DCR_TRY(S.cj_h.alloc(upper + upper / 4 + 1024));
+        DCR_HIP(hipMemcpyAsync(S.ci_h.p, S.ci.p, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
+        DCR_HIP(hipMemcpyAsync(S.cj_h.p, S.cj.p, sizeof(int32_t) * (size_t)upper, hipMemcpyDeviceToHost, g->stream));
     }
     DCR_TRY(sync_result(g));
-    const int64_t n = g->hres->n_cand;
+    const int64_t n = g->hres.p->n_cand;
     if (n < 0 || n > upper) DCR_FAIL(DCR_ESTATE, "candidate count outside its bound");
     S.n = n;
     *n_out = n;
@@ -1160,9 +1125,9 @@ int dcr_improvements(dcr_graph *g, int32_t x, int32_t y, int curv_type, int want
         else DCR_TRY(launch_argext(g, 1, -1, -1));
         g->amax_valid = true;
     }
-    if (out_improvement) *out_improvement = n > 0 ? S.out_h : nullptr;
-    if (out_ci) *out_ci = (n > 0 && want_candidates) ? S.ci_h : nullptr;
-    if (out_cj) *out_cj = (n > 0 && want_candidates) ? S.cj_h : nullptr;
+    if (out_improvement) *out_improvement = n > 0 ? S.out_h.p : nullptr;
+    if (out_ci) *out_ci = (n > 0 && want_candidates) ? S.ci_h.p : nullptr;
+    if (out_cj) *out_cj = (n > 0 && want_candidates) ? S.cj_h.p : nullptr;
     return DCR_OK;
 }
 
@@ -1174,12 +1139,12 @@ int dcr_improvements_argmax(dcr_graph *g, int64_t *out_index) {
     Ext *partial = nullptr;
     DCR_TRY(red_scratch_of(g, &partial));
     const int64_t blocks = (n + 255) / 256 > ARGEXT_BLOCKS ? ARGEXT_BLOCKS : (n + 255) / 256;
-    hipLaunchKernelGGL(k_argmax_array, dim3((unsigned)blocks), dim3(256), 0, g->stream, g->sdrf->out, n, (const DevResult *)nullptr,
+    hipLaunchKernelGGL(k_argmax_array, dim3((unsigned)blocks), dim3(256), 0, g->stream, g->sdrf->out.p, n, (const DevResult *)nullptr,
                        partial);
-    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, (int)blocks, g->dres);
+    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, (int)blocks, g->dres.p);
     DCR_HIP(hipGetLastError());
     DCR_TRY(sync_result(g));
-    *out_index = g->hres->imp_argmax;
+    *out_index = g->hres.p->imp_argmax;
     return DCR_OK;
 }
 
@@ -1187,8 +1152,8 @@ int dcr_candidate_at(dcr_graph *g, int64_t index, int32_t *out_i, int32_t *out_j
     if (!g || !out_i || !out_j) DCR_FAIL(DCR_EINVAL, "null argument");
     if (index < 0 || index >= g->sdrf->n) DCR_FAIL(DCR_EINVAL, "candidate index out of range");
     DCR_HIP(hipSetDevice(g->device));
-    DCR_HIP(hipMemcpyAsync(out_i, g->sdrf->ci + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    DCR_HIP(hipMemcpyAsync(out_j, g->sdrf->cj + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_i, g->sdrf->ci.p + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    DCR_HIP(hipMemcpyAsync(out_j, g->sdrf->cj.p + index, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     DCR_HIP(hipStreamSynchronize(g->stream));
     return DCR_OK;
 }
@@ -1260,16 +1225,16 @@ static int tail_enqueue(dcr_graph *g, const TailCall &tc, bool first_attempt) {
 // after a synchronisation that brought the result block over: host-side bookkeeping and outputs (out_max_val: the stale
 // maximum, for the callers whose result block still holds it — a pass behind the tail overwrites the ext fields)
 static void tail_finish(dcr_graph *g, const TailCall &tc, int32_t out_removed[2], double *out_max_val) {
-    if (tc.adding && g->hres->add_status == 0) {
+    if (tc.adding && g->hres.p->add_status == 0) {
         g->n_edges++;
         g->max_deg_bound++;
     }
     int32_t ru = -1, rv = -1;
     if (tc.do_remove) {
-        ru = g->hres->removed_u;
-        rv = g->hres->removed_v;
+        ru = g->hres.p->removed_u;
+        rv = g->hres.p->removed_v;
         if (ru >= 0) g->n_edges--;
-        if (out_max_val) *out_max_val = g->hres->ext_slot >= 0 ? g->hres->ext_val : 0.0;
+        if (out_max_val) *out_max_val = g->hres.p->ext_slot >= 0 ? g->hres.p->ext_val : 0.0;
     }
     if (out_removed) {
         out_removed[0] = ru;
@@ -1295,17 +1260,17 @@ static int run_tail(dcr_graph *g, const TailCall &tc, const TailPass *pass, int3
         } else {
             DCR_TRY(sync_result(g));
         }
-        if (g->hres->add_status != 1) {
+        if (g->hres.p->add_status != 1) {
             if (rc == DCR_OK) break;
             // the edit did happen on the device (the result block is from a completed synchronisation unless the failure was
             // the HIP call itself): keep the host's edge count and degree bound in step before reporting
-            if (rc != DCR_EHIP && g->hres->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
+            if (rc != DCR_EHIP && g->hres.p->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
             return rc;
         }
         if (attempt == 1) DCR_FAIL(DCR_ECAPACITY, "row still full after relayout");
         DCR_TRY(relayout(g));
     }
-    if (g->hres->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
+    if (g->hres.p->add_status != 3) tail_finish(g, tc, out_removed, out_max_val);
     return DCR_OK;
 }
 
@@ -1385,12 +1350,12 @@ int dcr_sdrf_iteration_device_draw(dcr_graph *g, int32_t x, int32_t y, int curv_
         Ext *partial = nullptr;
         DCR_TRY(red_scratch_of(g, &partial));
         // (red_scratch is free again: the stale arg-max beside the pipeline has been joined above)
-        hipLaunchKernelGGL(k_argmax_array, dim3(256), dim3(256), 0, g->stream, S.out, (int64_t)0, (const DevResult *)g->dres, partial);
-        hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, 256, g->dres);
-        hipLaunchKernelGGL(k_draw_from_argmax, dim3(1), dim3(1), 0, g->stream, S.ci, S.cj, g->dres);
+        hipLaunchKernelGGL(k_argmax_array, dim3(256), dim3(256), 0, g->stream, S.out.p, (int64_t)0, (const DevResult *)g->dres.p, partial);
+        hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, (const Ext *)partial, 256, g->dres.p);
+        hipLaunchKernelGGL(k_draw_from_argmax, dim3(1), dim3(1), 0, g->stream, S.ci.p, S.cj.p, g->dres.p);
     } else {
-        hipLaunchKernelGGL(k_draw_partial, dim3(DRAW_BLOCKS), dim3(256), 0, g->stream, S.out, S.ci, S.cj, g->dres, tau, uniform,
-                           S.draw_bsum, margin_scale >= 1.0 ? margin_scale : 1.0, S.imp.st);
+        hipLaunchKernelGGL(k_draw_partial, dim3(DRAW_BLOCKS), dim3(256), 0, g->stream, S.out.p, S.ci.p, S.cj.p, g->dres.p, tau, uniform,
+                           S.draw_bsum.p, margin_scale >= 1.0 ? margin_scale : 1.0, S.st.p);
     }
     const auto nothing_edited = [&]() {
         if (out_removed) out_removed[0] = out_removed[1] = -1;
@@ -1406,18 +1371,18 @@ int dcr_sdrf_iteration_device_draw(dcr_graph *g, int32_t x, int32_t y, int curv_
     //  pass then finds nothing flagged, and the verdict comes over with the pass's result.)
     if (!incremental) {
         DCR_TRY(sync_result(g));
-        S.n = *out_n_cand = g->hres->n_cand;
-        *out_status = g->hres->draw_status;
-        if (g->hres->draw_status != 0) return nothing_edited();
+        S.n = *out_n_cand = g->hres.p->n_cand;
+        *out_status = g->hres.p->draw_status;
+        if (g->hres.p->draw_status != 0) return nothing_edited();
     }
     TailCall tc;
     DCR_TRY(tail_prepare(g, -2, -2, do_remove, removal_bound, &tc));
     const TailPass pass{curv_type, incremental, out_u, out_v, out_val};
     DCR_TRY(run_tail(g, tc, &pass, out_removed, nullptr));
-    S.n = *out_n_cand = g->hres->n_cand;
-    *out_status = g->hres->draw_status;
-    if (g->hres->draw_status != 0 || g->hres->add_status == 3) {  // nothing was edited; the pass ran on the same graph
-        if (g->hres->draw_status == 0) DCR_FAIL(DCR_ESTATE, "device draw: edit skipped without a draw status");
+    S.n = *out_n_cand = g->hres.p->n_cand;
+    *out_status = g->hres.p->draw_status;
+    if (g->hres.p->draw_status != 0 || g->hres.p->add_status == 3) {  // nothing was edited; the pass ran on the same graph
+        if (g->hres.p->draw_status == 0) DCR_FAIL(DCR_ESTATE, "device draw: edit skipped without a draw status");
         return nothing_edited();
     }
     fill_added(g, out_added);

@@ -316,7 +316,7 @@ struct SpecRun {
     }
     // Lanczos step j: alpha[j], beta[j], and column j + 1 when there is room for it
     void step(int j, int m) const {
-        hipLaunchKernelGGL(k_spec_matvec, dim3(row_grid<SpecRows>(plan)), dim3(256), 0, g->stream, plan, g->rowinfo, g->col, col(j), z, s, w,
+        hipLaunchKernelGGL(k_spec_matvec, dim3(row_grid<SpecRows>(plan)), dim3(256), 0, g->stream, plan, g->rowinfo.p, g->col.p, col(j), z, s, w,
                            A->spc_part.p, ticket, alpha + j);
         // The deflation comes LAST.  Each column carries a rounding-size component along the k_C; Gram-Schmidt hands w the sum
         // of those, weighted by alpha and beta, and with nothing behind it that component obeys the Lanczos recurrence of an
@@ -426,7 +426,7 @@ int spectral_solve(dcr_graph *g, const dcr_spectral_opts *opts, dcr_spectral_res
         DCR_HIP(hipMemcpyAsync(R.order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, g->stream));
     DCR_HIP(hipMemcpyAsync(A.spc_chunks.p, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, g->stream));
     inv_sqrt_degree(g, R.s);
-    hipLaunchKernelGGL(k_spec_start, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo, R.w, n, (uint64_t)0, o.seed);
+    hipLaunchKernelGGL(k_spec_start, dim3(blocks_of(n)), dim3(256), 0, g->stream, g->rowinfo.p, R.w, n, (uint64_t)0, o.seed);
     R.first_column();
     DCR_HIP(hipGetLastError());
 

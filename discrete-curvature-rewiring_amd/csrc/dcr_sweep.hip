@@ -383,7 +383,7 @@ static int sweep_run(dcr_graph *g, const SweepPlan &P, int definition, const Row
     int32_t *d_in = P.diff, *d_lo = P.diff + n, *d_hi = P.diff + 2 * n;
     DCR_HIP(hipMemsetAsync(P.diff, 0, sizeof(int32_t) * 3 * (size_t)n, st));
     if (g->n_edges > 0)
-        hipLaunchKernelGGL(k_sweep_edges, dim3(row_grid<SweepRows>(rows)), dim3(256), 0, st, rows, g->rowinfo, g->col, P.rank, d_in, d_lo, d_hi);
+        hipLaunchKernelGGL(k_sweep_edges, dim3(row_grid<SweepRows>(rows)), dim3(256), 0, st, rows, g->rowinfo.p, g->col.p, P.rank, d_in, d_lo, d_hi);
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)P.nb_diff, 3), dim3(256), 0, st, P.diff, n, n, P.nb_diff, P.part, P.boff,
                        P.ctl + SW_CTL_TICKETS);
     hipLaunchKernelGGL(k_scan_apply<true>, dim3((unsigned)P.nb_diff, 3), dim3(256), 0, st, P.diff, n, n, P.nb_diff, P.boff);
