@@ -21,11 +21,20 @@
 //
 // expf is the library's (not a fast-math variant), every multiply-add an explicit fmaf (the file is built -ffp-contract=off), the
 // closing acc / den and the backward's w / den are true divisions.
+//
+// Attention dropout (the DROP = true instantiations; DROP = false is the code above and never reads GatDrop): the keep weight
+// k in {0, scale} of slot `pos` of the target CSR under head h multiplies alpha AFTER the softmax, so m and den run over every
+// slot and D = <dO, O> stays as it is.  No mask is stored: the decision is element E = h * S8 + pos (S8 = nnz rounded up to 8)
+// of the dropout stream of include/dcr.h, and both sweeps draw it again.  One Philox call holds the 8 slots pos & ~7 .. of one
+// head: the forward's slot-order sweep draws once per 8 slots (KeepDraw), the expand, which meets positions in the order of
+// the transposed pattern, once per slot.  The stream offset o = offset + *offset_dev is resolved by the gather, which leaves
+// it in a device word for the expand: a replayed graph whose counter moved on between the two still redraws the same mask.
 #include <cmath>
 #include <cstdint>
 #include <initializer_list>
 #include <type_traits>
 #include "dcr_internal.h"
+#include "dcr_philox.h"
 #include "dcr_spmm_pieces.h"
 
 namespace dcr {
@@ -36,6 +45,34 @@ static_assert(GAT_LONG == SPMM_LONG, "deal_rows parks rows by SPMM_LONG");
 constexpr int GAT_MAX_HEADS = 64;
 
 __device__ inline float leaky(float pre, float slope) { return pre > 0.f ? pre : slope * pre; }
+
+// what the DROP = true kernels read (a DROP = false kernel is passed one and touches none of it)
+struct GatDrop {
+    uint64_t seed = 0, offset = 0;
+    const int64_t *offset_dev = nullptr;   // gather: the caller's call counter, may be null; expand: the word the gather wrote
+    int64_t *offset_used = nullptr;        // gather: receives o = offset + *offset_dev
+    int64_t s8 = 0;                        // nnz rounded up to a multiple of 8: the stream's elements per head
+    uint32_t threshold = 0;                // kept: 16-bit draw >= threshold
+    float scale = 1.f;                     // (float)(1 / (1 - p))
+};
+
+// The keep decision of element E = h * s8 + pos: call E >> 3, word E & 3, half (E >> 2) & 1 (philox_quad16's rule).  The four
+// words of the last call stay in registers (named, not indexed: no scratch), so a sweep in slot order draws once per 8 slots.
+struct KeepDraw {
+    uint64_t call = ~(uint64_t)0;   // (no element reaches call 2^64 - 1)
+    uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+    __device__ bool keep(uint64_t E, uint64_t o, uint64_t seed, uint32_t threshold) {
+        if ((E >> 3) != call) {
+            call = E >> 3;
+            uint32_t r[4];
+            philox4x32_10(call, o, seed, r);
+            r0 = r[0]; r1 = r[1]; r2 = r[2]; r3 = r[3];
+        }
+        const uint32_t lo = (E & 1) ? r1 : r0, hi = (E & 1) ? r3 : r2;
+        const uint32_t word = (E & 2) ? hi : lo;
+        return ((word >> ((uint32_t)((E >> 2) & 1) * 16u)) & 0xFFFFu) >= threshold;
+    }
+};
 
 // deal_rows numbers the group `sub` of workgroup b as i = sub * gridDim + b (Deal::row).  Here the unit of that group is
 // b * G + sub: the heads of one row (units row * H .. row * H + H - 1) sit in neighbouring groups of one workgroup.
@@ -75,11 +112,14 @@ __device__ inline float group_sum(float p) {
 // ---- forward --------------------------------------------------------------------------------------------------------------
 // O[i, h·C + :] = Σ_slots w·Z[col, h·C + :] / den, w = expf(e − m), e = leaky(s_src[col, h] + s_dst[i, h]), m = max e, den = Σ w.
 // rec[(i·H + h)·2 ..] = (m, den); a row without slots: O = 0, rec = (0, 1).
-template <int LPH, int VEC>
+// DROP: O = (Σ_kept slots w·Z / den)·scale — den over every slot, the numerator's fmaf for kept slots only, in slot order from
+// 0.f, a true division, then one multiply; rec as without.
+template <int LPH, int VEC, bool DROP>
 __global__ void __launch_bounds__(256) k_gat_gather(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                      const float *__restrict__ Z, const float *__restrict__ s_src,
                                                      const float *__restrict__ s_dst, float *__restrict__ O, float *__restrict__ rec,
-                                                     int64_t n, int H, int C, int64_t ldz, int64_t lds, int64_t ldo, float slope) {
+                                                     int64_t n, int H, int C, int64_t ldz, int64_t lds, int64_t ldo, float slope,
+                                                     GatDrop drop) {
     using D = Deal<LPH>;
     __shared__ alignas(16) float red[256 * VEC];   // (sum_groups reads it VEC floats at a time)
     __shared__ float wave_max[4];
@@ -87,15 +127,23 @@ __global__ void __launch_bounds__(256) k_gat_gather(const int64_t *__restrict__ 
     const int f0 = sl * VEC;
     const bool mine = f0 < C;   // (C / VEC <= LPH: the lanes past the head's last piece only help with the scores)
     const int64_t n_units = n * H;
+    uint64_t o = 0;
+    if constexpr (DROP) {
+        o = drop.offset + (drop.offset_dev ? (uint64_t)*drop.offset_dev : 0);
+        if (blockIdx.x == 0 && threadIdx.x == 0) *drop.offset_used = (int64_t)o;
+    }
     // sub-sweep 2 of one unit over slots e0, e0 + stride, ...: den and acc in slot order
     auto sweep2 = [&](const float *zh, const float *ss, float sd, float m, int64_t e0, int64_t e1, int64_t stride, float &den,
-                      float (&acc)[VEC]) {
+                      float (&acc)[VEC], uint64_t head0) {   // (head0 = h * s8: element 0 of the head's stream; DROP only)
         float s[D::U], b[D::U][VEC];
         bool ok[D::U];
+        int64_t at[D::U];
+        KeepDraw draw;
         slot_batches<D::U>(
             e0, e1, stride,
             [&](int u, int64_t e, bool on) {
                 ok[u] = on;
+                if constexpr (DROP) at[u] = e;
                 const int64_t c = on ? col[e] : 0;
                 s[u] = on ? ss[c * lds] : 0.f;
                 if (on && mine) {
@@ -109,16 +157,22 @@ __global__ void __launch_bounds__(256) k_gat_gather(const int64_t *__restrict__ 
                 if (!ok[u]) return;
                 const float w = expf(leaky(s[u] + sd, slope) - m);
                 den += w;
+                if constexpr (DROP) {
+                    if (!draw.keep(head0 + (uint64_t)at[u], o, drop.seed, drop.threshold)) return;
+                }
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) acc[q] = fmaf(w, b[u][q], acc[q]);
             });
     };
     auto close = [&](int64_t unit, float *dst, const float (&acc)[VEC], float m, float den, bool any) {
         if (mine) {
-            float o[VEC];
+            float v[VEC];
 #pragma unroll
-            for (int q = 0; q < VEC; ++q) o[q] = any ? acc[q] / den : 0.f;
-            store_vec<VEC>(dst, o);
+            for (int q = 0; q < VEC; ++q) {
+                v[q] = any ? acc[q] / den : 0.f;
+                if constexpr (DROP) v[q] *= drop.scale;
+            }
+            store_vec<VEC>(dst, v);
         }
         if (sl == 0) {
             rec[unit * 2] = any ? m : 0.f;
@@ -145,7 +199,7 @@ __global__ void __launch_bounds__(256) k_gat_gather(const int64_t *__restrict__ 
 #pragma unroll
             for (int k = 1; k < LPH; k <<= 1) m = fmaxf(m, __shfl_xor(m, k, LPH));
             float den = 0.f, acc[VEC] = {};
-            sweep2(Z + (int64_t)h * C + f0, ss, sd, m, e0, e1, 1, den, acc);
+            sweep2(Z + (int64_t)h * C + f0, ss, sd, m, e0, e1, 1, den, acc, (uint64_t)h * (uint64_t)drop.s8);
             close(unit, O + row * ldo + (int64_t)h * C + f0, acc, m, den, e1 > e0);
         },
         [&](int64_t i, int64_t e0, int64_t e1) {
@@ -163,7 +217,7 @@ __global__ void __launch_bounds__(256) k_gat_gather(const int64_t *__restrict__ 
             __syncthreads();   // (wave_max is free again after the barriers of sum_groups below)
             m = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
             float den_p[1] = {0.f}, acc[VEC] = {};
-            sweep2(Z + (int64_t)h * C + f0, ss, sd, m, e0 + sub, e1, D::G, den_p[0], acc);
+            sweep2(Z + (int64_t)h * C + f0, ss, sd, m, e0 + sub, e1, D::G, den_p[0], acc, (uint64_t)h * (uint64_t)drop.s8);
             float den = 1.f;
             sum_groups<LPH, 1>(red, sub == 0, den_p, [&](const float (&sum)[1]) { den = sum[0]; });
             sum_groups<LPH, VEC>(red, sub == 0, acc,
@@ -199,19 +253,22 @@ __global__ void __launch_bounds__(256) k_gat_rowdot(const float *__restrict__ O,
 // Row j of the transposed pattern, head h; per slot (target i = col_t, position pos = slot_t in the target CSR):
 //   pre = s_src[j,h] + s_dst[i,h]; α = expf(leaky(pre) − m_i) / den_i; t = <dO[i,h,:], Z[j,h,:]>
 //   g = α·(t − D_i)·(pre > 0 ? 1 : slope) -> gbuf[pos·H + h];  dZ[j,h,:] = Σ fmaf(α, dO[i,h,:], ·);  dS_src[j,h] = Σ g
-template <int LPH, int VEC>
+// DROP: k = scale or 0 from (pos, h), drawn once per slot:  g = α·(k·t − D)·(pre > 0 ? 1 : slope);  dZ = Σ_kept fmaf(α·k, dO, ·)
+template <int LPH, int VEC, bool DROP>
 __global__ void __launch_bounds__(256) k_gat_expand(const int64_t *__restrict__ rowptr_t, const int32_t *__restrict__ col_t,
                                                      const int64_t *__restrict__ slot_t, const float *__restrict__ Z,
                                                      const float *__restrict__ s_src, const float *__restrict__ dO,
                                                      const float4 *__restrict__ rec4, float *__restrict__ dZ,
                                                      float *__restrict__ dS_src, float *__restrict__ gbuf, int64_t n, int H, int C,
-                                                     int64_t ldz, int64_t lds, int64_t ldo, float slope) {
+                                                     int64_t ldz, int64_t lds, int64_t ldo, float slope, GatDrop drop) {
     using D = Deal<LPH>;
     __shared__ alignas(16) float red[256 * VEC];   // (sum_groups reads it VEC floats at a time)
     const int sub = D::sub(), sl = D::sl();
     const int f0 = sl * VEC;
     const bool mine = f0 < C;
     const int64_t n_units = n * H;
+    uint64_t o = 0;
+    if constexpr (DROP) o = (uint64_t)*drop.offset_dev;
     auto sweep = [&](int h, const float (&z)[VEC], float ssj, int64_t e0, int64_t e1, int64_t stride, float &gs, float (&acc)[VEC]) {
         float4 r[D::U];
         float d[D::U][VEC];
@@ -240,9 +297,21 @@ __global__ void __launch_bounds__(256) k_gat_expand(const int64_t *__restrict__ 
                 if (!ok[u]) return;
                 const float pre = ssj + r[u].x;
                 const float a = expf(leaky(pre, slope) - r[u].y) / r[u].z;
-                const float g = a * (t - r[u].w) * (pre > 0.f ? 1.f : slope);
+                float g;
+                if constexpr (DROP) {
+                    KeepDraw draw;
+                    const bool kept = draw.keep((uint64_t)h * (uint64_t)drop.s8 + (uint64_t)pos[u], o, drop.seed, drop.threshold);
+                    g = a * ((kept ? drop.scale * t : 0.f) - r[u].w) * (pre > 0.f ? 1.f : slope);
+                    if (kept) {
+                        const float ak = a * drop.scale;
 #pragma unroll
-                for (int q = 0; q < VEC; ++q) acc[q] = fmaf(a, d[u][q], acc[q]);
+                        for (int q = 0; q < VEC; ++q) acc[q] = fmaf(ak, d[u][q], acc[q]);
+                    }
+                } else {
+                    g = a * (t - r[u].w) * (pre > 0.f ? 1.f : slope);
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) acc[q] = fmaf(a, d[u][q], acc[q]);
+                }
                 gs += g;
                 if (sl == 0) gbuf[pos[u] * H + h] = g;
             });
@@ -348,28 +417,44 @@ static int gat_check(int64_t n, int64_t H, int64_t C, int64_t ldz, int64_t lds, 
     return DCR_OK;
 }
 
-extern "C" int dcr_gat_gather_f32_dev(const int64_t *rowptr, const int32_t *col, const float *Z, const float *s_src,
-                                      const float *s_dst, float *O, float *rec, int64_t n, int64_t H, int64_t C, int64_t ldz,
-                                      int64_t lds, int64_t ldo, double negative_slope, void *hip_stream) {
+// p, nnz and the output word of the DROP = true entry points -> GatDrop (threshold and scale as every dropout kernel forms them)
+static int gat_drop_args(int64_t nnz, double p, uint64_t seed, uint64_t offset, const int64_t *offset_dev, int64_t *offset_used,
+                         GatDrop &drop) {
+    if (!(p >= 0.0 && p < 1.0)) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (attention dropout p outside [0, 1))");
+    if (nnz < 0) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (nnz < 0)");
+    drop.seed = seed;
+    drop.offset = offset;
+    drop.offset_dev = offset_dev;
+    drop.offset_used = offset_used;
+    drop.s8 = (nnz + 7) / 8 * 8;
+    drop.threshold = dropout_threshold16(p);
+    drop.scale = (float)(1.0 / (1.0 - p));
+    return DCR_OK;
+}
+
+template <bool DROP>
+static int gat_gather(const int64_t *rowptr, const int32_t *col, const float *Z, const float *s_src, const float *s_dst, float *O,
+                      float *rec, int64_t n, int64_t H, int64_t C, int64_t ldz, int64_t lds, int64_t ldo, double negative_slope,
+                      void *hip_stream, const GatDrop &drop) {
     if (!rowptr || !col || !Z || !s_src || !s_dst || !O || !rec) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (null pointer)");
     DCR_TRY(gat_check(n, H, C, ldz, lds, ldo));
     if (n == 0) return DCR_OK;
     hipStream_t st = (hipStream_t)hip_stream;
     const bool fits = pick_lph_vec((int)C, {ldz, ldo}, {Z, O}, [&](auto L, auto V) {
         constexpr int LPH = decltype(L)::value, VEC = decltype(V)::value;
-        hipLaunchKernelGGL((k_gat_gather<LPH, VEC>), Deal<LPH>::grid(n * H), dim3(256), 0, st, rowptr, col, Z, s_src, s_dst, O, rec, n,
-                           (int)H, (int)C, ldz, lds, ldo, (float)negative_slope);
+        hipLaunchKernelGGL((k_gat_gather<LPH, VEC, DROP>), Deal<LPH>::grid(n * H), dim3(256), 0, st, rowptr, col, Z, s_src, s_dst, O,
+                           rec, n, (int)H, (int)C, ldz, lds, ldo, (float)negative_slope, drop);
     });
     if (!fits) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (C above 64 lanes of the widest access the operands allow)");
     DCR_HIP(hipGetLastError());
     return DCR_OK;
 }
 
-extern "C" int dcr_gat_expand_f32_dev(const int64_t *rowptr, const int64_t *rowptr_t, const int32_t *col_t, const int64_t *slot_t,
-                                      const float *Z, const float *s_src, const float *s_dst, const float *O, const float *dO,
-                                      const float *rec, float *dZ, float *dS_src, float *dS_dst, float *work_rec, float *work_g,
-                                      int64_t n, int64_t H, int64_t C, int64_t ldz, int64_t lds, int64_t ldo, double negative_slope,
-                                      void *hip_stream) {
+template <bool DROP>
+static int gat_expand(const int64_t *rowptr, const int64_t *rowptr_t, const int32_t *col_t, const int64_t *slot_t, const float *Z,
+                      const float *s_src, const float *s_dst, const float *O, const float *dO, const float *rec, float *dZ,
+                      float *dS_src, float *dS_dst, float *work_rec, float *work_g, int64_t n, int64_t H, int64_t C, int64_t ldz,
+                      int64_t lds, int64_t ldo, double negative_slope, void *hip_stream, const GatDrop &drop) {
     if (!rowptr || !rowptr_t || !col_t || !slot_t || !Z || !s_src || !s_dst || !O || !dO || !rec || !dZ || !dS_src || !dS_dst ||
         !work_rec || !work_g)
         DCR_FAIL(DCR_EINVAL, "bad GAT arguments (null pointer)");
@@ -381,11 +466,50 @@ extern "C" int dcr_gat_expand_f32_dev(const int64_t *rowptr, const int64_t *rowp
         constexpr int LPH = decltype(L)::value, VEC = decltype(V)::value;
         hipLaunchKernelGGL((k_gat_rowdot<LPH, VEC>), Deal<LPH>::grid(n * H), dim3(256), 0, st, O, dO, s_dst, rec, (float4 *)work_rec, n,
                            (int)H, (int)C, lds, ldo);
-        hipLaunchKernelGGL((k_gat_expand<LPH, VEC>), Deal<LPH>::grid(n * H), dim3(256), 0, st, rowptr_t, col_t, slot_t, Z, s_src, dO,
-                           (const float4 *)work_rec, dZ, dS_src, work_g, n, (int)H, (int)C, ldz, lds, ldo, (float)negative_slope);
+        hipLaunchKernelGGL((k_gat_expand<LPH, VEC, DROP>), Deal<LPH>::grid(n * H), dim3(256), 0, st, rowptr_t, col_t, slot_t, Z, s_src,
+                           dO, (const float4 *)work_rec, dZ, dS_src, work_g, n, (int)H, (int)C, ldz, lds, ldo, (float)negative_slope,
+                           drop);
     });
     if (!fits) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (C above 64 lanes of the widest access the operands allow)");
     hipLaunchKernelGGL(k_gat_dst_sum, Deal<DST_LPR>::grid(n), dim3(256), 0, st, rowptr, (const float *)work_g, dS_dst, n, (int)H, lds);
     DCR_HIP(hipGetLastError());
     return DCR_OK;
+}
+
+extern "C" int dcr_gat_gather_f32_dev(const int64_t *rowptr, const int32_t *col, const float *Z, const float *s_src,
+                                      const float *s_dst, float *O, float *rec, int64_t n, int64_t H, int64_t C, int64_t ldz,
+                                      int64_t lds, int64_t ldo, double negative_slope, void *hip_stream) {
+    return gat_gather<false>(rowptr, col, Z, s_src, s_dst, O, rec, n, H, C, ldz, lds, ldo, negative_slope, hip_stream, GatDrop{});
+}
+
+extern "C" int dcr_gat_gather_drop_f32_dev(const int64_t *rowptr, const int32_t *col, const float *Z, const float *s_src,
+                                           const float *s_dst, float *O, float *rec, int64_t n, int64_t H, int64_t C, int64_t ldz,
+                                           int64_t lds, int64_t ldo, double negative_slope, void *hip_stream, int64_t nnz, double p,
+                                           uint64_t seed, uint64_t offset, const int64_t *offset_dev, int64_t *offset_used_dev) {
+    if (!offset_used_dev) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (null pointer)");
+    GatDrop drop;
+    DCR_TRY(gat_drop_args(nnz, p, seed, offset, offset_dev, offset_used_dev, drop));
+    return gat_gather<true>(rowptr, col, Z, s_src, s_dst, O, rec, n, H, C, ldz, lds, ldo, negative_slope, hip_stream, drop);
+}
+
+extern "C" int dcr_gat_expand_f32_dev(const int64_t *rowptr, const int64_t *rowptr_t, const int32_t *col_t, const int64_t *slot_t,
+                                      const float *Z, const float *s_src, const float *s_dst, const float *O, const float *dO,
+                                      const float *rec, float *dZ, float *dS_src, float *dS_dst, float *work_rec, float *work_g,
+                                      int64_t n, int64_t H, int64_t C, int64_t ldz, int64_t lds, int64_t ldo, double negative_slope,
+                                      void *hip_stream) {
+    return gat_expand<false>(rowptr, rowptr_t, col_t, slot_t, Z, s_src, s_dst, O, dO, rec, dZ, dS_src, dS_dst, work_rec, work_g, n, H,
+                             C, ldz, lds, ldo, negative_slope, hip_stream, GatDrop{});
+}
+
+extern "C" int dcr_gat_expand_drop_f32_dev(const int64_t *rowptr, const int64_t *rowptr_t, const int32_t *col_t,
+                                           const int64_t *slot_t, const float *Z, const float *s_src, const float *s_dst,
+                                           const float *O, const float *dO, const float *rec, float *dZ, float *dS_src, float *dS_dst,
+                                           float *work_rec, float *work_g, int64_t n, int64_t H, int64_t C, int64_t ldz, int64_t lds,
+                                           int64_t ldo, double negative_slope, void *hip_stream, int64_t nnz, double p, uint64_t seed,
+                                           const int64_t *offset_used_dev) {
+    if (!offset_used_dev) DCR_FAIL(DCR_EINVAL, "bad GAT arguments (null pointer)");
+    GatDrop drop;
+    DCR_TRY(gat_drop_args(nnz, p, seed, 0, offset_used_dev, nullptr, drop));
+    return gat_expand<true>(rowptr, rowptr_t, col_t, slot_t, Z, s_src, s_dst, O, dO, rec, dZ, dS_src, dS_dst, work_rec, work_g, n, H, C,
+                            ldz, lds, ldo, negative_slope, hip_stream, drop);
 }

@@ -154,6 +154,8 @@ SIGNATURES = {
     'dcr_spmm_csr_typed_expand_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _vp]),
     'dcr_gat_gather_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f64, _vp]),
     'dcr_gat_expand_f32_dev': (ctypes.c_int, [_vp] * 15 + [_i64] * 6 + [_f64, _vp]),
+    'dcr_gat_gather_drop_f32_dev': (ctypes.c_int, [_vp] * 7 + [_i64] * 6 + [_f64, _vp, _i64, _f64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
+    'dcr_gat_expand_drop_f32_dev': (ctypes.c_int, [_vp] * 15 + [_i64] * 6 + [_f64, _vp, _i64, _f64, ctypes.c_uint64, _vp]),
     'dcr_relu_dropout_bits_words': (ctypes.c_int, [_i64, _i64p]),
     'dcr_relu_dropout_fwd_f32_dev': (ctypes.c_int, [_vp, _vp, _vp, _i64, _f64, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'dcr_relu_dropout_fwd_f32_ctr_dev': (ctypes.c_int, [_vp, _vp, _vp, _i64, _f64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),

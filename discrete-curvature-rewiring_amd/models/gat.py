@@ -14,6 +14,12 @@ gradients.  The heads are concatenated (``concat=True``) or averaged, then the b
 Evaluated as ONE GEMM X·[Wᵀ | Wᵀ·att_src | Wᵀ·att_dst] (Z and both scores) and ONE sweep of the CSR by target
 (``dcr_gat_gather_f32_dev``, csrc/dcr_gat.hip); the backward pass is one sweep of the CSR of the transposed pattern between a
 row-local kernel and a closing sum (``dcr_gat_expand_f32_dev``).  No floating-point atomics: two runs train the same weights.
+
+Attention dropout (``attn_dropout = p``, in training): a keep weight k_ij,h in {0, 1 / (1 − p)} multiplies α AFTER the softmax, as
+torch_geometric does, so m and den still run over every slot:  O[i,h,:] = Σ_slots k_ij,h·α_ij,h·Z[j,h,:].  No mask is stored: a
+keep decision is a pure function of (seed, stream offset, slot position in the target CSR, head) in the Philox stream of the
+GCN dropout kernels (include/dcr.h), and the forward sweep and the transposed sweep each draw it again
+(``dcr_gat_gather_drop_f32_dev``, ``dcr_gat_expand_drop_f32_dev``).
 """
 from typing import List
 
@@ -33,10 +39,18 @@ class AttnCSR:
     ``col_t`` int32 targets) and the slot map ``slot_t`` (int64): the position in the target CSR of each slot of the source CSR.
     Inside a row of either the slots keep the order of ``edge_index``'s columns, an added self-loop last."""
 
-    def __init__(self, rowptr, col, rowptr_t, col_t, slot_t, num_nodes):
+    def __init__(self, rowptr, col, rowptr_t, col_t, slot_t, num_nodes, nnz=None):
         self.rowptr, self.col = rowptr, col
         self.rowptr_t, self.col_t, self.slot_t = rowptr_t, col_t, slot_t
         self.num_nodes = num_nodes
+        self._nnz = nnz
+
+    @property
+    def nnz(self):
+        """The number of slots, ``rowptr[n]``, as a host integer (read back once where the constructor was not given it)."""
+        if self._nnz is None:
+            self._nnz = int(self.rowptr[-1])
+        return self._nnz
 
 
 def _rowptr(row, n):
@@ -60,12 +74,15 @@ def gat_csr(edge_index, num_nodes, add_self_loops=True):
     col, col_t = src.to(torch.int32), tgt[slot_t].to(torch.int32)
     if perm.numel() == 0:
         col, col_t, slot_t = col.new_zeros(1), col_t.new_zeros(1), slot_t.new_zeros(1)
-    return AttnCSR(_rowptr(tgt, n), col.contiguous(), _rowptr(src, n), col_t.contiguous(), slot_t.contiguous(), n)
+    return AttnCSR(_rowptr(tgt, n), col.contiguous(), _rowptr(src, n), col_t.contiguous(), slot_t.contiguous(), n,
+                   nnz=int(perm.numel()))
 
 
-def _aggregate_torch(z, s_src, s_dst, csr, slope):
+def _aggregate_torch(z, s_src, s_dst, csr, slope, keep=None, p=0.0, training=False):
     """The rule in plain differentiable torch ops, any float dtype: the chain of index_select, scatter-max, exp, scatter-add,
-    divide and scatter-add (the maximum is a constant of the softmax, so it is detached)."""
+    divide and scatter-add (the maximum is a constant of the softmax, so it is detached).  ``keep`` [nnz, H], values 0 or
+    1 / (1 − p) per (slot of the target CSR, head), multiplies α.  Without one, ``training`` and 0 < p < 1 draw it with
+    ``torch.rand``: the same distribution as the HIP kernels' mask, NOT their Philox stream (two backends, two masks)."""
     n, heads = csr.num_nodes, s_src.shape[1]
     e_count = int(csr.rowptr[-1])
     rows, cols = _slot_rows(csr.rowptr), csr.col[:e_count].long()
@@ -76,6 +93,10 @@ def _aggregate_torch(z, s_src, s_dst, csr, slope):
     w = torch.exp(e - m[rows])
     den = torch.zeros((n, heads), dtype=z.dtype, device=z.device).index_add(0, rows, w)
     alpha = w / den[rows]
+    if keep is None and training and 0.0 < p < 1.0:
+        keep = (torch.rand(alpha.shape, device=z.device) >= p).to(z.dtype) / (1.0 - p)
+    if keep is not None:
+        alpha = alpha * keep
     zh = z.reshape(n, heads, -1)
     out = torch.zeros_like(zh).index_add(0, rows, alpha[:, :, None] * zh[cols])
     return out.reshape(n, -1)
@@ -106,10 +127,13 @@ def _packed(z, s_src, s_dst):
 
 
 class _GatAggregate(torch.autograd.Function):
-    """O = gather(Z, s_src, s_dst); (dZ, dS_src, dS_dst) = expand(dO) on the transposed pattern."""
+    """O = gather(Z, s_src, s_dst); (dZ, dS_src, dS_dst) = expand(dO) on the transposed pattern.  With 0 < p < 1 both take the
+    attention-dropout entry points: seed ``torch.initial_seed()``, offset 0 plus the device's dropout call counter
+    (``models.gcn._dropout_counter``, stepped after the launch as ``_ReluDropoutFn`` does); the one word the gather resolves
+    the stream offset into is all the backward keeps of the mask."""
 
     @staticmethod
-    def forward(ctx, z, s_src, s_dst, csr, slope):
+    def forward(ctx, z, s_src, s_dst, csr, slope, p=0.0):
         for t in (z, s_src, s_dst):
             _require_hip(t)
         z, s_src, s_dst = _row_major(z), _row_major(s_src), _row_major(s_dst)
@@ -120,9 +144,18 @@ class _GatAggregate(torch.autograd.Function):
             raise ValueError(f'Z {tuple(z.shape)}, s_src {tuple(s_src.shape)}, s_dst {tuple(s_dst.shape)} for {n} nodes')
         out = torch.empty((n, z.shape[1]), dtype=torch.float32, device=z.device)
         rec = torch.empty((max(n * heads, 1), 2), dtype=torch.float32, device=z.device)
-        _lib.check(_lib.lib().dcr_gat_gather_f32_dev(csr.rowptr.data_ptr(), csr.col.data_ptr(), z.data_ptr(), s_src.data_ptr(),
-                                                     s_dst.data_ptr(), out.data_ptr(), rec.data_ptr(), n, heads, z.shape[1] // heads,
-                                                     z.stride(0), s_src.stride(0), out.stride(0), float(slope), _stream(z)))
+        args = (csr.rowptr.data_ptr(), csr.col.data_ptr(), z.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(), out.data_ptr(),
+                rec.data_ptr(), n, heads, z.shape[1] // heads, z.stride(0), s_src.stride(0), out.stride(0), float(slope), _stream(z))
+        ctx.p, ctx.seed, ctx.offset_used = float(p), 0, None
+        if ctx.p > 0.0:
+            ctr = _gcn._dropout_counter(z.device)
+            ctx.seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+            ctx.offset_used = torch.empty(1, dtype=torch.int64, device=z.device)
+            _lib.check(_lib.lib().dcr_gat_gather_drop_f32_dev(*args, csr.nnz, ctx.p, ctx.seed, 0, ctr.data_ptr(),
+                                                              ctx.offset_used.data_ptr()))
+            ctr.add_(1)
+        else:
+            _lib.check(_lib.lib().dcr_gat_gather_f32_dev(*args))
         ctx.save_for_backward(z, s_src, s_dst, out, rec)
         ctx.csr, ctx.slope = csr, float(slope)
         return out
@@ -144,37 +177,50 @@ class _GatAggregate(torch.autograd.Function):
             ds_dst = torch.empty((n, s_src.stride(0)), dtype=torch.float32, device=z.device)[:, :heads]
         work_rec = torch.empty((max(n * heads, 1), 4), dtype=torch.float32, device=z.device)
         work_g = torch.empty(max(int(csr.col_t.numel()) * heads, 1), dtype=torch.float32, device=z.device)
-        _lib.check(_lib.lib().dcr_gat_expand_f32_dev(csr.rowptr.data_ptr(), csr.rowptr_t.data_ptr(), csr.col_t.data_ptr(),
-                                                     csr.slot_t.data_ptr(), z.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
-                                                     out.data_ptr(), grad_out.data_ptr(), rec.data_ptr(), dz.data_ptr(),
-                                                     ds_src.data_ptr(), ds_dst.data_ptr(), work_rec.data_ptr(), work_g.data_ptr(), n,
-                                                     heads, width // heads, z.stride(0), s_src.stride(0), width, ctx.slope,
-                                                     _stream(z)))
-        return dz, ds_src, ds_dst, None, None
+        args = (csr.rowptr.data_ptr(), csr.rowptr_t.data_ptr(), csr.col_t.data_ptr(), csr.slot_t.data_ptr(), z.data_ptr(),
+                s_src.data_ptr(), s_dst.data_ptr(), out.data_ptr(), grad_out.data_ptr(), rec.data_ptr(), dz.data_ptr(),
+                ds_src.data_ptr(), ds_dst.data_ptr(), work_rec.data_ptr(), work_g.data_ptr(), n, heads, width // heads, z.stride(0),
+                s_src.stride(0), width, ctx.slope, _stream(z))
+        if ctx.p > 0.0:
+            _lib.check(_lib.lib().dcr_gat_expand_drop_f32_dev(*args, csr.nnz, ctx.p, ctx.seed, ctx.offset_used.data_ptr()))
+        else:
+            _lib.check(_lib.lib().dcr_gat_expand_f32_dev(*args))
+        return dz, ds_src, ds_dst, None, None, None
 
 
-def gat_aggregate(z, s_src, s_dst, csr, negative_slope=0.2):
+def gat_aggregate(z, s_src, s_dst, csr, negative_slope=0.2, attn_dropout=0.0, training=False):
     """O [n, H·C] of the rule above from Z [n, H·C] and the scores [n, H] each, differentiable in all three.  On the 'hip'
     backend (``models.gcn.set_aggregate_backend``) the kernels of csrc/dcr_gat.hip, and a CPU tensor raises; 'torch' is the
-    plain-torch path of the CPU tests (any float dtype), never chosen automatically."""
+    plain-torch path of the CPU tests (any float dtype), never chosen automatically.  ``attn_dropout`` in [0, 1) acts only
+    with ``training``: on 'hip' the kernels redraw the mask from the Philox stream in both passes, on 'torch' the mask comes
+    from ``torch.rand`` (another stream, the same distribution)."""
+    p = float(attn_dropout)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'attn_dropout must be in [0, 1), got {attn_dropout}')
+    if not training:
+        p = 0.0
     if _gcn._AGG_BACKEND == 'hip':
-        return _GatAggregate.apply(z, s_src, s_dst, csr, negative_slope)
-    return _aggregate_torch(z, s_src, s_dst, csr, negative_slope)
+        return _GatAggregate.apply(z, s_src, s_dst, csr, negative_slope, p)
+    return _aggregate_torch(z, s_src, s_dst, csr, negative_slope, p=p, training=training)
 
 
 class GATConv(torch.nn.Module):
     """One attention layer.  Parameters: ``lin.weight`` [H·C, in] (glorot), ``att_src`` and ``att_dst`` [1, H, C] (glorot),
     ``bias`` [H·C], or [C] with ``concat=False`` (zeros).  These are torch_geometric's names and shapes as far as they are
     known here; torch_geometric is not installed where this was written, so the interchange of state dicts was NOT checked.
-    ``dropout`` on the attention coefficients is not implemented: a non-zero value raises.  ``edge_attr`` is not read: the
+    Dropout on the attention coefficients is ``attn_dropout`` (in training, after the softmax, as torch_geometric's
+    ``dropout``); the keyword ``dropout`` itself is not taken and a non-zero value raises.  ``edge_attr`` is not read: the
     layer's own learned weights take the place of edge weights."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
-                 bias=True):
+                 bias=True, attn_dropout=0.0):
         super().__init__()
         if dropout != 0.0:
-            raise NotImplementedError('GATConv: dropout on the attention coefficients is not implemented '
-                                      '(only dropout=0.0; dropout between the layers is GAT\'s own argument)')
+            raise NotImplementedError('GATConv: dropout on the attention coefficients is the keyword attn_dropout '
+                                      '(dropout= is not taken here; dropout between the layers is GAT\'s own argument)')
+        if not 0.0 <= float(attn_dropout) < 1.0:
+            raise ValueError(f'attn_dropout must be in [0, 1), got {attn_dropout}')
+        self.attn_dropout = float(attn_dropout)
         if not 1 <= int(heads) <= MAX_HEADS:
             raise ValueError(f'heads must be in [1, {MAX_HEADS}], got {heads}')
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
@@ -228,7 +274,8 @@ class GATConv(torch.nn.Module):
         h, c = self.heads, self.out_channels
         csr = self.attn_csr(edge_index, x.shape[0])
         zs = x @ self.operand()
-        out = gat_aggregate(zs[:, :h * c], zs[:, h * c:h * c + h], zs[:, h * c + h:h * c + 2 * h], csr, self.negative_slope)
+        out = gat_aggregate(zs[:, :h * c], zs[:, h * c:h * c + h], zs[:, h * c + h:h * c + 2 * h], csr, self.negative_slope,
+                            self.attn_dropout, self.training)
         if not self.concat:
             out = out.view(-1, h, c).mean(1)
         return out if self.bias is None else out + self.bias
@@ -236,18 +283,22 @@ class GATConv(torch.nn.Module):
 
 class GAT(torch.nn.Module):
     """``GCN``'s surface (models/gcn.py) on ``GATConv`` layers: ``heads`` heads of each hidden width, concatenated, ELU and
-    dropout between the layers; the last layer has ``output_heads`` heads, averaged.  Dropout on the input features and on the
-    attention coefficients (the paper applies both) is not part of the model.  Weight decay on the first layer only."""
+    dropout between the layers; the last layer has ``output_heads`` heads, averaged.  The paper's two other dropouts are
+    off by default: ``attn_dropout`` on the attention coefficients of every layer, ``input_dropout`` (a stock
+    ``torch.nn.Dropout``) on the input features before the first layer; the paper trains with 0.6 for both.  Weight decay on
+    the first layer only."""
 
-    def __init__(self, dataset, hidden: List[int] = [8], heads: int = 8, output_heads: int = 1, dropout: float = 0.6):
+    def __init__(self, dataset, hidden: List[int] = [8], heads: int = 8, output_heads: int = 1, dropout: float = 0.6,
+                 attn_dropout: float = 0.0, input_dropout: float = 0.0):
         super().__init__()
         widths = [dataset.data.x.shape[1], *[w * heads for w in hidden]]
-        layers = [GATConv(w_in, w_out, heads=heads) for w_in, w_out in zip(widths, hidden)]
-        layers.append(GATConv(widths[-1], dataset.num_classes, heads=output_heads, concat=False))
+        layers = [GATConv(w_in, w_out, heads=heads, attn_dropout=attn_dropout) for w_in, w_out in zip(widths, hidden)]
+        layers.append(GATConv(widths[-1], dataset.num_classes, heads=output_heads, concat=False, attn_dropout=attn_dropout))
         self.layers = ModuleList(layers)
         self.reg_params = list(self.layers[0].parameters())
         self.non_reg_params = [p for conv in list(self.layers)[1:] for p in conv.parameters()]
         self.dropout = Dropout(p=dropout)
+        self.input_dropout = Dropout(p=input_dropout)
         self.act_fn = ELU()
 
     def reset_parameters(self):
@@ -256,6 +307,8 @@ class GAT(torch.nn.Module):
 
     def forward(self, data):
         x = data.x
+        if self.input_dropout.p > 0.0:
+            x = self.input_dropout(x)
         for i, conv in enumerate(self.layers):
             x = conv(x, data.edge_index)
             if i < len(self.layers) - 1:

@@ -643,6 +643,32 @@ int dcr_gat_expand_f32_dev(const int64_t *rowptr_dev, const int64_t *rowptr_t_de
                            const float *O_dev, const float *dO_dev, const float *rec_dev, float *dZ_dev, float *dS_src_dev,
                            float *dS_dst_dev, float *work_rec_dev, float *work_g_dev, int64_t n, int64_t H, int64_t C,
                            int64_t ldz, int64_t lds, int64_t ldo, double negative_slope, void *hip_stream);
+/* Attention dropout (torch_geometric's GATConv(dropout = p) in training): the keep weight k in {0, scale},
+ * scale = float32(1 / (1 - p)), multiplies alpha AFTER the softmax, so m and den run over every slot:
+ *   O[i,h,:]  = ((sum_kept slots w * Z[col,h,:]) / den[i,h]) * scale        rec as without dropout
+ *   g_ij,h    = alpha * (k * <dO[i,h,:], Z[j,h,:]> - D[i,h]) * (pre > 0 ? 1 : negative_slope)
+ *   dZ[j,h,:] = sum_kept i (alpha * k) * dO[i,h,:]                          D, dS_src and dS_dst as without dropout
+ * The stream is the one of the dropout section below, and NO mask is stored: with nnz = rowptr[n] and S8 = nnz rounded up to
+ * a multiple of 8, the slot at position pos of the target CSR under head h is element E = h * S8 + pos of an (H * S8)-element
+ * tensor under that rule (call E >> 3, word E & 3, half (E >> 2) & 1, key seed, o = offset + *offset_dev; kept when the 16-bit
+ * draw >= min(floor(p * 65536), 65535)), so the host's decisions are dropout_ref.decisions(H * S8, p, seed, o) reshaped
+ * [H, S8] and cut to [:, :nnz].  The gather redraws it per 8 slots, the expand per slot through slot_t.
+ * The gather resolves o (offset_dev may be null: o = offset) and writes it to offset_used_dev [1]; the expand reads o from
+ * that word, so a replayed hipGraph whose counter has moved on between the two still applies the forward's mask.
+ * nnz must be rowptr[n] (it only sizes S8; nothing on the device checks it).  p outside [0, 1), nnz < 0, a null
+ * offset_used_dev: DCR_EINVAL.  At p = 0 every slot is kept and scale is 1: the bits of the entry points above.
+ * Every other argument, limit and order: as dcr_gat_gather_f32_dev / dcr_gat_expand_f32_dev. */
+int dcr_gat_gather_drop_f32_dev(const int64_t *rowptr_dev, const int32_t *col_dev, const float *Z_dev, const float *s_src_dev,
+                                const float *s_dst_dev, float *O_dev, float *rec_dev, int64_t n, int64_t H, int64_t C,
+                                int64_t ldz, int64_t lds, int64_t ldo, double negative_slope, void *hip_stream, int64_t nnz,
+                                double p, uint64_t seed, uint64_t offset, const int64_t *offset_dev /* nullable */,
+                                int64_t *offset_used_dev);
+int dcr_gat_expand_drop_f32_dev(const int64_t *rowptr_dev, const int64_t *rowptr_t_dev, const int32_t *col_t_dev,
+                                const int64_t *slot_t_dev, const float *Z_dev, const float *s_src_dev, const float *s_dst_dev,
+                                const float *O_dev, const float *dO_dev, const float *rec_dev, float *dZ_dev, float *dS_src_dev,
+                                float *dS_dst_dev, float *work_rec_dev, float *work_g_dev, int64_t n, int64_t H, int64_t C,
+                                int64_t ldz, int64_t lds, int64_t ldo, double negative_slope, void *hip_stream, int64_t nnz,
+                                double p, uint64_t seed, const int64_t *offset_used_dev);
 
 /* ---- GCN weight gradient on the matrix cores (device pointers, caller's stream)
  * C[M x N] = A^T * B with A [K x M] and B [K x N] row-major fp32 (lda/ldb/ldc in

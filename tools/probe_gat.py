@@ -3,8 +3,11 @@ models/gat.py on the GPU (index_select, scatter-max, exp, scatter-add, divide, s
 and (b) dcr_spmm_csr_f32_dev at width H·C on the same CSR, which gathers the same operand rows and is the floor.
 
 Shapes: the bench graph (100,000 nodes, 999,900 edges: 2,099,800 slots with both directions and the self-loops) at
-(H, C) = (8, 8) and (1, 64), and a Cora-sized graph at (8, 8).  The variants run interleaved in rounds; each figure is the median
-over the rounds of the mean call time of one round, with the smallest and largest round.
+(H, C) = (8, 8), (1, 64) and (1, 7), and a Cora-sized graph at (8, 8) and (1, 7) (the two layers of the paper's model).  The
+``attn_dropout 0.6`` rows are the same calls in training with attention dropout: the keep bits are redrawn from the Philox
+stream in both sweeps (per 8 slots in the gather, per slot in the expand), nothing is stored; each such call also steps the
+device's call counter (one more tiny launch).  The variants run interleaved in rounds, the p = 0 and p = 0.6 paths in the
+same process; each figure is the median over the rounds of the mean call time of one round, with the smallest and largest round.
 
     python tools/probe_gat.py [--rounds 9] [--reps 20] [--out FILE.json]
 """
@@ -44,7 +47,7 @@ def main():
         raise SystemExit('probe_gat.py measures on the MI355X: no GPU here')
     dev = torch.device('cuda', 0)
     results = []
-    for name, nodes, m, shapes in (('bench graph', 100000, 10, ((8, 8), (1, 64))), ('Cora-sized', 2485, 2, ((8, 8),))):
+    for name, nodes, m, shapes in (('bench graph', 100000, 10, ((8, 8), (1, 64), (1, 7))), ('Cora-sized', 2485, 2, ((8, 8), (1, 7)))):
         ei, n = synthetic.powerlaw_graph(nodes, m, seed=12345)
         csr = gat_csr(torch.from_numpy(ei).to(dev), n)
         ones = torch.ones(csr.col.numel(), dtype=torch.float32, device=dev)
@@ -59,14 +62,16 @@ def main():
                 _lib.check(_lib.lib().dcr_spmm_csr_f32_dev(csr.rowptr.data_ptr(), csr.col.data_ptr(), ones.data_ptr(), z.data_ptr(),
                                                            out_spmm.data_ptr(), n, heads * c, heads * c, heads * c, None, 0, _stream(z)))
 
-            def fwd_bwd(fn):
-                out = fn(*leaves, csr, 0.2)
+            def fwd_bwd(fn, *extra):
+                out = fn(*leaves, csr, 0.2, *extra)
                 torch.autograd.grad(out, leaves, d_out)
 
             variants = {
                 'hip forward': lambda: gat_aggregate(z, s_src, s_dst, csr),
                 'torch forward': lambda: _aggregate_torch(z, s_src, s_dst, csr, 0.2),
                 'hip forward+backward': lambda: fwd_bwd(gat_aggregate),
+                'hip forward, attn_dropout 0.6': lambda: gat_aggregate(z, s_src, s_dst, csr, 0.2, 0.6, True),
+                'hip forward+backward, attn_dropout 0.6': lambda: fwd_bwd(gat_aggregate, 0.6, True),
                 'torch forward+backward': lambda: fwd_bwd(_aggregate_torch),
                 'spmm floor': spmm,
             }
