@@ -1545,18 +1545,181 @@ __device__ inline void h2_stream(const View &g, const H2Tasks tk, H2Alloc &al, i
     if (qn > 0) h2_drain<L1, EXS, PHASE, PARTS>(t, sc, qn, tk, al, -1, ls, part, nparts);  // (after the loop: a wave's last batches may be empty; PHASE 1 only)
 }
 
+// ---- class M's row-mask path ------------------------------------------------------------------------------------------------
+// A unit of at most 128 rows whose pieces fit the registers (h2_node_fast) is settled the way the wave classes settle a node
+// (h2s_node), with the workgroup where that function has a wave and 128-bit masks where it has 64-bit ones: sweep B's flagged
+// entries are looked up in a small exact table; a hit on a member of N(u) sets the bit of that member's position in row u in the
+// adjacency mask of the entry's row, any other key gets the entry's row into its row mask and the occurrence {slot, row} onto a
+// candidate list; step C is one pass over that list, c = |rows(w) \ adj(row)| - 1.  No item list in device memory, no counting
+// sort, no probe of the edge set, no third sweep: per entry the block path cost nine times what a wave class pays.
+// The arrays alias what the block path keeps in LDS and this path does not use: the row masks lie in the counting table's keys,
+// the exact keys, the adjacency masks and the per-row results in its counts, the candidate list in B1 (dead once sweep A is
+// through).  Sizes are typical, not worst case (tools/count_rowmask_keys.py, profiles/h2_rowmask_ab.txt): a unit whose table or
+// list fills up publishes nothing here — h2_rows_unit returns false — and the block path takes it: its own tables cleared and seeded,
+// then its sweep B, behind the sweep A the two paths share (B2 is as that sweep left it; see h2_node_fast).
+constexpr int H2_ROWS_MAX = 128;   // rows of a unit: four 32-bit mask words
+constexpr int H2_ROWS_EXS = 1024;  // slots of the exact table: {key, four mask words}
+constexpr int H2_ROWS_CL = 2048;   // candidate occurrences: slot | row << 16
+// diagnostic (tools/h2_rowmask_coverage.py): class-M units published by the row-mask path / handed over to the block path
+__device__ unsigned h2_rows_units[2];
+
+// h2s_find_or_insert with the walk cut at H2_WALK slots: a longer one counts as "full".  (Walked to the end, as the wave classes'
+// small tables are, the one unit of the bench graph with more keys than slots took 1,024 dependent LDS reads per missing key and
+// round, and units near a full table not many fewer: the iteration was a fifth slower than without the path,
+// profiles/h2_rowmask_ab.txt.)
+__device__ inline int h2r_find_or_insert(unsigned *exkey, unsigned w) {
+    unsigned s = h2s_home<H2_ROWS_EXS>(w);
+#pragma unroll 1
+    for (int walk = 0; walk < H2_WALK; ++walk) {
+        const unsigned e = exkey[s];
+        if ((e & ~H2_NBR) == w && e != H2_EMPTY) return (int)s;
+        if (e == H2_EMPTY) {
+            const unsigned old = atomicCAS(&exkey[s], H2_EMPTY, w);
+            if (old == H2_EMPTY || (old & ~H2_NBR) == w) return (int)s;
+        }
+        s = (s + 1) & (unsigned)(H2_ROWS_EXS - 1);
+    }
+    return -1;
+}
+
+// From sweep B on.  w, meta: the pieces of this wave's rows as h2_node_fast holds them after sweep A; i, k: this lane's position in
+// row u and its member of N(u).  The caller has cleared the arrays below, seeded the members of N(u) into the exact table (*t.full
+// set if one found no slot) and run sweep A, which is the block path's own; every thread is past it.
+template <int L1, int EXS, int NW, int NP>
+__device__ inline bool h2_rows_unit(const View &g, int u, int2 ru, int i, int k, int P, const int4 (&w)[NP], unsigned long long (&meta)[NP],
+                                    const H2Tab t, H2Scratch *sc, uint4 *rec) {
+    static_assert(EXS >= 4 * H2_ROWS_EXS, "the row masks fit the counting table's keys");
+    static_assert(EXS / 2 >= H2_ROWS_EXS + 6 * H2_ROWS_MAX, "the exact keys, adjacency masks and row results fit its counts");
+    static_assert((1 << L1) / 32 >= H2_ROWS_CL, "the candidate list fits B1");
+    static_assert(64 * NW >= H2_ROWS_MAX && H2_ROWS_MAX <= 256 && H2_ROWS_EXS <= 65536, "a row per lane; 8-bit rows, 16-bit slots");
+    const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    constexpr int NT = 64 * NW;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned *exm = t.key;                           // [slot][4] candidate: the rows that hold it; member of N(u): word 0 = its position in row u
+    unsigned *exkey = t.cnt;                         // [slot] candidate key, or a member of N(u) | H2_NBR
+    unsigned *adj = t.cnt + H2_ROWS_EXS;             // [row][4] the rows adjacent to it = triangle partners of edge {u, v_row}
+    int *pos = reinterpret_cast<int *>(adj + 4 * H2_ROWS_MAX), *mx = pos + H2_ROWS_MAX;
+    unsigned *cl = t.b1;                             // (from sweep B on)
+    int *cln = t.wsum;                               // candidate occurrences so far (counts past the capacity)
+    bool full = *t.full != 0;  // (a member of N(u) found no slot in the exact table)
+    // sweep B: the flagged entries are queued by lane (see h2s_node) and settled against the exact table 64 at a time
+    int qn = 0;  // uniform over the wave
+    auto drain = [&]() {
+        h2_wave_sync();
+        for (int base = 0; base < qn; base += 64) {
+            const int j = base + lane;
+            bool cand = false;
+            int slot = -1, row = 0;
+            if (j < qn) {
+                row = sc->qr[j];
+                slot = h2r_find_or_insert(exkey, sc->qw[j]);
+                if (slot < 0) {
+                    full = true;
+                } else if (row >= ru.y) {
+                    row_ok(g, make_int2(-1, row), 47, u, ru.y);  // an entry of a row the node does not have: report, the pass fails
+                } else if (exkey[slot] & H2_NBR) {  // a member of N(u) in row `row`: rows `row` and exm[slot] are adjacent
+                    const unsigned x = exm[4 * slot];
+                    if (x >= (unsigned)ru.y) row_ok(g, make_int2(-1, (int)x), 48, u, ru.y);  // a position row u does not have: the same
+                    else atomicOr(&adj[4 * row + (int)(x >> 5)], 1u << (x & 31u));
+                } else {
+                    atomicOr(&exm[4 * slot + (row >> 5)], 1u << (row & 31));
+                    cand = true;
+                }
+            }
+            const unsigned long long m = __ballot(cand);
+            if (m == 0ull) continue;  // uniform
+            int first = 0;
+            if (lane == 0) first = atomicAdd(cln, __popcll(m));
+            first = __shfl(first, 0);
+            if (cand) {
+                const int idx = first + __popcll(m & below);
+                if (idx < H2_ROWS_CL) cl[idx] = (unsigned)slot | ((unsigned)row << 16);
+                else full = true;
+            }
+        }
+        h2_wave_sync();
+        qn = 0;
+    };
+    {
+        // (the flags of a piece's entries ride in bits 48-51 of its meta word, free in every piece: an array of their own raised the
+        //  kernel's spills)
+        constexpr int FL = 48;
+        int nfl = 0;  // this lane's flagged entries
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            if (64 * q >= P) continue;  // uniform
+            const unsigned kk[4] = {(unsigned)w[q].x, (unsigned)w[q].y, (unsigned)w[q].z, (unsigned)w[q].w};
+            // (where u sits in the row, the reverse slot of edge {u, v_row}, found while the pieces are at hand)
+            const unsigned isu = h2_eq4(kk, (unsigned)u) & (unsigned)meta[q] & 0xFu;
+            if (isu) sc->rowRev[(int)((meta[q] >> 8) & 0xFFull)] = (int)(meta[q] >> 16) + __ffs((int)isu) - 1;
+            const unsigned f = h2_again4<L1>(t.b2, kk, (unsigned)(meta[q] >> 4) & 0xFu);
+            meta[q] |= (unsigned long long)f << FL;
+            nfl += __popc(f);
+        }
+        int qi;  // queue index of this lane's next entry, counted from the start of the round
+        const int qtotal = h2_prefix_dpp(nfl, qi);
+#pragma unroll 1
+        for (int left = qtotal; left > 0; left -= H2_QCAP) {  // uniform
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                if (64 * q >= P) continue;  // uniform
+                while ((meta[q] >> FL) != 0ull && qi < H2_QCAP) {
+                    const unsigned f = (unsigned)(meta[q] >> FL), b = f & (0u - f);  // the lowest flagged entry of the piece
+                    sc->qw[qi] = h2_pick4(w[q], b);
+                    sc->qr[qi] = (unsigned char)((int)((meta[q] >> 8) & 0xFFull) * NW + wid);  // (lane r of wave wid holds row r * NW + wid)
+                    meta[q] ^= (unsigned long long)b << FL;
+                    ++qi;
+                }
+            }
+            qn = left < H2_QCAP ? left : H2_QCAP;
+            drain();
+            if (__ballot(full) != 0ull) break;  // uniform over the wave: the unit is handed over, the rest of the queue is not looked at
+            qi -= H2_QCAP;
+        }
+    }
+    if (__syncthreads_or(full)) return false;  // the table or the list filled up: nothing is published, the block path takes the unit
+    // step C: c(w) for the occurrence of w in row r = the rows that hold w, less row r, less the rows adjacent to row r
+    const int cl_n = *cln;
+    const uint4 *exm4 = reinterpret_cast<const uint4 *>(exm), *adj4 = reinterpret_cast<const uint4 *>(adj);
+    for (int e = tid; e < cl_n; e += NT) {
+        const unsigned item = cl[e];
+        const int row = (int)(item >> 16);
+        const uint4 m = exm4[item & 0xFFFFu], a = adj4[row];
+        const int c = __popc(m.x & ~a.x) + __popc(m.y & ~a.y) + __popc(m.z & ~a.z) + __popc(m.w & ~a.w) - 1;
+        if (c > 0) {
+            atomicAdd(&pos[row], 1);
+            atomicMax(&mx[row], c);
+        }
+    }
+    __syncthreads();
+    if (k >= 0) {
+        const int rev = sc->rowRev[lane];
+        if (rev < 0 || rev >= g.cap_total) {
+            row_ok(g, make_int2(-1, rev), 33, u, k);  // adjacency not symmetric: report, never publish
+        } else {
+            const uint4 a = adj4[i];
+            const int T = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w);
+            rec[(int64_t)ru.x + i] = make_uint4((unsigned)pos[i], (unsigned)mx[i], h2_rec_t(T, ru.y), (unsigned)rev);
+        }
+    }
+    return true;
+}
+
 // A unit whose rows fit one batch (at most 64 per wave) and whose pieces fit NPB per lane: rows, descriptors and pieces
 // are read ONCE and stay in registers for all three sweeps (the streaming version pays the chain unit -> row of u -> rows'
 // descriptors -> pieces three times, with a handful of pieces per wave to hide it behind).  false: does not fit (decided
 // before anything is written; the caller streams).  `ok` is set like h2_node's return value.
+// Class M (one partition, four waves) tries the row-mask path first for a unit of at most H2_ROWS_MAX rows.
 constexpr int H2_NPB = 12;
 template <int L1, int EXS, int NW, bool PARTS>
 __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al, int u, int2 ru, int part, int nparts,
                                     const H2Tab t, H2Scratch *sc, uint4 *rec, bool &ok, H2List &ls) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
     constexpr int NT = 64 * NW, NP = H2_NPB;
+    constexpr bool ROWS = !PARTS && NW == 4 && EXS >= 4 * H2_ROWS_EXS;
     const unsigned long long below = (1ull << lane) - 1ull;
     if (ru.y > 64 * NW) return false;  // uniform
+    const bool rows = ROWS && ru.y <= H2_ROWS_MAX;  // uniform
     const int i = lane * NW + wid;
     int k = -1;
     int2 rk = make_int2(0, 0);
@@ -1573,16 +1736,23 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
     int poff_lane;
     const int P = h2_prefix(np, poff_lane);
     if (__syncthreads_or(P > 64 * NP)) return false;  // some wave's share is too long for the registers
-    {
+    // the bitmaps and the tables of the path named: the block path's (key empty, counts zero) or the row-mask path's, which lie in
+    // the same arrays (row masks zero where the keys are; exact keys empty, adjacency masks and row results zero where the counts are)
+    auto clear = [&](bool for_rows) {
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u), none = make_uint4(H2_EMPTY, H2_EMPTY, H2_EMPTY, H2_EMPTY);
         uint4 *z = reinterpret_cast<uint4 *>(t.b1);  // b1 and b2 are adjacent
         constexpr int NZ = ((1 << L1) / 32 + (1 << (L1 - 2)) / 32) / 4;
-        for (int j = tid; j < NZ; j += NT) z[j] = make_uint4(0u, 0u, 0u, 0u);
+        for (int j = tid; j < NZ; j += NT) z[j] = zero;
         uint4 *k4 = reinterpret_cast<uint4 *>(t.key);
-        for (int j = tid; j < EXS / 4; j += NT) k4[j] = make_uint4(H2_EMPTY, H2_EMPTY, H2_EMPTY, H2_EMPTY);
+        for (int j = tid; j < EXS / 4; j += NT) k4[j] = for_rows ? zero : none;
         uint4 *c4 = reinterpret_cast<uint4 *>(t.cnt);
-        for (int j = tid; j < EXS / 8; j += NT) c4[j] = make_uint4(0u, 0u, 0u, 0u);
-        if (tid == 0) *t.full = 0;
-    }
+        for (int j = tid; j < EXS / 8; j += NT) c4[j] = (for_rows && j < H2_ROWS_EXS / 4) ? none : zero;
+        if (tid == 0) {
+            *t.full = 0;
+            t.wsum[0] = 0;  // (the row-mask path's candidate count; the join writes its own before it reads)
+        }
+    };
+    clear(rows);
     sc->desc[lane] = rk;
     sc->poff[lane] = poff_lane;
     if (lane == 0) sc->poff[64] = P;
@@ -1607,12 +1777,23 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
         }
     }
     __syncthreads();  // the tables are cleared
-    if (k >= 0) {     // the members of N(u): flagged table entries (in every partition's tables)
+    // the members of N(u): flagged table entries (in every partition's tables); both paths seed the same bits into the bitmaps
+    auto seed_table = [&]() {
         const int sl = h2_insert<EXS>(t.key, (unsigned)k);
         if (sl < 0) *t.full = 1;
         else h2_cnt_flag(t.cnt, sl);
+    };
+    if (k >= 0) {
+        if (rows) {  // uniform: the row-mask path's exact table, flagged too, with the member's position in row u
+            const int sl = h2s_insert_nbr<H2_ROWS_EXS>(t.cnt, (unsigned)k);
+            if (sl < 0) *t.full = 1;
+            else t.key[4 * sl] = (unsigned)i;
+        } else {
+            seed_table();
+        }
         h2_seed<L1>(t.b1, t.b2, (unsigned)k);
     }
+    if (rows) sc->rowRev[lane] = -1;
     __syncthreads();
     // sweep A
 #pragma unroll
@@ -1629,6 +1810,31 @@ __device__ inline bool h2_node_fast(const View &g, const H2Tasks tk, H2Alloc &al
         h2_mark4<L1>(t.b1, t.b2, kk, valid);
     }
     __syncthreads();
+    if constexpr (ROWS) {
+        if (rows) {  // uniform
+            const bool done = h2_rows_unit<L1, EXS, NW, NP>(g, u, ru, i, k, P, w, meta, t, sc, rec);
+            if (tid == 0) atomicAdd(&h2_rows_units[done ? 0 : 1], 1u);
+            __syncthreads();  // the tables are rewritten: by the next unit, or right here
+            if (done) {
+                ok = true;
+                return true;
+            }
+            // Its table or its list filled up and nothing is published: the block path takes the unit — no retry, no fallback, the
+            // unit is counted where it would have been without the row-mask path.  Sweep A is common to both paths and B2 is as it
+            // left it (B1, the candidate list since, is dead on the block path as well: the join's cursors are written before they
+            // are read), so the block path starts from its own tables, cleared and seeded, and goes on with its sweep B.
+            {
+                uint4 *k4 = reinterpret_cast<uint4 *>(t.key);
+                for (int j = tid; j < EXS / 4; j += NT) k4[j] = make_uint4(H2_EMPTY, H2_EMPTY, H2_EMPTY, H2_EMPTY);
+                uint4 *c4 = reinterpret_cast<uint4 *>(t.cnt);
+                for (int j = tid; j < EXS / 8; j += NT) c4[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (tid == 0) *t.full = 0;
+            }
+            __syncthreads();
+            if (k >= 0) seed_table();
+            __syncthreads();
+        }
+    }
     // Sweep B: flagged entries are queued, the drain has one call site.  It lists its exact-path entries (slot and row) and
     // where u sits in each row; the third step is then one pass over that list (h2_settle_items) — unless the list overflowed:
     // that wave streams its rows for the third sweep (h2_stream, the path of the units that do not fit the registers).
@@ -1766,7 +1972,9 @@ __device__ inline bool h2_node(const View &g, const H2Tasks tk, H2Alloc &al, int
 
 // RETRY: the units come from the retry list (whose tables must not fill up again: the pass falls back then)
 // (at least three waves per SIMD: class M's fast path wanted 232 registers, i.e. two of its 4-wave workgroups per CU where its
-//  LDS lets three live; at 168 registers and 136 bytes of spills the pass is 2.6 % faster on S100k, 4.3 % on S1M)
+//  LDS lets three live; at 168 registers and 136 bytes of spills the pass was 2.6 % faster on S100k, 4.3 % on S1M.  With the
+//  row-mask path class M stands at 168 registers, 41 spilled and 192 bytes of scratch per lane, 23 and 96 before it:
+//  profiles/h2_rowmask_resources.txt, and profiles/h2_rowmask_ab.txt for what that costs the units of the other paths)
 template <int L1, int EXS, int NW, bool PARTS>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) k_h2_block(View g, H2Tasks tk, const int4 *units, const int32_t *count, int64_t unit_cap,
                                                        uint4 *rec, H2Retry rt, int is_retry) {
@@ -2517,3 +2725,12 @@ int h2_weight_check(dcr_graph *g, int64_t *mismatches) {
 }
 
 }  // namespace dcr
+
+// diagnostic, for tools/h2_rowmask_coverage.py alone (not part of include/dcr.h): the class-M units of the current device that
+// the row-mask path published (out[0]) and handed over to the block path (out[1]) since the last call; the counters start again.
+// Call it with the device idle.
+extern "C" int dcr_h2_rowmask_units(uint32_t out[2]) {
+    const unsigned zero[2] = {0u, 0u};
+    if (!out || hipMemcpyFromSymbol(out, HIP_SYMBOL(dcr::h2_rows_units), sizeof zero) != hipSuccess) return DCR_EHIP;
+    return hipMemcpyToSymbol(HIP_SYMBOL(dcr::h2_rows_units), zero, sizeof zero) == hipSuccess ? DCR_OK : DCR_EHIP;
+}
